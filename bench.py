@@ -7,9 +7,11 @@ random-init durations round to 0, fact 6), inputs already resident in HBM.  With
 (`--scaling weak`: B per GPU, the default; `--scaling strong`: B is the GLOBAL batch, B/N per GPU) and each step ends with the
 RCCL all-gather of the mel shards over xGMI, pipelined one step behind the compute on a side stream.
 
-Prints ONE JSON line (rank 0):
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints:
   value / ms_per_step    whole-job frames/s of the timed region (barrier + synchronize on both sides, max over ranks)
   roofline               the dominant kernel (fused mel decoder), timed live with HIP events on the launch stream
+With --full the line also carries every other leg (each takes runs of its own) and the parity gate of the headline:
+  parity_spot            two utterances of the timed batch against the CPU oracle, outside the timed region
   exact_fp32             (N=1) the same step on efficientspeech_amd/libesmi_fp32mfma.so: every contraction on
                          v_mfma_f32_32x32x2_f32, with its own kernel time and fraction of the 157.3 TFLOP/s fp32-MFMA peak
   decoder_only           (N=1) MelDecoder.forward alone on frame-rate features ~ N(0,1)
@@ -83,7 +85,16 @@ def parse():
     ap.add_argument("--event-every", type=int, default=5,
                     help="bracket every n-th mel-decoder launch of the timed region with HIP events for roofline.kernel_ms "
                          "(each event pair drains the queue: ~12 us per step when placed on every launch)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg of the line (parity gate, clock / pipes, encoder side, exact-fp32, "
+                         "decoder-only, small, base, vocoder, train step, CPU baseline; N > 1: all-gather, strong, base_strong, "
+                         "without_allgather); default: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step (mel, mel_len) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    return a
 
 
 def _omp_threads(n):
@@ -405,6 +416,26 @@ def timed_steps(pipe, net, x, steps, warmup, sync_all, event_every, graph):
     return dt, dec_ms, len(ev)
 
 
+DUMP_BYTES = 63_000_000      # --dump-outputs: array bytes in all (64 MB with the .npy headers)
+
+
+def dump_outputs(path, mel, mel_len):
+    """--dump-outputs: the (B, L, 80) mel batch and the (B,) mel lengths the timed path returned, as DIR/mel.npy (float32) and
+    DIR/mel_len.npy (float64).  A batch above DUMP_BYTES keeps a fixed seeded sample of its utterances, in batch order, and names them
+    in DIR/utterance_index.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    b = mel.shape[0]
+    per_utt = mel[0].numel() * 4 + 8
+    if b * per_utt > DUMP_BYTES:
+        keep = max(1, DUMP_BYTES // (per_utt + 8))           # mel rows + length + index of every kept utterance
+        idx = np.sort(np.random.default_rng(0).choice(b, size=keep, replace=False))
+        sel = torch.from_numpy(idx).to(mel.device)
+        mel, mel_len = mel.index_select(0, sel), mel_len.index_select(0, sel)
+        np.save(os.path.join(path, "utterance_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "mel.npy"), mel.float().cpu().numpy())
+    np.save(os.path.join(path, "mel_len.npy"), mel_len.cpu().numpy().astype(np.float64))
+
+
 def _self_launch(n):
     """`python bench.py --gpus N` without a launcher (no WORLD_SIZE in the environment): become
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same arguments>` -- one rank per
@@ -501,7 +532,12 @@ def main():
             pipe, a.two_stream = alt, True
         launch_note = f"; warm-up trial: eager {t_eager * 1e3:.3f} ms/step, two-stream {t_two * 1e3:.3f} ms/step"
     dt, dec_ms, n_ev = timed_steps(pipe, net, x, a.steps, a.warmup, sync_all, a.event_every, a.graph)
-    if a.two_stream and world == 1:
+    if a.dump_outputs and rank == 0:
+        pipe.wait_last()
+        dump_outputs(a.dump_outputs, *pipe.last)
+    if a.two_stream and world == 1 and not a.full:
+        launch_note += "; roofline kernel_ms from the two-stream timed steps (--full: from a single-stream run)"
+    elif a.two_stream and world == 1:
         # with the encoder side of step i+1 running beside it, the decoder's event-timed duration is not the kernel's own: time
         # the kernel for the roofline in a short single-stream run (the step time above stays the two-stream one)
         solo = ShardedMelPipeline(net, world_size=1, gather=False)
@@ -582,7 +618,7 @@ def main():
                              "= 0.0 %, below the 8 % bar: stopped"},
     }
 
-    if rank == 0:
+    if rank == 0 and a.full:
         # ---- parity gate of the headline (outside the timed region): two utterances of the timed batch against the CPU oracle
         try:
             out["parity_spot"] = parity_spot(net, x, cfg, sd)
@@ -591,7 +627,7 @@ def main():
                 out["value_unverified"], out["value"] = out["value"], None
         except Exception as e:                     # noqa: BLE001
             out["parity_spot"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not a.exact_fp32:
+    if rank == 0 and world == 1 and not a.exact_fp32 and a.full:
         # ---- what the decoder kernel's time consists of, in the line itself: the clock the chip actually ran it
         # at (measured inside the kernel), `frac` re-priced at that clock, and the busy fraction of each pipe from the committed PMC pass
         try:
@@ -612,7 +648,7 @@ def main():
         except Exception as e:                     # noqa: BLE001
             out["encoder_side"] = {"error": repr(e)}
 
-    if world > 1 and pipe.gather:
+    if world > 1 and pipe.gather and a.full:
         # the exchange by itself: all-gather of one step's mel shards (what every step hides behind the next step's compute)
         mel_shard = torch.randn((B, L, cfg.n_mel_channels), device=dev)
         full = torch.empty((B * world, L, cfg.n_mel_channels), device=dev)
@@ -632,7 +668,7 @@ def main():
                             "note": "all_gather_into_tensor of the (B, L, 80) fp32 mel shards alone, blocking; in the timed steps it "
                                     "runs on a side stream under the next step's compute"}
 
-    if world > 1 and pipe.gather:
+    if world > 1 and pipe.gather and a.full:
         # the same steps with the exchange switched off: what the shards compute when nobody collects the mels.  Every rank
         # RECEIVES (N-1) x 62.9 MB per step in the timed region above, so its rate is capped by its xGMI ingress
         # (7 links x 76.8 GB/s / 320 B per frame = 1.7e9 frames/s per rank whatever N is); this line separates the two.
@@ -682,7 +718,7 @@ def main():
             res = gate(res, spot2)
         return res, net2, x2, cfg2, sd2
 
-    if world > 1 and not a.no_extras and a.config == "tiny" and a.scaling == "weak":
+    if world > 1 and a.full and not a.no_extras and a.config == "tiny" and a.scaling == "weak":
         # north_star asks for both: the headline above is weak scaling (B per GPU fixed); here the headline's GLOBAL batch is split
         # over the ranks (32 utterances per GPU at N = 8: bounded by the encoder side's latency chain), and BASELINE configs[3]
         # (base ES, B = 512 x T = 256 over the node).  Collectives inside: every rank runs them or none does.
@@ -904,7 +940,7 @@ def main():
                               "note": "synthetic seeded generator weights; 20 launches (one per ResBlock, csrc/hifigan_resblock.h); "
                                       "text_to_wav = acoustic model and vocoder back to back on one GPU"}
             del voc, wav, mel_v
-    if rank == 0 and world == 1 and not a.no_extras:
+    if rank == 0 and world == 1 and a.full and not a.no_extras:
         try:                                   # an optional leg must never cost the headline line
             _single_gpu_extras()
         except Exception as e:                 # noqa: BLE001
@@ -982,7 +1018,7 @@ def main():
                                      "(efficientspeech_amd/train.py; esmi_train_* kernels); synthetic teacher-forced batch, D-const "
                                      "durations; data-parallel: one all-reduce of the flat fp32 gradient buffer"}
         del tnet, ts
-    if not a.no_extras and not a.exact_fp32:
+    if a.full and not a.no_extras and not a.exact_fp32:
         if world == 1:
             try:
                 _train_leg()
@@ -1016,7 +1052,7 @@ def main():
             finally:
                 done_evt.set()
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(cfg, sd, T, a.dur)
             except Exception as e:                 # noqa: BLE001  (e.g. no C compiler on the box: the headline line still prints)

@@ -8,8 +8,8 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 300 python $REPO/bench.py "$@" > $OUT/bench_unprofiled.json 2> $OUT/bench_unprofiled.err < /dev/null
-PROF_ARGS="--no-cpu-baseline --no-extras --no-auto-launch"
+timeout 300 python $REPO/bench.py --full "$@" > $OUT/bench_unprofiled.json 2> $OUT/bench_unprofiled.err < /dev/null
+PROF_ARGS="--full --no-cpu-baseline --no-extras --no-auto-launch"
 timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o r -- \
     python $REPO/bench.py --steps 10 --warmup 3 --event-every 1 $PROF_ARGS "$@" > $OUT/stats.log 2>&1 < /dev/null
 if [ "${PMC:-1}" == "1" ]; then

@@ -6,7 +6,7 @@ OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for grp in "$@"; do
   name=pmc_$(echo $grp | cut -d' ' -f1)
-  timeout 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT/$name -o r -- python $REPO/bench.py --steps 3 --warmup 2 --no-cpu-baseline > $OUT/$name.log 2>&1
+  timeout 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT/$name -o r -- python $REPO/bench.py --steps 3 --warmup 2 --full --no-cpu-baseline > $OUT/$name.log 2>&1
 done
 cd $REPO; python tools/prof_summary.py $OUT > /dev/null 2>&1
 python - <<PY

@@ -9,7 +9,7 @@ for lib in "$@"; do
   name=$(basename $lib .so)
   for grp in FETCH_SIZE WRITE_SIZE; do
     ESMI_LIB=$REPO/$lib timeout 200 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT/$name/$grp -o r -- \
-        python $REPO/bench.py --config $CFG --steps 3 --warmup 2 --no-cpu-baseline --no-extras --no-auto-launch > $OUT/$name.$grp.log 2>&1 < /dev/null
+        python $REPO/bench.py --config $CFG --steps 3 --warmup 2 --full --no-cpu-baseline --no-extras --no-auto-launch > $OUT/$name.$grp.log 2>&1 < /dev/null
   done
 done
 python - $OUT "$@" <<'PY'
