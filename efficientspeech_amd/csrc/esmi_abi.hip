@@ -10,20 +10,7 @@ ESMI_TU_RANGE_SETTER(abi)
 
 namespace {
 
-// does the fused Fuse + variance-adaptor chain kernel serve this call?  (needs the packed weights and one of its instantiations)
-bool fuse_va_chain_ok(const esmi_fuse_weights* fw, int depth, int dim, int kernel, int n0, int T, const esmi_predictor_weights* pitch,
-                      const esmi_predictor_weights* energy, const esmi_predictor_weights* duration, int plan) {
-    bool chain = (plan & ESMI_FUSE_VARIANCE) && (dim == 32 || dim == 64) && (kernel == 3 || kernel == 5) && n0 == T && fw->fuse_wp &&
-                 pitch->conv1_wp && pitch->conv2_wp && energy->conv1_wp && energy->conv2_wp && duration->conv1_wp &&
-                 duration->conv2_wp;
-    for (int i = 0; i < depth && chain; ++i) chain = fw->mlp_wp[i] && (i == 0 || fw->up_wp[i]);
-    return chain;
-}
-// ... and can it also produce the mel decoder's first stage at phoneme rate?
-bool fuse_va_head_ok(bool chain, int dim, const esmi_decoder_head* head) {
-    return chain && head && head->proj_wp && dim == 32 && head->d4 == 128 && head->dx2 == 128;
-}
-// ... or can the stage run as its own phoneme-rate GEMM launch (esmi_decoder_head_f32) behind the variance adaptor?
+// can the mel decoder's first stage run as its own phoneme-rate GEMM launch (esmi_decoder_head_f32)?
 bool head_gemm_ok(const esmi_decoder_head* head) {
     return head && head->proj_w && head->proj_b && head->ln_g && head->ln_b && head->d4 > 0 && (head->d4 & 7) == 0 &&
            (head->dx2 == 32 || head->dx2 == 64 || head->dx2 == 128 || head->dx2 == 256);
@@ -144,30 +131,57 @@ int esmi_pool_mask_u8(const uint8_t* mask, int B, int T, int pool, uint8_t* out,
 
 size_t esmi_encoder_block_workspace_bytes(const esmi_encoder_block_shape* s) { return s ? enc_ws(s).total : 0; }
 
-// The parameters of a whole encoder block as ONE folded chain-kernel launch (what esmi_encoder_block_f32 below hands
-// launch_enc_block16 / launch_enc_block), for the one-launch encoder side of the one-call forward; false when the block's packed / folded
-// weights are not all there.
-static bool block_chain_params(const esmi_encoder_block_weights* w, const esmi_encoder_block_shape* s, const int32_t* ids, const float* embed,
-                               const float* x_in, const uint8_t* mask, float* x_out, EncAttnFfnP* out) {
-    const bool ffn_folded = w->ffn_cw && w->ffn_cwp && w->ffn_cb && w->ffn_cb_first && w->ffn_cb_last;
-    if (!(w->merge_cwp && w->qkv_wp && w->proj_wp && ffn_folded && w->mlp2_wp && w->qk_wp && w->vo_wp)) return false;
+// ------------------------------------------------------------------ encoder side: which kernel serves which shape
+// Each stage tries its candidates best first; a launcher answers ESMI_ERR_UNSUPPORTED for a shape it is not built for and the next
+// candidate runs.  What serves the published models under launch plan 63:
+//   stage                     candidates, in order                               serves
+//   whole encoder side        enc_all16 (one-call forward)                       tiny ES (dim 32, MixFFN expansion 1), T <= 128
+//   block, whole              enc_block16 > enc_block                            tiny ES blocks (module path); small ES block 0, N <= 128
+//   block, front              enc_merge_q256 > enc_merge_qkv > per-op            base ES block 1 > every other packed block
+//   block, back               enc_attn_ffn (chosen with the front, N <= 128)     small ES block 1; base ES block 0, N <= 128
+//                             attention, then enc_post_attn64 | enc_post_attn128 small ES block 0 | base ES block 0, 128 < N <= 256
+//                             > per-op GEMMs                                     base ES block 1; tiny ES block 0 at T > 128; N > 256
+//   Fuse + variance adaptor   enc_va16 > enc_va64 > enc_fuse_va                  tiny ES (dim 32) > small ES (dim 64), T <= 256 > longer
+//                             enc_fuse128, enc_pred128 > per-op                  base ES (dim 128), T <= 256 > everything else
+// A candidate that cannot serve the shape leaves the stage to the next one; any other return code ends the call.
+#define ESMI_TRY(eligible, launch)                            \
+    if (eligible) {                                           \
+        const int rc_ = (launch);                             \
+        if (rc_ != ESMI_ERR_UNSUPPORTED) return rc_;          \
+    }
+
+namespace {
+
+bool ffn_folded(const esmi_encoder_block_weights* w) { return w->ffn_cw && w->ffn_cwp && w->ffn_cb && w->ffn_cb_first && w->ffn_cb_last; }
+// the pre-split weights the chain kernels of a block read (merge convs composed, q / k / v, projection, folded MixFFN, mlp2)
+bool block_packed(const esmi_encoder_block_weights* w) { return w->merge_cwp && w->qkv_wp && w->proj_wp && ffn_folded(w) && w->mlp2_wp; }
+
+// The chain kernels' parameters of one block: the merge / qkv stage (f.m) and everything behind the attention.  x_mid / qkv: the block
+// input after the merge convs and the q / k / v rows when they travel between two launches (nullptr when one launch does the block).
+EncAttnFfnP block_params(const esmi_encoder_block_weights* w, const esmi_encoder_block_shape* s, const int32_t* ids, const float* embed,
+                         const float* x_in, const uint8_t* mask, float* x_mid, float* qkv, float* x_out) {
     const int n = conv_out_len(s->n_in, s->kernel, s->stride, s->kernel / 2);
     EncAttnFfnP f;
     memset(&f, 0, sizeof f);
     EncMergeP& m = f.m;
     m.ids = ids; m.table = embed; m.vocab = s->vocab; m.x_in = ids ? nullptr : x_in;
     m.B = s->B; m.n_in = s->n_in; m.n_out = n; m.k = s->kernel; m.stride = s->stride; m.pad = s->kernel / 2; m.h = s->heads;
-    m.merge_w = w->merge_cwp; m.qkv_w = w->qk_wp; m.emb_conv = ids ? w->emb_conv : nullptr; m.tiles_per_b = (n + 31) / 32;
-    f.B = s->B; f.N = n; f.C = s->c_out; f.h = s->heads; f.scale = 1.0f / sqrtf((float)(s->c_out / s->heads));
-    f.proj_w = w->vo_wp; f.proj_b = w->proj_b; f.ln1_g = w->ln1_g; f.ln1_b = w->ln1_b;
+    m.merge_w = w->merge_cwp; m.qkv_w = w->qkv_wp; m.x_out = x_mid; m.qkv = qkv; m.emb_conv = ids ? w->emb_conv : nullptr;
+    m.tiles_per_b = (n + 31) / 32;
+    f.x = x_mid; f.qkv = qkv; f.B = s->B; f.N = n; f.C = s->c_out; f.h = s->heads; f.scale = 1.0f / sqrtf((float)(s->c_out / s->heads));
+    f.proj_w = w->proj_wp; f.proj_b = w->proj_b; f.ln1_g = w->ln1_g; f.ln1_b = w->ln1_b;
     f.ffn_w = w->ffn_cwp; f.ffn_b = w->ffn_cb; f.ffn_b0 = w->ffn_cb_first; f.ffn_b2 = w->ffn_cb_last;
     f.mlp2_w = w->mlp2_wp; f.mlp2_b = w->mlp2_b; f.ln2_g = w->ln2_g; f.ln2_b = w->ln2_b;
     f.mask = mask; f.out = x_out;
     f.mask_pool = s->mask_pool > 0 ? s->mask_pool : 1; f.mask_len = s->mask_pool > 0 ? s->mask_len : n;
-    f.fold = 1; f.wgs_per_b = 1; f.halo = 0;
-    *out = f;
-    return true;
+    return f;
 }
+// ... with the whole-block kernels' weight-folded attention: a third of the q / k / v contraction
+void fold_attention(const esmi_encoder_block_weights* w, EncAttnFfnP* f) {
+    f->fold = 1; f->m.qkv_w = w->qk_wp; f->m.nq_override = 0; f->proj_w = w->vo_wp;
+}
+
+}  // namespace
 
 int esmi_encoder_block_f32(const esmi_encoder_block_weights* w, const esmi_encoder_block_shape* s, const int32_t* ids,
                            const float* embed, const float* x_in, const uint8_t* mask, float* x_out, void* workspace,
@@ -175,6 +189,7 @@ int esmi_encoder_block_f32(const esmi_encoder_block_weights* w, const esmi_encod
     if (!w || !s || !x_out || !workspace) return ESMI_ERR_ARG;
     if (!ids && !x_in) return ESMI_ERR_ARG;
     const int plan = s->plan & ESMI_FUSE_ALL;
+    const bool chain16 = plan & ESMI_FUSE_CHAIN16;
     const EncWs ws = enc_ws(s);
     if (workspace_bytes < ws.total) return ESMI_ERR_WORKSPACE;
     char* wsb = static_cast<char*>(workspace);
@@ -188,67 +203,43 @@ int esmi_encoder_block_f32(const esmi_encoder_block_weights* w, const esmi_encod
     const int n = conv_out_len(s->n_in, s->kernel, s->stride, s->kernel / 2);
     hipStream_t st = S(stream);
     int rc;
-    ConvGemmP p = conv_defaults();
-    bool fused1 = false;
-    // With the fused second stage, x (the block input after the merge convs) lives in scratch and the final
-    // result is written straight to x_out: tiles read their neighbours' x rows, so in-place is not possible.
-    const bool ffn_folded = w->ffn_cw && w->ffn_cwp && w->ffn_cb && w->ffn_cb_first && w->ffn_cb_last;
-    const bool packed = w->merge_cwp && w->qkv_wp && w->proj_wp && ffn_folded && w->mlp2_wp;
-    const bool fused2 = packed && (plan & ESMI_FUSE_ATTN_FFN) && enc_attn_ffn_supported(C, n, s->expansion);
-    float* x_mid = fused2 ? y1 : x_out;
+    const bool packed = block_packed(w);
+    // enc_attn_ffn behind the front: x (the block input after the merge convs) lives in scratch and the result goes straight to x_out
+    // (tiles read their neighbours' x rows, so in place is not possible)
+    const bool attn_ffn = packed && (plan & ESMI_FUSE_ATTN_FFN) && enc_attn_ffn_supported(C, n, s->expansion);
+    float* x_mid = attn_ffn ? y1 : x_out;
     // one-kernel-per-op attention with folded weights (esmi.h): the Linear behind the merge convs is x M (h*C wide) instead of qkv
-    const bool folded = !fused2 && h >= 2 && w->qk_w && w->qk_wp && w->vo_w && w->vo_wp;   // (one head: measured no gain per op; HISTORY.md 3.3)
+    const bool folded = !attn_ffn && h >= 2 && w->qk_w && w->qk_wp && w->vo_w && w->vo_wp;   // (one head: measured no gain per op; HISTORY.md 3.3)
     const int nq = folded ? h * C : 3 * h * C;
-    EncMergeP m;
-    memset(&m, 0, sizeof m);
-    m.ids = ids; m.table = embed; m.vocab = s->vocab; m.x_in = ids ? nullptr : x_in;
-    m.B = B; m.n_in = s->n_in; m.n_out = n; m.k = s->kernel; m.stride = s->stride; m.pad = s->kernel / 2; m.h = h;
-    m.merge_w = w->merge_cwp; m.qkv_w = folded ? w->qk_wp : w->qkv_wp; m.x_out = x_mid; m.qkv = qkv;
-    m.nq_override = folded ? nq : 0;
-    m.emb_conv = ids ? w->emb_conv : nullptr;
-    m.tiles_per_b = (n + 31) / 32;
-    EncAttnFfnP f;
-    memset(&f, 0, sizeof f);
-    f.x = x_mid; f.qkv = qkv; f.B = B; f.N = n; f.C = C; f.h = h; f.scale = 1.0f / sqrtf((float)(C / h));
-    f.proj_w = w->proj_wp; f.proj_b = w->proj_b; f.ln1_g = w->ln1_g; f.ln1_b = w->ln1_b;
-    f.ffn_w = w->ffn_cwp; f.ffn_b = w->ffn_cb; f.ffn_b0 = w->ffn_cb_first; f.ffn_b2 = w->ffn_cb_last;
-    f.mlp2_w = w->mlp2_wp; f.mlp2_b = w->mlp2_b; f.ln2_g = w->ln2_g; f.ln2_b = w->ln2_b;
-    f.mask = mask; f.out = x_out;
-    f.mask_pool = s->mask_pool > 0 ? s->mask_pool : 1; f.mask_len = s->mask_pool > 0 ? s->mask_len : n;
-    if (fused2 && (plan & ESMI_FUSE_MERGE_QKV) && (plan & ESMI_FUSE_BLOCK)) {   // the whole block in one launch
+    const EncAttnFfnP f = block_params(w, s, ids, embed, x_in, mask, x_mid, qkv, x_out);
+
+    // ---- the whole block in one launch
+    if (attn_ffn && (plan & ESMI_FUSE_MERGE_QKV) && (plan & ESMI_FUSE_BLOCK)) {
         EncAttnFfnP fb = f;
-        fb.m = m;
         fb.x = nullptr; fb.qkv = nullptr;
-        if (w->qk_wp && w->vo_wp) {   // weight-folded attention inside the whole-block kernels: a third of the q / k / v contraction
-            fb.fold = 1; fb.m.qkv_w = w->qk_wp; fb.m.nq_override = 0; fb.proj_w = w->vo_wp;
+        if (w->qk_wp && w->vo_wp) fold_attention(w, &fb);
+        ESMI_TRY(chain16, launch_enc_block16(fb, s->expansion, s->c_in, st))
+        ESMI_TRY(true, launch_enc_block(fb, s->expansion, s->c_in, plan & ESMI_FUSE_SPLIT2, st))
+    }
+
+    // ---- front: merge convs + the q / k / v GEMM (folded: q) -> x_mid, qkv
+    auto front = [&]() -> int {
+        ESMI_TRY(chain16 && folded && !ids && x_in && s->c_in == 128 && C == 256 && s->stride == 2 && n <= 128 && w->merge_cwp,
+                 launch_enc_merge_q256(MergeQ256P{x_in, x_mid, qkv, w->merge_cwp, w->qk_wp, B, s->n_in, n, s->kernel, h}, st))
+        if (packed && (plan & ESMI_FUSE_MERGE_QKV)) {
+            EncMergeP m = f.m;
+            if (folded) { m.qkv_w = w->qk_wp; m.nq_override = nq; }
+            ESMI_TRY(true, launch_enc_merge_qkv(m, s->c_in, C, st))
         }
-        rc = (plan & ESMI_FUSE_CHAIN16) ? launch_enc_block16(fb, s->expansion, s->c_in, st) : ESMI_ERR_UNSUPPORTED;
-        if (rc == ESMI_ERR_UNSUPPORTED) rc = launch_enc_block(fb, s->expansion, s->c_in, plan, st);
-        if (rc != ESMI_ERR_UNSUPPORTED) return rc;
-    }
-    if ((plan & ESMI_FUSE_CHAIN16) && folded && !ids && x_in && s->c_in == 128 && C == 256 && s->stride == 2 && n <= 128 && w->merge_cwp) {
-        // round 6: base ES's block 1 front (enc_merge256.h) -- the strided merge convolution and the folded attention's query GEMM in ONE launch
-        MergeQ256P q;
-        q.x_in = x_in; q.x_out = x_mid; q.q = qkv; q.merge_w = w->merge_cwp; q.q_w = w->qk_wp; q.B = B; q.n_in = s->n_in; q.n_out = n;
-        q.kernel = s->kernel; q.heads = h;
-        rc = launch_enc_merge_q256(q, st);
-        if (rc == ESMI_OK) fused1 = true;
-        else if (rc != ESMI_ERR_UNSUPPORTED) return rc;
-    }
-    if (!fused1 && packed && (plan & ESMI_FUSE_MERGE_QKV)) {   // E1: merge conv + 1x1 + qkv as one wave-chain kernel
-        rc = launch_enc_merge_qkv(m, s->c_in, C, st);
-        if (rc == ESMI_OK) fused1 = true;
-        else if (rc != ESMI_ERR_UNSUPPORTED) return rc;
-    }
-    if (!fused1) {
         // merge conv k x k (dense, bias-free), networks.py:64-66
+        ConvGemmP p = conv_defaults();
         p.B = B; p.n_in = s->n_in; p.c_in = s->c_in; p.n_out = n; p.c_out = s->c_in;
         p.k = s->kernel; p.stride = s->stride; p.pad = s->kernel / 2;
         if (ids) { p.ids = ids; p.table = embed; p.ld_table = s->c_in; p.vocab = s->vocab; }
         else { p.A = x_in; p.lda = s->c_in; }
         if (ESMI_CHAIN_SPLIT && w->merge_cwp && (s->c_in & 31) == 0) {   // (the exact-fp32 build's GEMMs read fp32 weights)
             // both merge convolutions as ONE launch on the composed, pre-split weights the chain kernels use (merge_cwp: k x k conv . 1x1,
-            // esmi_compose_merge_f32 -> esmi_pack_bfrag_f32): no t_merge round trip, no weight split per wave (round 5)
+            // esmi_compose_merge_f32 -> esmi_pack_bfrag_f32): no t_merge round trip, no weight split per wave
             p.c_out = C; p.W = nullptr; p.Wp = w->merge_cwp; p.out = x_mid; p.ldo = C;
             if ((rc = launch_convgemm(p, st))) return rc;
         } else {
@@ -264,11 +255,12 @@ int esmi_encoder_block_f32(const esmi_encoder_block_weights* w, const esmi_encod
         p = conv_defaults();
         p.B = B; p.n_in = n; p.c_in = C; p.n_out = n; p.c_out = nq;
         p.A = x_mid; p.lda = C; p.W = folded ? w->qk_w : w->qkv_w; p.Wp = folded ? w->qk_wp : w->qkv_wp; p.out = qkv; p.ldo = nq;
-        if ((rc = launch_convgemm(p, st))) return rc;
-    }
-    if (fused2) {   // E2: attention + proj + LN1 + MixFFN + LN2 as one wave-chain kernel
-        return launch_enc_attn_ffn(f, s->expansion, plan, st);
-    }
+        return launch_convgemm(p, st);
+    };
+    if ((rc = front())) return rc;
+
+    // ---- back: attention + proj + LN1 + MixFFN + LN2 -> x_out
+    if (attn_ffn) return launch_enc_attn_ffn(f, s->expansion, plan & ESMI_FUSE_SPLIT2, st);   // (the front wrote x to y1 for it)
     if (mask && s->mask_pool > 1) {   // the one-kernel-per-op plan takes a pooled (B, n) mask: blocks.py:51-57
         uint8_t* pm = reinterpret_cast<uint8_t*>(wsb + ws.pmask);
         if ((rc = esmi_pool_mask_u8(mask, B, s->mask_len, s->mask_pool, pm, n, stream))) return rc;
@@ -285,33 +277,22 @@ int esmi_encoder_block_f32(const esmi_encoder_block_weights* w, const esmi_encod
         a.qkv = qkv;
     }
     if ((rc = launch_attn(a, st))) return rc;
-    if ((plan & ESMI_FUSE_CHAIN16) && packed && !folded && C == 64 && h == 1 && s->expansion == 1 && n <= 256) {
-        // round 6: everything behind the attention in ONE launch (enc_ffn64.h) instead of three GEMM launches through HBM
-        PostAttn64P q;
-        q.ctx = ctx; q.x = x_out; q.out = x_out; q.proj_w = w->proj_wp; q.ffn_w = w->ffn_cwp; q.mlp2_w = w->mlp2_wp;
-        q.proj_b = w->proj_b; q.ln1_g = w->ln1_g; q.ln1_b = w->ln1_b; q.ffn_b = w->ffn_cb; q.ffn_b0 = w->ffn_cb_first; q.ffn_b2 = w->ffn_cb_last;
-        q.mlp2_b = w->mlp2_b; q.ln2_g = w->ln2_g; q.ln2_b = w->ln2_b; q.rowmask = mask; q.B = B; q.N = n;
-        rc = launch_enc_post_attn64(q, st);
-        if (rc != ESMI_ERR_UNSUPPORTED) return rc;
-    }
-    if ((plan & ESMI_FUSE_CHAIN16) && packed && folded && ffn_folded && C == 128 && h == 2 && s->expansion == 2 && n <= 256) {
-        // round 6: the same for base ES's block 0 (enc_ffn128.h): ctx = the two heads' P_h x, the projection is the folded [Wv_h^T Wp_h^T]
-        PostAttn128P q;
-        q.ctx = ctx; q.x = x_out; q.y1 = y1; q.out = x_out; q.proj_w = w->vo_wp; q.ffn_w = w->ffn_cwp; q.mlp2_w = w->mlp2_wp;
-        q.proj_b = w->proj_b; q.ln1_g = w->ln1_g; q.ln1_b = w->ln1_b; q.ffn_b = w->ffn_cb; q.ffn_b0 = w->ffn_cb_first; q.ffn_b2 = w->ffn_cb_last;
-        q.mlp2_b = w->mlp2_b; q.ln2_g = w->ln2_g; q.ln2_b = w->ln2_b; q.rowmask = mask; q.B = B; q.N = n;
-        rc = launch_enc_post_attn128(q, st);
-        if (rc != ESMI_ERR_UNSUPPORTED) return rc;
-    }
+    // everything behind the attention in one launch; folded (enc_ffn128.h): ctx = the heads' P_h x, the projection is [Wv_h^T Wp_h^T]
+    ESMI_TRY(chain16 && packed && !folded && C == 64 && h == 1 && s->expansion == 1 && n <= 256,
+             launch_enc_post_attn64(PostAttn64P{ctx, x_out, x_out, w->proj_wp, w->ffn_cwp, w->mlp2_wp, w->proj_b, w->ln1_g, w->ln1_b, w->ffn_cb,
+                                                w->ffn_cb_first, w->ffn_cb_last, w->mlp2_b, w->ln2_g, w->ln2_b, mask, B, n}, st))
+    ESMI_TRY(chain16 && packed && folded && C == 128 && h == 2 && s->expansion == 2 && n <= 256,
+             launch_enc_post_attn128(PostAttn128P{ctx, x_out, y1, x_out, w->vo_wp, w->ffn_cwp, w->mlp2_wp, w->proj_b, w->ln1_g, w->ln1_b,
+                                                  w->ffn_cb, w->ffn_cb_first, w->ffn_cb_last, w->mlp2_b, w->ln2_g, w->ln2_b, mask, B, n}, st))
     // proj + residual + LN1 + mask, blocks.py:65 + networks.py:73-75  (folded: ctx holds P_h x, the matrix is [O_h])
-    p = conv_defaults();
+    ConvGemmP p = conv_defaults();
     p.B = B; p.n_in = n; p.c_in = h * C; p.n_out = n; p.c_out = C;
     p.A = ctx; p.lda = h * C; p.W = folded ? w->vo_w : w->proj_w; p.Wp = folded ? w->vo_wp : w->proj_wp; p.bias = w->proj_b;
     p.res = x_out; p.ldr = C; p.ln_g = w->ln1_g; p.ln_b = w->ln1_b; p.rowmask = mask;
     p.out = y1; p.ldo = C;
     if ((rc = launch_convgemm(p, st))) return rc;
     // MixFFN, blocks.py:22-29
-    if (ffn_folded) {   // Linear folded into the k = 3 conv (esmi.h, ffn_cw): one contraction C -> E, position-dependent bias at the two ends
+    if (ffn_folded(w)) {   // Linear folded into the k = 3 conv (esmi.h, ffn_cw): one contraction C -> E, position-dependent bias at the two ends
         p = conv_defaults();
         p.B = B; p.n_in = n; p.c_in = C; p.n_out = n; p.c_out = E; p.k = 3; p.pad = 1;
         p.A = y1; p.lda = C; p.W = w->ffn_cw; p.Wp = w->ffn_cwp; p.bias = w->ffn_cb; p.bias_first = w->ffn_cb_first; p.bias_last = w->ffn_cb_last;
@@ -428,49 +409,176 @@ size_t esmi_fuse_variance_adaptor_workspace_bytes(int B, int T, int dim, int dep
     return esmi_fuse_workspace_bytes(B, T, dim, depth) + esmi_variance_adaptor_workspace_bytes(B, T, dim);
 }
 
-// the chain kernels' parameter block of the fused Fuse + variance adaptor stage (enc_fuse_va_kernel / enc_va16_kernel)
-static void fuse_va_chain_params(const esmi_fuse_weights* fw, int depth, int dim, int kernel, int B, int T, const float* const* feats,
-                                 const int* n_i, const esmi_predictor_weights* pitch, const esmi_predictor_weights* energy,
-                                 const esmi_predictor_weights* duration, const uint8_t* mask, const float* pitch_target,
-                                 const float* energy_target, const int32_t* duration_target, float* feat, float* pitch_pred,
-                                 float* energy_pred, float* duration_pred, int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur,
-                                 int32_t* cum, int32_t* mel_len, const esmi_decoder_head* head_in_chain, float* h0, FuseVaP* out, int* nw) {
-    FuseVaP p;
-    memset(&p, 0, sizeof p);
-    p.B = B; p.T = T; p.depth = depth; p.kernel = kernel;
-    for (int i = 0; i < depth; ++i) {
-        p.feats[i] = feats[i]; p.n_i[i] = n_i[i];
-        p.mlp_w[i] = fw->mlp_wp[i]; p.mlp_b[i] = fw->mlp_b[i]; p.up_w[i] = fw->up_wp[i]; p.up_b[i] = fw->up_b[i];
-    }
-    p.fuse_w = fw->fuse_wp; p.fuse_b = fw->fuse_b;
-    const esmi_predictor_weights* pw[3] = {pitch, energy, duration};
-    for (int q = 0; q < 3; ++q) {
-        PredW& d = p.pred[q];
-        d.conv1_w = pw[q]->conv1_wp; d.conv1_b = pw[q]->conv1_b; d.ln1_g = pw[q]->ln1_g; d.ln1_b = pw[q]->ln1_b;
-        d.conv2_w = pw[q]->conv2_wp; d.conv2_b = pw[q]->conv2_b; d.ln2_g = pw[q]->ln2_g; d.ln2_b = pw[q]->ln2_b;
-        d.lin_w = pw[q]->lin_w; d.lin_b = pw[q]->lin_b; d.bins = pw[q]->bins; d.emb = pw[q]->emb;
-    }
-    p.mask = mask; p.pitch_t = pitch_target; p.energy_t = energy_target; p.dur_t = duration_target;
-    p.feat = feat; p.preds[0] = pitch_pred; p.preds[1] = energy_pred; p.preds[2] = duration_pred;
-    p.pitch_idx = pitch_idx; p.energy_idx = energy_idx; p.dur = dur;
-    fuse_va_plan(T, dim, depth, nw, &p.wgs_per_b, &p.useful, &p.halo);
-    const bool scan_fused = cum && p.halo == 0;   // one workgroup sees every duration of its utterance
-    p.cum = scan_fused ? cum : nullptr; p.mel_len = scan_fused ? mel_len : nullptr;
-    if (head_in_chain) { p.head_w = head_in_chain->proj_wp; p.head_b = head_in_chain->proj_b; p.head_g = head_in_chain->ln_g; p.head_beta = head_in_chain->ln_b; p.h0 = h0; }
-    *out = p;
+namespace {
+
+// the Fuse + variance-adaptor stage's arguments (esmi_fuse_variance_adaptor_f32's, and the one-call forward's)
+struct VaArgs {
+    const esmi_fuse_weights* fw;
+    int depth, dim, kernel, B, T;
+    const float* const* feats;
+    const int* n_i;
+    const esmi_predictor_weights* pw[3];   // pitch, energy, duration
+    const uint8_t* mask;
+    const float *pitch_t, *energy_t;
+    const int32_t* dur_t;
+    float *feat, *preds[3];
+    int32_t *pitch_idx, *energy_idx, *dur, *cum, *mel_len;
+    const esmi_decoder_head* head;
+    float* h0;
+    int plan;
+    void* workspace;
+    size_t workspace_bytes;
+    esmi_stream_t stream;
+    // the caller (the one-call inference forward) only consumes duration_pred / dur / cum / mel_len / h0: when a chain kernel produces
+    // h0, the phoneme-rate feature tensor, the pitch / energy predictions and the bucket indices are not written at all (16.8 MB of
+    // stores per tiny-ES batch that nobody reads: the decoder gathers h0)
+    bool lean;
+};
+
+// does the fused Fuse + variance-adaptor chain kernel family (enc_va16 / enc_va64 / enc_fuse_va) serve this call?  (packed weights)
+bool va_chain_ok(const VaArgs& a) {
+    if (!(a.plan & ESMI_FUSE_VARIANCE) || (a.dim != 32 && a.dim != 64) || (a.kernel != 3 && a.kernel != 5) || a.n_i[0] != a.T || !a.fw->fuse_wp)
+        return false;
+    for (int q = 0; q < 3; ++q)
+        if (!a.pw[q]->conv1_wp || !a.pw[q]->conv2_wp) return false;
+    for (int i = 0; i < a.depth; ++i)
+        if (!a.fw->mlp_wp[i] || (i > 0 && !a.fw->up_wp[i])) return false;
+    return true;
 }
 
-// `lean`: the caller (the one-call inference forward) only consumes duration_pred / dur / cum / mel_len / h0 -- when the round-5 chain
-// kernel serves the shape and produces h0, the phoneme-rate feature tensor, the pitch / energy predictions and the bucket indices are
-// not written at all (16.8 MB of stores per tiny-ES batch that nobody reads: the decoder gathers h0)
-static int fuse_variance_adaptor(const esmi_fuse_weights* fw, int depth, int dim, int kernel, int B, int T,
-                                 const float* const* feats, const int* n_i, const esmi_predictor_weights* pitch,
-                                 const esmi_predictor_weights* energy, const esmi_predictor_weights* duration,
-                                 const uint8_t* mask, const float* pitch_target, const float* energy_target,
-                                 const int32_t* duration_target, float* feat, float* pitch_pred, float* energy_pred,
-                                 float* duration_pred, int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur,
-                                 int32_t* cum, int32_t* mel_len, const esmi_decoder_head* head, float* h0, int plan,
-                                 void* workspace, size_t workspace_bytes, esmi_stream_t stream, bool lean);
+// Where the mel decoder's first stage runs at phoneme rate: inside the chain kernel (dim 32 models), as its own GEMM launch behind the
+// variance adaptor (esmi_decoder_head_f32), or not at all (the decoder runs it at frame rate).
+enum class Head { none, in_chain, gemm };
+Head phoneme_rate_head(const VaArgs& a, const esmi_decoder_head* head) {
+    if (!head) return Head::none;
+    if (va_chain_ok(a) && head->proj_wp && a.dim == 32 && head->d4 == 128 && head->dx2 == 128) return Head::in_chain;
+    if (head_gemm_ok(head) && head->d4 == 4 * a.dim) return Head::gemm;
+    return Head::none;
+}
+
+void set_head(FuseVaP* p, const esmi_decoder_head* head, float* h0) {
+    p->head_w = head->proj_wp; p->head_b = head->proj_b; p->head_g = head->ln_g; p->head_beta = head->ln_b; p->h0 = h0;
+}
+void drop_unread_outputs(FuseVaP* p) {   // (VaArgs::lean)
+    p->feat = nullptr; p->preds[0] = p->preds[1] = nullptr; p->pitch_idx = p->energy_idx = nullptr;
+}
+
+// the Fuse part of the chain kernels' parameters
+FuseVaP fuse_params(const VaArgs& a) {
+    FuseVaP p;
+    memset(&p, 0, sizeof p);
+    p.B = a.B; p.T = a.T; p.depth = a.depth; p.kernel = a.kernel;
+    for (int i = 0; i < a.depth; ++i) {
+        p.feats[i] = a.feats[i]; p.n_i[i] = a.n_i[i];
+        p.mlp_w[i] = a.fw->mlp_wp[i]; p.mlp_b[i] = a.fw->mlp_b[i]; p.up_w[i] = a.fw->up_wp[i]; p.up_b[i] = a.fw->up_b[i];
+    }
+    p.fuse_w = a.fw->fuse_wp; p.fuse_b = a.fw->fuse_b; p.mask = a.mask; p.feat = a.feat;
+    return p;
+}
+void pred_weights(const VaArgs& a, PredW* out) {
+    for (int q = 0; q < 3; ++q) {
+        const esmi_predictor_weights* w = a.pw[q];
+        out[q] = PredW{w->conv1_wp, w->conv1_b, w->ln1_g, w->ln1_b, w->conv2_wp, w->conv2_b, w->ln2_g, w->ln2_b, w->lin_w, w->lin_b, w->bins, w->emb};
+    }
+}
+// ... and the whole parameter block of the Fuse + variance-adaptor chain kernels
+FuseVaP va_chain_params(const VaArgs& a, bool head_in_chain, int* nw) {
+    FuseVaP p = fuse_params(a);
+    pred_weights(a, p.pred);
+    p.pitch_t = a.pitch_t; p.energy_t = a.energy_t; p.dur_t = a.dur_t;
+    for (int q = 0; q < 3; ++q) p.preds[q] = a.preds[q];
+    p.pitch_idx = a.pitch_idx; p.energy_idx = a.energy_idx; p.dur = a.dur;
+    fuse_va_plan(a.T, a.dim, a.depth, nw, &p.wgs_per_b, &p.useful, &p.halo);
+    const bool scan_fused = a.cum && p.halo == 0;   // one workgroup sees every duration of its utterance
+    p.cum = scan_fused ? a.cum : nullptr; p.mel_len = scan_fused ? a.mel_len : nullptr;
+    if (head_in_chain) set_head(&p, a.head, a.h0);
+    return p;
+}
+
+// enc_pred128 DMA-loads every one of these for all three predictors (esmi.h lets a caller leave pitch / energy's ln2 NULL)
+bool pred128_weights_ok(const VaArgs& a) {
+    for (int q = 0; q < 3; ++q) {
+        const esmi_predictor_weights* w = a.pw[q];
+        if (!w->conv1_wp || !w->conv1_b || !w->ln1_g || !w->ln1_b || !w->conv2_wp || !w->conv2_b || !w->ln2_g || !w->ln2_b || !w->lin_w || !w->lin_b)
+            return false;
+    }
+    return true;
+}
+
+int fuse_variance_adaptor(const VaArgs& a) {
+    if ((a.cum == nullptr) != (a.mel_len == nullptr)) return ESMI_ERR_ARG;
+    if (a.h0 && (!a.head || (!a.head->proj_wp && !a.head->proj_w) || !a.head->proj_b || !a.head->ln_g || !a.head->ln_b)) return ESMI_ERR_ARG;
+    if (!a.fw || !a.feats || !a.n_i || !a.pw[0] || !a.pw[1] || !a.pw[2] || !a.feat || !a.preds[0] || !a.preds[1] || !a.preds[2] || !a.dur ||
+        a.depth < 1 || a.depth > ESMI_MAX_DEPTH)
+        return ESMI_ERR_ARG;
+    const Head head = a.h0 ? phoneme_rate_head(a, a.head) : Head::none;
+    if (a.h0 && head == Head::none) return ESMI_ERR_UNSUPPORTED;
+    const bool head_in_chain = head == Head::in_chain, chain16 = a.plan & ESMI_FUSE_CHAIN16;
+    hipStream_t st = S(a.stream);
+    bool head_done = head_in_chain;
+    int rc;
+    if (va_chain_ok(a)) {   // ---- the whole stage in one chain kernel
+        for (int i = 1; i < a.depth; ++i)
+            if ((a.n_i[i] - 1) * (1 << i) + a.kernel < a.T) return ESMI_ERR_UNSUPPORTED;   // torch.cat would raise in the reference
+        if (!a.pw[0]->bins || !a.pw[0]->emb || !a.pw[1]->bins || !a.pw[1]->emb) return ESMI_ERR_ARG;
+        int nw;
+        const FuseVaP p = va_chain_params(a, head_in_chain, &nw);
+        bool scan_done = p.cum != nullptr;
+        auto chain = [&]() -> int {
+            if (chain16 && scan_done == (a.cum != nullptr)) {
+                FuseVaP q = p;
+                if (a.lean && head_in_chain) drop_unread_outputs(&q);
+                ESMI_TRY(true, launch_enc_va16(q, a.dim, a.kernel, st))
+            }
+            if (chain16 && !head_in_chain) {
+                // dim = 64, T <= 256: one workgroup per utterance, so the length regulator's scan runs inside it -- and the decoder's
+                // phoneme-rate first stage too when the caller wants h0 (4 dim = dx2 = 256, pre-split weights)
+                FuseVaP q = p;
+                q.cum = a.cum; q.mel_len = a.mel_len;
+                const bool head64 = a.h0 && a.head->proj_wp && a.head->d4 == 4 * a.dim && a.head->dx2 == 4 * a.dim;
+                if (head64) {
+                    set_head(&q, a.head, a.h0);
+                    if (a.lean) drop_unread_outputs(&q);
+                }
+                const int rc64 = launch_enc_va64(q, a.dim, a.kernel, st);
+                if (rc64 == ESMI_OK) { scan_done = a.cum != nullptr; head_done = head64; }
+                if (rc64 != ESMI_ERR_UNSUPPORTED) return rc64;
+            }
+            return launch_enc_fuse_va(p, a.dim, a.kernel, nw, head_in_chain, st);
+        };
+        if ((rc = chain())) return rc;
+        if (a.cum && !scan_done) ESMI_LAUNCH(length_regulate_kernel, dim3(a.B), dim3(64), 0, st, a.dur, a.T, a.cum, a.mel_len, (int*)nullptr);
+    } else {                // ---- Fuse, then the three predictors + the variance adaptor's tail + the length regulator's scan
+        if (!a.workspace || a.workspace_bytes < esmi_fuse_variance_adaptor_workspace_bytes(a.B, a.T, a.dim, a.depth)) return ESMI_ERR_WORKSPACE;
+        const size_t fws = esmi_fuse_workspace_bytes(a.B, a.T, a.dim, a.depth);
+        const esmi_fuse_weights* fw = a.fw;
+        auto fuse = [&]() -> int {
+            ESMI_TRY(chain16 && a.dim == 128 && a.depth == 2 && fw->mlp_wp[0] && fw->mlp_wp[1] && fw->up_wp[1] && fw->fuse_wp,
+                     launch_enc_fuse128(fuse_params(a), a.dim, a.kernel, st))
+            return esmi_fuse_f32(fw, a.depth, a.dim, a.kernel, a.B, a.T, a.feats, a.n_i, a.mask, a.feat, 4 * a.dim, a.workspace, fws, a.stream);
+        };
+        auto predictors = [&]() -> int {
+            if (chain16 && a.dim == 128 && pred128_weights_ok(a)) {
+                Pred128P q{{}, a.mask, a.pitch_t, a.energy_t, a.dur_t, a.feat, {a.preds[0], a.preds[1], a.preds[2]}, a.pitch_idx, a.energy_idx,
+                           a.dur, a.cum, a.mel_len, a.B, a.T};
+                pred_weights(a, q.pred);
+                ESMI_TRY(true, launch_enc_pred128(q, a.dim, st))
+            }
+            const int r = esmi_variance_adaptor_f32(a.pw[0], a.pw[1], a.pw[2], a.dim, a.B, a.T, a.mask, a.pitch_t, a.energy_t, a.dur_t, a.feat,
+                                                    a.preds[0], a.preds[1], a.preds[2], a.pitch_idx, a.energy_idx, a.dur,
+                                                    static_cast<char*>(a.workspace) + fws, a.workspace_bytes - fws, a.stream);
+            if (r) return r;
+            if (a.cum) ESMI_LAUNCH(length_regulate_kernel, dim3(a.B), dim3(64), 0, st, a.dur, a.T, a.cum, a.mel_len, (int*)nullptr);
+            return ESMI_OK;
+        };
+        if ((rc = fuse()) || (rc = predictors())) return rc;
+    }
+    if (a.h0 && !head_done) return esmi_decoder_head_f32(a.head, (long)a.B * a.T, a.feat, a.h0, a.stream);
+    return launch_status();
+}
+
+}  // namespace
+
 int esmi_fuse_variance_adaptor_f32(const esmi_fuse_weights* fw, int depth, int dim, int kernel, int B, int T,
                                    const float* const* feats, const int* n_i, const esmi_predictor_weights* pitch,
                                    const esmi_predictor_weights* energy, const esmi_predictor_weights* duration,
@@ -479,111 +587,9 @@ int esmi_fuse_variance_adaptor_f32(const esmi_fuse_weights* fw, int depth, int d
                                    float* duration_pred, int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur,
                                    int32_t* cum, int32_t* mel_len, const esmi_decoder_head* head, float* h0, int plan,
                                    void* workspace, size_t workspace_bytes, esmi_stream_t stream) {
-    return fuse_variance_adaptor(fw, depth, dim, kernel, B, T, feats, n_i, pitch, energy, duration, mask, pitch_target, energy_target,
-                                 duration_target, feat, pitch_pred, energy_pred, duration_pred, pitch_idx, energy_idx, dur, cum, mel_len,
-                                 head, h0, plan, workspace, workspace_bytes, stream, false);
-}
-static int fuse_variance_adaptor(const esmi_fuse_weights* fw, int depth, int dim, int kernel, int B, int T,
-                                 const float* const* feats, const int* n_i, const esmi_predictor_weights* pitch,
-                                 const esmi_predictor_weights* energy, const esmi_predictor_weights* duration,
-                                 const uint8_t* mask, const float* pitch_target, const float* energy_target,
-                                 const int32_t* duration_target, float* feat, float* pitch_pred, float* energy_pred,
-                                 float* duration_pred, int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur,
-                                 int32_t* cum, int32_t* mel_len, const esmi_decoder_head* head, float* h0, int plan,
-                                 void* workspace, size_t workspace_bytes, esmi_stream_t stream, bool lean) {
-    if ((cum == nullptr) != (mel_len == nullptr)) return ESMI_ERR_ARG;
-    if (h0 && (!head || (!head->proj_wp && !head->proj_w) || !head->proj_b || !head->ln_g || !head->ln_b)) return ESMI_ERR_ARG;
-    if (!fw || !feats || !n_i || !pitch || !energy || !duration || !feat || !pitch_pred || !energy_pred ||
-        !duration_pred || !dur || depth < 1 || depth > ESMI_MAX_DEPTH)
-        return ESMI_ERR_ARG;
-    const bool chain = fuse_va_chain_ok(fw, depth, dim, kernel, n_i[0], T, pitch, energy, duration, plan);
-    const bool head_in_chain = h0 && fuse_va_head_ok(chain, dim, head);
-    if (h0 && !head_in_chain && !(head_gemm_ok(head) && head->d4 == 4 * dim)) return ESMI_ERR_UNSUPPORTED;
-    for (int i = 1; i < depth && chain; ++i)
-        if ((n_i[i] - 1) * (1 << i) + kernel < T) return ESMI_ERR_UNSUPPORTED;   // torch.cat would raise in the reference
-    if (chain) {
-        FuseVaP p;
-        int nw;
-        if (!pitch->bins || !pitch->emb || !energy->bins || !energy->emb) return ESMI_ERR_ARG;
-        fuse_va_chain_params(fw, depth, dim, kernel, B, T, feats, n_i, pitch, energy, duration, mask, pitch_target, energy_target,
-                             duration_target, feat, pitch_pred, energy_pred, duration_pred, pitch_idx, energy_idx, dur, cum, mel_len,
-                             head_in_chain ? head : nullptr, head_in_chain ? h0 : nullptr, &p, &nw);
-        bool scan_fused = cum && p.halo == 0;   // one workgroup sees every duration of its utterance
-        int rc16 = ESMI_ERR_UNSUPPORTED;
-        if ((plan & ESMI_FUSE_CHAIN16) && scan_fused == (cum != nullptr)) {
-            FuseVaP q = p;
-            if (lean && head_in_chain) { q.feat = nullptr; q.preds[0] = q.preds[1] = nullptr; q.pitch_idx = q.energy_idx = nullptr; }
-            rc16 = launch_enc_va16(q, dim, kernel, S(stream));
-        }
-        bool head_done = head_in_chain;
-        if (rc16 == ESMI_ERR_UNSUPPORTED && (plan & ESMI_FUSE_CHAIN16) && !head_in_chain) {
-            // dim = 64, T <= 256 (round 6): one workgroup per utterance, so the length regulator's scan runs inside it -- and the decoder's
-            // phoneme-rate first stage too when the caller wants h0 (4 dim = dx2 = 256, pre-split weights); a lean caller then gets
-            // neither the feature rows nor the pitch / energy outputs written
-            FuseVaP q = p;
-            q.cum = cum; q.mel_len = mel_len;
-            const bool head64 = h0 && head->proj_wp && head->d4 == 4 * dim && head->dx2 == 4 * dim;
-            if (head64) {
-                q.head_w = head->proj_wp; q.head_b = head->proj_b; q.head_g = head->ln_g; q.head_beta = head->ln_b; q.h0 = h0;
-                if (lean) { q.feat = nullptr; q.preds[0] = q.preds[1] = nullptr; q.pitch_idx = q.energy_idx = nullptr; }
-            }
-            rc16 = launch_enc_va64(q, dim, kernel, S(stream));
-            if (rc16 == ESMI_OK) { scan_fused = cum != nullptr; head_done = head64; }
-        }
-        if (rc16 == ESMI_ERR_UNSUPPORTED) rc16 = launch_enc_fuse_va(p, dim, kernel, nw, head_in_chain, S(stream));
-        if (rc16) return rc16;
-        if (cum && !scan_fused) ESMI_LAUNCH(length_regulate_kernel, dim3(B), dim3(64), 0, S(stream), dur, T, cum, mel_len, (int*)nullptr);
-        if (h0 && !head_done) return esmi_decoder_head_f32(head, (long)B * T, feat, h0, stream);
-        return launch_status();
-    }
-    if (!workspace || workspace_bytes < esmi_fuse_variance_adaptor_workspace_bytes(B, T, dim, depth)) return ESMI_ERR_WORKSPACE;
-    const size_t fws = esmi_fuse_workspace_bytes(B, T, dim, depth);
-    // dim = 128, two levels, T <= 256 (round 6): the Fuse stage as ONE launch (enc_fuse128.h) instead of four GEMM launches through HBM
-    int rc = ESMI_ERR_UNSUPPORTED;
-    if ((plan & ESMI_FUSE_CHAIN16) && dim == 128 && depth == 2 && fw->mlp_wp[0] && fw->mlp_wp[1] && fw->up_wp[1] && fw->fuse_wp) {
-        FuseVaP q;
-        memset(&q, 0, sizeof q);
-        q.B = B; q.T = T; q.depth = depth; q.kernel = kernel;
-        for (int i = 0; i < depth; ++i) {
-            q.feats[i] = feats[i]; q.n_i[i] = n_i[i];
-            q.mlp_w[i] = fw->mlp_wp[i]; q.mlp_b[i] = fw->mlp_b[i]; q.up_w[i] = fw->up_wp[i]; q.up_b[i] = fw->up_b[i];
-        }
-        q.fuse_w = fw->fuse_wp; q.fuse_b = fw->fuse_b; q.mask = mask; q.feat = feat;
-        rc = launch_enc_fuse128(q, dim, kernel, S(stream));
-    }
-    if (rc == ESMI_ERR_UNSUPPORTED) rc = esmi_fuse_f32(fw, depth, dim, kernel, B, T, feats, n_i, mask, feat, 4 * dim, workspace, fws, stream);
-    if (rc) return rc;
-    // dim = 128, T <= 256 (round 6): the three predictors as ONE launch -- a workgroup per (utterance, predictor) with the hidden rows in
-    // registers, bucketize / embeddings / duration features / rounding and the length regulator's scan inside (enc_pred128.h) -- instead
-    // of six GEMM launches through HBM + va_tail_kernel + length_regulate_kernel
-    rc = ESMI_ERR_UNSUPPORTED;
-    if ((plan & ESMI_FUSE_CHAIN16) && dim == 128 && pitch->conv1_wp && pitch->conv2_wp && energy->conv1_wp && energy->conv2_wp &&
-        duration->conv1_wp && duration->conv2_wp) {
-        Pred128P q;
-        memset(&q, 0, sizeof q);
-        const esmi_predictor_weights* pw[3] = {pitch, energy, duration};
-        for (int k = 0; k < 3; ++k) {
-            PredW& d = q.pred[k];
-            d.conv1_w = pw[k]->conv1_wp; d.conv1_b = pw[k]->conv1_b; d.ln1_g = pw[k]->ln1_g; d.ln1_b = pw[k]->ln1_b;
-            d.conv2_w = pw[k]->conv2_wp; d.conv2_b = pw[k]->conv2_b; d.ln2_g = pw[k]->ln2_g; d.ln2_b = pw[k]->ln2_b;
-            d.lin_w = pw[k]->lin_w; d.lin_b = pw[k]->lin_b; d.bins = pw[k]->bins; d.emb = pw[k]->emb;
-        }
-        q.mask = mask; q.pitch_t = pitch_target; q.energy_t = energy_target; q.dur_t = duration_target;
-        q.feat = feat; q.preds[0] = pitch_pred; q.preds[1] = energy_pred; q.preds[2] = duration_pred;
-        q.pitch_idx = pitch_idx; q.energy_idx = energy_idx; q.dur = dur; q.cum = cum; q.mel_len = mel_len; q.B = B; q.T = T;
-        rc = launch_enc_pred128(q, dim, S(stream));
-    }
-    if (rc == ESMI_ERR_UNSUPPORTED) {
-        rc = esmi_variance_adaptor_f32(pitch, energy, duration, dim, B, T, mask, pitch_target, energy_target,
-                                       duration_target, feat, pitch_pred, energy_pred, duration_pred, pitch_idx, energy_idx,
-                                       dur, static_cast<char*>(workspace) + fws, workspace_bytes - fws, stream);
-        if (rc) return rc;
-        if (cum) ESMI_LAUNCH(length_regulate_kernel, dim3(B), dim3(64), 0, S(stream), dur, T, cum, mel_len, (int*)nullptr);
-    } else if (rc) {
-        return rc;
-    }
-    if (h0) return esmi_decoder_head_f32(head, (long)B * T, feat, h0, stream);
-    return launch_status();
+    return fuse_variance_adaptor(VaArgs{fw, depth, dim, kernel, B, T, feats, n_i, {pitch, energy, duration}, mask, pitch_target, energy_target,
+                                        duration_target, feat, {pitch_pred, energy_pred, duration_pred}, pitch_idx, energy_idx, dur, cum, mel_len,
+                                        head, h0, plan, workspace, workspace_bytes, stream, false});
 }
 
 // MelDecoder's first stage at phoneme rate as one launch: GEMM (k = 1) + bias + tanh + LayerNorm in the epilogue (networks.py:291-293)
@@ -965,6 +971,45 @@ int esmi_phoneme2mel_forward_f32(const esmi_forward_args* a, int stage, esmi_str
     return ESMI_ERR_UNSUPPORTED;   // this library was built without the range check (libesmi_checked.so has it)
 #endif
 }
+namespace {
+// The encoder blocks' shapes of a one-call forward, the padding mask pooled to each block's length included: networks.py:69-70,
+// pool = round(T / n), half to even; ESMI_ERR_UNSUPPORTED when that pool does not give back n.
+int block_shapes(const esmi_forward_args* a, const FwdArena& o, int plan, esmi_encoder_block_shape* sh) {
+    int n_in = a->T;
+    for (int i = 0; i < a->depth; ++i) {
+        sh[i] = a->shapes[i];
+        sh[i].B = a->B; sh[i].n_in = n_in; sh[i].plan = plan; sh[i].mask_pool = 1; sh[i].mask_len = a->T;
+        if (a->mask) {
+            sh[i].mask_pool = (int)nearbyint((double)a->T / o.n[i]);
+            if ((a->T + sh[i].mask_pool - 1) / sh[i].mask_pool != o.n[i]) return ESMI_ERR_UNSUPPORTED;
+        }
+        n_in = o.n[i];
+    }
+    return ESMI_OK;
+}
+
+// The whole encoder side as ONE launch (enc_all16_kernel: block 0 | block 1 | Fuse + variance adaptor + scan + head behind each other in
+// one workgroup per utterance) when each of the three chain16 bodies serves its stage; ESMI_ERR_UNSUPPORTED otherwise.
+int encoder_side_one_launch(const esmi_forward_args* a, const esmi_encoder_block_shape* sh, const VaArgs& va, Head head, float* x0, float* x1) {
+    // (the chain16 bodies are built for MixFFN expansion 1 only, like launch_enc_block16)
+    if (va.plan != ESMI_FUSE_ALL || a->depth != 2 || a->T > 128 || sh[0].expansion != 1 || sh[1].expansion != 1) return ESMI_ERR_UNSUPPORTED;
+    const esmi_encoder_block_weights *w0 = &a->blocks[0], *w1 = &a->blocks[1];
+    const bool want_head = a->head.proj_wp || a->head.proj_w;
+    if (!block_packed(w0) || !w0->qk_wp || !w0->vo_wp || !block_packed(w1) || !w1->qk_wp || !w1->vo_wp || !va_chain_ok(va) ||
+        (want_head && head != Head::in_chain) || !va.pw[0]->bins || !va.pw[0]->emb || !va.pw[1]->bins || !va.pw[1]->emb ||
+        (va.n_i[1] - 1) * 2 + va.kernel < va.T)
+        return ESMI_ERR_UNSUPPORTED;
+    EncAttnFfnP b0 = block_params(w0, &sh[0], a->ids, a->embed, nullptr, va.mask, nullptr, nullptr, x0);
+    EncAttnFfnP b1 = block_params(w1, &sh[1], nullptr, nullptr, x0, va.mask, nullptr, nullptr, x1);
+    fold_attention(w0, &b0); fold_attention(w1, &b1);
+    b0.wgs_per_b = b1.wgs_per_b = 1;
+    int nw;
+    FuseVaP p = va_chain_params(va, head == Head::in_chain, &nw);
+    if (va.lean && head == Head::in_chain) drop_unread_outputs(&p);
+    return p.cum ? launch_enc_all16(b0, b1, sh[1].c_in, p, va.dim, va.kernel, S(va.stream)) : ESMI_ERR_UNSUPPORTED;
+}
+}  // namespace
+
 static int forward_impl(const esmi_forward_args* a, int stage, esmi_stream_t stream) {
     FwdArena o;
     int rc = fwd_arena(a, &o);
@@ -979,93 +1024,36 @@ static int forward_impl(const esmi_forward_args* a, int stage, esmi_stream_t str
     int32_t* cum = a->cum ? a->cum : I(o.cum);
     float* h0 = (a->head.proj_wp || a->head.proj_w) ? F(o.h0) : nullptr;
     const uint8_t* mask = a->mask;
-    bool enc_done = false;
-    if (stage != 2 && (plan & ESMI_FUSE_ALL) == ESMI_FUSE_ALL && a->depth == 2 && T <= 128) {
-        // ---- the whole encoder side as ONE launch (round 5: enc_all16_kernel = block 0 | block 1 | Fuse + variance adaptor + head behind
-        // each other in one workgroup per utterance) when all three chain16 kernels serve their shapes
-        esmi_encoder_block_shape sh[2];
-        // (the chain16 bodies are built for MixFFN expansion 1 only, like launch_enc_block16: anything else takes the per-block path below)
-        bool ok = a->shapes[0].expansion == 1 && a->shapes[1].expansion == 1;
-        int n_in = T;
-        for (int i = 0; i < 2 && ok; ++i) {
-            sh[i] = a->shapes[i];
-            sh[i].B = B; sh[i].n_in = n_in; sh[i].plan = plan; sh[i].mask_pool = 1; sh[i].mask_len = T;
-            if (mask) {
-                sh[i].mask_pool = (int)nearbyint((double)T / o.n[i]);
-                ok = (T + sh[i].mask_pool - 1) / sh[i].mask_pool == o.n[i];
-            }
-            n_in = o.n[i];
+    const float* feats[ESMI_MAX_DEPTH];
+    for (int i = 0; i < a->depth; ++i) feats[i] = F(o.feats[i]);
+    VaArgs va{&a->fuse, a->depth, a->dim, a->fuse_kernel, B, T, feats, o.n, {&a->pitch, &a->energy, &a->duration}, mask, nullptr, nullptr,
+              a->dur_forced, feat,
+              {a->pitch_pred ? a->pitch_pred : F(o.preds[0]), a->energy_pred ? a->energy_pred : F(o.preds[1]), a->duration_pred},
+              a->pitch_idx ? a->pitch_idx : I(o.idx[0]), a->energy_idx ? a->energy_idx : I(o.idx[1]), a->dur ? a->dur : I(o.dur), cum,
+              a->mel_len, nullptr, nullptr, plan, base + o.ws, esmi_fuse_variance_adaptor_workspace_bytes(B, T, a->dim, a->depth), stream,
+              !a->pitch_pred && !a->energy_pred && !a->pitch_idx && !a->energy_idx};
+    // the decoder's first stage at phoneme rate: stage 1 produces h0, stage 2 reads it (a stage-2 call re-derives the same static test)
+    const Head head = phoneme_rate_head(va, &a->head);
+    const bool head_ok = head == Head::in_chain || (head == Head::gemm && a->head.dx2 == a->dec_shape.dx2);
+    if (head_ok) { va.head = &a->head; va.h0 = h0; }
+    if (stage != 2) {
+        esmi_encoder_block_shape sh[ESMI_MAX_DEPTH];
+        if ((rc = block_shapes(a, o, plan, sh))) return rc;
+        rc = encoder_side_one_launch(a, sh, va, head, F(o.feats[0]), F(o.feats[1]));
+        if (rc == ESMI_ERR_UNSUPPORTED) {   // block by block, then the Fuse + variance-adaptor stage
+            rc = ESMI_OK;
+            for (int i = 0; i < a->depth && !rc; ++i)
+                rc = esmi_encoder_block_f32(&a->blocks[i], &sh[i], i == 0 ? a->ids : nullptr, i == 0 ? a->embed : nullptr,
+                                            i == 0 ? nullptr : feats[i - 1], mask, F(o.feats[i]), base + o.ws,
+                                            esmi_encoder_block_workspace_bytes(&sh[i]), stream);
+            if (!rc) rc = fuse_variance_adaptor(va);
         }
-        EncAttnFfnP b0, b1;
-        ok = ok && block_chain_params(&a->blocks[0], &sh[0], a->ids, a->embed, nullptr, mask, F(o.feats[0]), &b0) &&
-             block_chain_params(&a->blocks[1], &sh[1], nullptr, nullptr, F(o.feats[0]), mask, F(o.feats[1]), &b1);
-        const bool chain = fuse_va_chain_ok(&a->fuse, a->depth, a->dim, a->fuse_kernel, o.n[0], T, &a->pitch, &a->energy, &a->duration, plan);
-        const bool want_head = a->head.proj_wp || a->head.proj_w;
-        const bool head_in_chain = want_head && fuse_va_head_ok(chain, a->dim, &a->head);
-        ok = ok && chain && (!want_head || head_in_chain) && a->pitch.bins && a->pitch.emb && a->energy.bins && a->energy.emb &&
-             (o.n[1] - 1) * 2 + a->fuse_kernel >= T;
-        if (ok) {
-            const float* feats[2] = {F(o.feats[0]), F(o.feats[1])};
-            const bool lean = !a->pitch_pred && !a->energy_pred && !a->pitch_idx && !a->energy_idx && head_in_chain;
-            FuseVaP va;
-            int nw_unused;
-            fuse_va_chain_params(&a->fuse, 2, a->dim, a->fuse_kernel, B, T, feats, o.n, &a->pitch, &a->energy, &a->duration, mask, nullptr, nullptr,
-                                 a->dur_forced, lean ? nullptr : feat, lean ? nullptr : (a->pitch_pred ? a->pitch_pred : F(o.preds[0])),
-                                 lean ? nullptr : (a->energy_pred ? a->energy_pred : F(o.preds[1])), a->duration_pred,
-                                 lean ? nullptr : (a->pitch_idx ? a->pitch_idx : I(o.idx[0])), lean ? nullptr : (a->energy_idx ? a->energy_idx : I(o.idx[1])),
-                                 a->dur ? a->dur : I(o.dur), cum, a->mel_len, head_in_chain ? &a->head : nullptr, head_in_chain ? h0 : nullptr, &va,
-                                 &nw_unused);
-            rc = va.cum ? launch_enc_all16(b0, b1, sh[1].c_in, va, a->dim, a->fuse_kernel, S(stream)) : ESMI_ERR_UNSUPPORTED;
-            if (rc == ESMI_OK) enc_done = true;
-            else if (rc != ESMI_ERR_UNSUPPORTED) return rc;
-        }
-        if (enc_done && a->lmax_dev && (rc = esmi_max_i32(a->mel_len, B, a->lmax_dev, stream))) return rc;
-    }
-    if (stage != 2 && !enc_done) {
-        const float* x_in = nullptr;
-        int n_in = T;
-        for (int i = 0; i < a->depth; ++i) {
-            esmi_encoder_block_shape sh = a->shapes[i];
-            sh.B = B; sh.n_in = n_in; sh.plan = plan;
-            sh.mask_pool = 1; sh.mask_len = T;
-            if (mask) {   // networks.py:69-70: pool = round(T / n), half to even
-                const double r = (double)T / o.n[i];
-                sh.mask_pool = (int)nearbyint(r);
-                if ((T + sh.mask_pool - 1) / sh.mask_pool != o.n[i]) return ESMI_ERR_UNSUPPORTED;
-            }
-            rc = esmi_encoder_block_f32(&a->blocks[i], &sh, i == 0 ? a->ids : nullptr, i == 0 ? a->embed : nullptr, x_in, mask,
-                                        F(o.feats[i]), base + o.ws, esmi_encoder_block_workspace_bytes(&sh), stream);
-            if (rc) return rc;
-            x_in = F(o.feats[i]);
-            n_in = o.n[i];
-        }
-        const float* feats[ESMI_MAX_DEPTH];
-        for (int i = 0; i < a->depth; ++i) feats[i] = F(o.feats[i]);
-        float* pp = a->pitch_pred ? a->pitch_pred : F(o.preds[0]);
-        float* ep = a->energy_pred ? a->energy_pred : F(o.preds[1]);
-        int32_t* pi = a->pitch_idx ? a->pitch_idx : I(o.idx[0]);
-        int32_t* ei = a->energy_idx ? a->energy_idx : I(o.idx[1]);
-        int32_t* dur = a->dur ? a->dur : I(o.dur);
-        const size_t wsb = esmi_fuse_variance_adaptor_workspace_bytes(B, T, a->dim, a->depth);
-        const bool head_ok = fuse_va_head_ok(fuse_va_chain_ok(&a->fuse, a->depth, a->dim, a->fuse_kernel, o.n[0], T, &a->pitch, &a->energy,
-                                                              &a->duration, plan), a->dim, &a->head) ||
-                             (head_gemm_ok(&a->head) && a->head.d4 == 4 * a->dim && a->head.dx2 == a->dec_shape.dx2);
-        // (lean: nobody reads the arena's feature / prediction / index buffers when the caller did not ask for them and h0 is produced)
-        const bool lean = !a->pitch_pred && !a->energy_pred && !a->pitch_idx && !a->energy_idx;
-        rc = fuse_variance_adaptor(&a->fuse, a->depth, a->dim, a->fuse_kernel, B, T, feats, o.n, &a->pitch, &a->energy,
-                                   &a->duration, mask, nullptr, nullptr, a->dur_forced, feat, pp, ep, a->duration_pred,
-                                   pi, ei, dur, cum, a->mel_len, head_ok ? &a->head : nullptr, head_ok ? h0 : nullptr, plan,
-                                   base + o.ws, wsb, stream, lean);
         if (rc) return rc;
         if (a->lmax_dev && (rc = esmi_max_i32(a->mel_len, B, a->lmax_dev, stream))) return rc;
     }
     if (stage != 1) {
         if (a->L_out <= 0) return ESMI_OK;   // every duration zero: empty mel, nothing to launch
         if (!a->mel || !a->dec_blob) return ESMI_ERR_ARG;
-        // (a stage-2 call re-derives whether stage 1 produced the phoneme-rate head: the same static test)
-        const bool head_ok = fuse_va_head_ok(fuse_va_chain_ok(&a->fuse, a->depth, a->dim, a->fuse_kernel, o.n[0], T, &a->pitch, &a->energy,
-                                                              &a->duration, plan), a->dim, &a->head) ||
-                             (head_gemm_ok(&a->head) && a->head.d4 == 4 * a->dim && a->head.dx2 == a->dec_shape.dx2);
         // the decoder's carried rows: the encoder side's scratch (free again), or the arena's tail region when that is too small
         const size_t dec_need = esmi_mel_decoder_workspace_bytes(&a->dec_shape, B, a->L_out);
         const bool use_tail = dec_need > o.feat - o.ws && a->arena_bytes >= o.total + dec_need;

@@ -51,45 +51,38 @@ ConvGemmP conv_defaults();
 int launch_convgemm(ConvGemmP p, hipStream_t st);
 // tu_attention.hip
 int launch_attn(const AttnP& p, hipStream_t st);
-// tu_enc_merge.hip / tu_enc_block.hip / tu_enc_attn_ffn.hip / tu_enc_fuse_va.hip (the encoder-side chain kernels)
+// tu_enc_merge.hip / tu_enc_block.hip / tu_enc_attn_ffn.hip / tu_enc_fuse_va.hip (rounds 1-4: the 32-row wave-chain kernels).  Every
+// launcher answers ESMI_ERR_UNSUPPORTED for a shape it is not built for; which plan bits apply is decided by its caller (esmi_abi.hip).
 int launch_enc_merge_qkv(const EncMergeP& p, int c_in, int c_out, hipStream_t st);
-int launch_enc_block(const EncAttnFfnP& p, int expansion, int c_in, int plan, hipStream_t st);
-int launch_enc_attn_ffn(const EncAttnFfnP& p, int expansion, int plan, hipStream_t st);
+int launch_enc_block(const EncAttnFfnP& p, int expansion, int c_in, bool split2, hipStream_t st);   // split2: two waves per row tile
+int launch_enc_attn_ffn(const EncAttnFfnP& p, int expansion, bool split2, hipStream_t st);
 int launch_enc_fuse_va(const FuseVaP& p, int dim, int kernel, int nw, bool head, hipStream_t st);
-// tu_enc_va16.hip (round 5: 16-row tiles, weights through LDS; ESMI_ERR_UNSUPPORTED for the shapes it is not built for)
+// tu_enc_block16.hip / tu_enc_va16.hip (round 5: dim = 32 models on 16-row tiles, weights through LDS)
+int launch_enc_block16(const EncAttnFfnP& p, int expansion, int c_in, hipStream_t st);
 int launch_enc_va16(const FuseVaP& p, int dim, int kernel, hipStream_t st);
 bool enc_va16_ok(const FuseVaP& p, int dim, int kernel);
-// tu_enc_va64.hip (round 6: the same stage for dim = 64 models, T <= 256; ESMI_ERR_UNSUPPORTED otherwise)
-int launch_enc_va64(const FuseVaP& p, int dim, int kernel, hipStream_t st);
-struct PostAttn64P;
-int launch_enc_post_attn64(const PostAttn64P& p, hipStream_t st);   // (enc_ffn64.h: proj + LN1 + MixFFN + LN2 of a C = 64 one-head block, N <= 256)
-// tu_enc_pred128.hip (round 6: the three predictors + variance-adaptor tail + scan of a dim = 128 model, T <= 256; reads feat[:, 0 .. dim))
-int launch_enc_pred128(const Pred128P& p, int dim, hipStream_t st);
-int launch_enc_fuse128(const FuseVaP& p, int dim, int kernel, hipStream_t st);
-int launch_enc_post_attn128(const PostAttn128P& p, hipStream_t st);
-int launch_enc_merge_q256(const MergeQ256P& p, hipStream_t st);   // (enc_merge256.h: merge conv k = 5 stride 2, 128 -> 256, + the folded query GEMM, N <= 128)   // (enc_ffn128.h: proj + LN1 + MixFFN + LN2 of a C = 128 two-head expansion-2 block, N <= 256)
-   // (enc_fuse128.h: the Fuse stage of the same models, one launch)
-// tu_enc_block16.hip (round 5: whole-block kernels of dim = 32 models on 16-row tiles)
-int launch_enc_block16(const EncAttnFfnP& p, int expansion, int c_in, hipStream_t st);
 // ... and the whole encoder side in one launch (block 0 | block 1 | Fuse + variance adaptor), when each of the three chain16 kernels
-// serves its shape and they run the same number of waves; ESMI_ERR_UNSUPPORTED otherwise
+// serves its shape and they run the same number of waves
 int launch_enc_all16(const EncAttnFfnP& b0, const EncAttnFfnP& b1, int c_in1, const FuseVaP& va, int dim, int kernel, hipStream_t st);
+// tu_enc_va64.hip / tu_enc_pred128.hip (round 6: activations in registers, weights streamed through LDS; one workgroup per utterance)
+int launch_enc_va64(const FuseVaP& p, int dim, int kernel, hipStream_t st);   // enc_va64.h: Fuse + variance adaptor of a dim = 64 model, T <= 256
+struct PostAttn64P;
+int launch_enc_post_attn64(const PostAttn64P& p, hipStream_t st);   // enc_ffn64.h: proj + LN1 + MixFFN + LN2 of a C = 64 one-head block, N <= 256
+int launch_enc_pred128(const Pred128P& p, int dim, hipStream_t st);   // enc_pred128.h: three predictors + tail + scan, dim = 128, T <= 256
+int launch_enc_fuse128(const FuseVaP& p, int dim, int kernel, hipStream_t st);   // enc_fuse128.h: the Fuse stage of the same models
+int launch_enc_post_attn128(const PostAttn128P& p, hipStream_t st);   // enc_ffn128.h: proj + LN1 + MixFFN + LN2, C = 128, two heads, expansion 2, N <= 256
+int launch_enc_merge_q256(const MergeQ256P& p, hipStream_t st);   // enc_merge256.h: merge conv k = 3 stride 2, 128 -> 256, + the folded query GEMM, N <= 128
 // tu_hifigan.hip
 int launch_resblock(const ResblockP& p, int c, hipStream_t st);
 
+// Does enc_attn_ffn serve this block (the shapes it is instantiated for)?  Not beyond 128 positions: there the chain kernel runs one
+// latency chain per 32 rows against up to 256 keys, and the same ops as launches (LDS-staged attention + GEMMs) are faster (launches
+// vs chain: small ES at T = 256 2.53 vs 2.62 ms/step, base ES block 0 at N = 256, B = 512 1.33 vs 2.00 ms; tools/debug_plan_base.py).
 inline bool enc_attn_ffn_supported(int C, int N, int expansion) {
-    if ((C & 31) || N > 256 || N < 1) return false;
-    // sequences of more than 128 positions: the chain kernel runs one latency chain per 32 rows against up to 256 keys; the same
-    // ops as launches (LDS-staged attention + LDS-staged GEMMs) are faster there (small ES T = 256: 2.53 vs 2.62 ms/step; base ES
-    // block 0: 1.33 vs 2.00 ms) -- `tools/debug_plan_base.py` measures the plans
-    if (N > 128) return false;
+    if ((C & 31) || N > 128 || N < 1) return false;
     const int nc = C / 32;
-    // base ES block 0 (C = 128, expansion 2) at N = 256: the chain kernel runs one latency chain per 32 rows against 256 keys
-    // (2.00 ms at B = 512); the same ops as LDS-staged GEMM launches take 1.33 ms, so that shape goes per-op
-    return (expansion == 1 && (nc == 1 || nc == 2 || nc == 4)) || (expansion == 2 && nc == 4 && N <= 128);
+    return (expansion == 1 && (nc == 1 || nc == 2 || nc == 4)) || (expansion == 2 && nc == 4);
 }
-
-
 
 // ---- activation-range check (esmi_dev.h, the ESMI_RANGE_CHECK build): every translation unit owns a copy of the device-side flag
 // pointer and defines its setter with ESMI_TU_RANGE_SETTER(<unit>); `set_range_flag_all` (esmi_abi.hip) calls them all.

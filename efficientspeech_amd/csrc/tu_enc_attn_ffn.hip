@@ -10,7 +10,7 @@ ESMI_TU_CHAIN_TRACE_SETTER(enc_attn_ffn)
 namespace esmi {
 
 // E2: attention + proj + LN1 + MixFFN + LN2 in one launch.
-int launch_enc_attn_ffn(const EncAttnFfnP& p, int expansion, int plan, hipStream_t st) {
+int launch_enc_attn_ffn(const EncAttnFfnP& p, int expansion, bool split2, hipStream_t st) {
     // N <= 128 only: the 8-key-tile instantiations (N <= 256) spilled 84 .. 820 B per lane at 512 + 256 registers and were slower than the
     // per-op launches (`enc_attn_ffn_supported`, launch.h, never selected them); round 6 stops building them -- a longer sequence gets
     // ESMI_ERR_UNSUPPORTED here and the LDS-staged attention + GEMM launches from the caller
@@ -18,7 +18,7 @@ int launch_enc_attn_ffn(const EncAttnFfnP& p, int expansion, int plan, hipStream
     const int nc = p.C / 32, nkt = p.N <= 64 ? 2 : 4;
     int nw, wgs, useful, halo;
     EncAttnFfnP q = p;
-    if (p.h == 2 && nc == 2 && expansion == 1 && (plan & ESMI_FUSE_SPLIT2)) {   // two waves per row tile when rows are scarce
+    if (p.h == 2 && nc == 2 && expansion == 1 && split2) {   // two waves per row tile when rows are scarce
         enc_attn_ffn_split_plan(p.N, &nw, &wgs, &useful, &halo);
         if ((long)p.B * wgs * 2 * nw <= 1024 && nkt <= 4) {
             q.wgs_per_b = wgs; q.useful = useful; q.halo = halo;

@@ -11,10 +11,10 @@ namespace esmi {
 
 // Whole encoder block (merge conv + qkv + attention + MixFFN) in one launch: sequences one workgroup covers, shapes
 // whose q/k/v tile fits in LDS.  Returns ESMI_ERR_UNSUPPORTED otherwise (-> enc_merge_qkv + enc_attn_ffn launches).
-int launch_enc_block(const EncAttnFfnP& p, int expansion, int c_in, int plan, hipStream_t st) {
+int launch_enc_block(const EncAttnFfnP& p, int expansion, int c_in, bool split2, hipStream_t st) {
     if ((p.C & 31) || (c_in & 31) || p.N > 128) return ESMI_ERR_UNSUPPORTED;
     const int nc = p.C / 32, nci = c_in / 32, nkt = p.N <= 64 ? 2 : 4;
-    if (p.h == 2 && nc == 2 && expansion == 1 && (plan & ESMI_FUSE_SPLIT2)) {   // two waves per row tile when rows are scarce
+    if (p.h == 2 && nc == 2 && expansion == 1 && split2) {   // two waves per row tile when rows are scarce
         int nw, wgs, useful, halo;
         enc_attn_ffn_split_plan(p.N, &nw, &wgs, &useful, &halo);
         if ((long)p.B * wgs * 2 * nw <= 1024) {

@@ -9,7 +9,7 @@
 #include "wavesim.h"
 #define ESMI_DYN_LDS(name) float* name = (float*)wavesim::dyn_lds()
 #define ESMI_LAUNCH(kern, grid, block, lds, stream, ...) \
-    wavesim::launch(grid, block, lds, [&]() { kern(__VA_ARGS__); })
+    wavesim::launch(#kern, grid, block, lds, [&]() { kern(__VA_ARGS__); })
 #else
 #include <hip/hip_runtime.h>
 #define ESMI_DYN_LDS(name) extern __shared__ __attribute__((aligned(16))) float name[]

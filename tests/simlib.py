@@ -27,6 +27,7 @@ def sim_lib():
         from efficientspeech_amd import _lib
         _handle = _lib.bind(ctypes.CDLL(SIM_SO))
         assert _handle.esmi_backend() == b"wavesim"
+        _handle.wavesim_launch_log.restype = ctypes.c_char_p
     return _handle
 
 
@@ -46,3 +47,19 @@ def use_sim():
         yield _lib._LIB
     finally:
         _lib._LIB, networks._runtime = old_lib, old_rt
+
+
+@contextlib.contextmanager
+def launched_kernels():
+    """The kernels the simulator launches inside the block, in order: the list is filled when the block exits.  Names are the
+    launch sites' spelling without the outer parentheses and blanks, e.g. `enc_va64_kernel<2>`."""
+    lib = sim_lib()
+    lib.wavesim_launch_log_clear()
+    names = []
+    try:
+        yield names
+    finally:
+        for rec in lib.wavesim_launch_log().decode().splitlines():
+            name = rec.rsplit(" ", 7)[0].replace(" ", "")      # (grid, block and LDS bytes follow the name)
+            names.append(name[1:-1] if name.startswith("(") else name)
+        lib.wavesim_launch_log_clear()

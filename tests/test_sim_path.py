@@ -15,7 +15,7 @@ from efficientspeech_amd import _lib
 from efficientspeech_amd.synth import synth_phonemes
 from oracle import oracle
 from tests import helpers as H
-from tests.simlib import use_sim
+from tests.simlib import launched_kernels, use_sim
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 # all tiny fixtures + a padded / teacher-forced one for the wider models (keeps the CPU suite short)
@@ -63,12 +63,14 @@ def test_simulated_unfused_path_matches_golden(path, nets):
     ("base", 2, 150, [150, 97], 77),           # round 6: enc_pred128_kernel, five waves x two tiles, the last tile partly / wholly outside
 ])
 def test_simulated_eval_vs_oracle_multi_tile(name, B, T, lens, seed, nets):
+    kernels = {("small", 150): {"enc_va64_kernel<2>", "enc_post_attn64_kernel<2>"}, ("base", 150): {"enc_pred128_kernel"}}.get((name, T), set())
     net, cfg, sd = nets(name)
     ids, mask = synth_phonemes(B, T, seed, lens)
     x = {"phoneme": torch.from_numpy(ids), "phoneme_mask": torch.from_numpy(mask)}
-    with use_sim(), torch.no_grad():
+    with use_sim(), torch.no_grad(), launched_kernels() as launched:
         enc = net.encoder._encode(x)
         mel, mel_len, _ = net(x)
+    assert kernels <= set(launched)
     o = oracle.phoneme2mel(cfg, oracle.Weights(sd), ids, mask)
     err = H.compare_eval_with_oracle(cfg, o, enc, mel, mel_len, sd)
     assert err == err
@@ -163,8 +165,10 @@ def test_simulated_one_launch_encoder_side(B, T, lens, nets):
     if B > 1:
         x["phoneme_mask"] = torch.from_numpy(mask)
     with use_sim(), torch.no_grad():
-        mel, mel_len, dur = net(x)                                    # one-call forward: enc_all16_kernel
-        enc = net.encoder._encode(x)                                  # module path: three chain16 launches
+        with launched_kernels() as one_call:
+            mel, mel_len, dur = net(x)                                # one-call forward: enc_all16_kernel
+        with launched_kernels() as module:
+            enc = net.encoder._encode(x)                              # module path: three chain16 launches
         with _lib.launch_plan(31):
             mel31, _, dur31 = net(x)
     o = oracle.phoneme2mel(cfg, oracle.Weights(sd), ids, mask if B > 1 else None)
@@ -172,6 +176,8 @@ def test_simulated_one_launch_encoder_side(B, T, lens, nets):
     assert err == err
     np.testing.assert_allclose(dur.numpy(), o.duration, atol=H.PRED_TOL, rtol=0)
     assert float((mel - mel31).abs().max()) < 2e-5 and float((dur - dur31).abs().max()) < 2e-5
+    assert [k.split("<")[0] for k in one_call if k.startswith("enc_")] == ["enc_all16_kernel"]
+    assert [k.split("<")[0] for k in module if k.startswith("enc_")] == ["enc_b0_16_kernel", "enc_b1_16_kernel", "enc_va16_kernel"]
 
 
 @pytest.mark.parametrize("fusion", [7, 31 - 8, 31], ids=["staged", "no-split", "chain32"])
@@ -186,16 +192,18 @@ def test_simulated_intermediate_plans(fusion, nets):
 
 def test_simulated_long_sequence_halo_paths(nets):
     """T = 150 > 128: every cooperative chain kernel needs several workgroups per utterance, i.e. the halo-recompute
-    branches of enc_attn_ffn (block 0, halo 1), enc_attn_ffn_split (block 1, N = 75 > 64) and enc_fuse_va (halo 2)."""
+    branches of enc_attn_ffn_split (block 1, N = 75 > 64) and enc_fuse_va (halo 2).  (Block 0, N = 150, is past
+    enc_attn_ffn_supported's N <= 128 gate: attention + GEMM launches.)"""
     net, cfg, sd = nets("tiny")
     B, T = 2, 150
     ids, mask = synth_phonemes(B, T, 77, [150, 97])
     dur = np.ones((B, T), np.int32)
     dur[:, ::7] = 2
     x = {"phoneme": torch.from_numpy(ids), "phoneme_mask": torch.from_numpy(mask), "duration_forced": torch.from_numpy(dur)}
-    with use_sim(), torch.no_grad():
+    with use_sim(), torch.no_grad(), launched_kernels() as launched:
         enc = net.encoder._encode(x)
         mel, mel_len, _ = net(x)
+    assert {"enc_attn_ffn_split_kernel<4,2,1>", "enc_fuse_va_kernel<1,3>"} <= set(launched)
     o = oracle.phoneme2mel(cfg, oracle.Weights(sd), ids, mask, duration=dur, taps=True)
     np.testing.assert_allclose(enc["duration"].numpy(), o.duration, atol=H.PRED_TOL, rtol=0)
     np.testing.assert_allclose(enc["pitch"].numpy(), o.pitch, atol=H.PRED_TOL, rtol=0)
@@ -450,9 +458,10 @@ def test_simulated_tiny_with_expansion_2_takes_the_per_block_path():
     res = {}
     with use_sim(), torch.no_grad():
         for plan in (_lib.FUSE_ALL, 31, 0):
-            with _lib.launch_plan(plan):
+            with _lib.launch_plan(plan), launched_kernels() as launched:
                 enc = net.encoder._encode(x)
                 mel, mel_len, dpred = net(x)
+            assert not any(k.startswith("enc_all16_kernel") for k in launched), f"plan {plan}"
             res[plan] = (mel.numpy().copy(), mel_len.numpy().copy(), dpred.numpy().copy(), enc)
     o = oracle.phoneme2mel(cfg, oracle.Weights(sd), ids, mask)
     for plan, (mel, mel_len, dpred, enc) in res.items():
@@ -477,8 +486,10 @@ def test_simulated_dim128_model_with_kernel_3_and_odd_length():
     o = oracle.phoneme2mel(cfg, oracle.Weights(sd), ids, mask)
     with use_sim(), torch.no_grad():
         for plan in (_lib.FUSE_ALL, 31):
-            with _lib.launch_plan(plan):
+            with _lib.launch_plan(plan), launched_kernels() as launched:
                 enc = net.encoder._encode(x)
                 mel, mel_len, _ = net(x)
+            round6 = {"enc_fuse128_kernel<3>", "enc_pred128_kernel"}
+            assert round6 <= set(launched) if plan == _lib.FUSE_ALL else not round6 & set(launched), f"plan {plan}"
             err = H.compare_eval_with_oracle(cfg, o, enc, mel, mel_len, sd)
             assert err == err, f"plan {plan}: a discrete decision inside its margin; pick another seed"

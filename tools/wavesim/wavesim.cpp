@@ -5,6 +5,8 @@
 #include <ucontext.h>
 
 #include <atomic>
+#include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -127,7 +129,18 @@ static void run_block(BlockCtx& B) {
     }
 }
 
-void launch(dim3 grid, dim3 block, size_t lds_bytes, const std::function<void()>& body) {
+// the launch log: one line per launch, "<name> <grid x y z> <block x y z> <LDS bytes>" (tests/simlib.py launched_kernels)
+static std::mutex g_log_mu;
+static std::string g_log, g_log_read;
+
+void launch(const char* name, dim3 grid, dim3 block, size_t lds_bytes, const std::function<void()>& body) {
+    {
+        char rec[64];
+        snprintf(rec, sizeof rec, " %u %u %u %u %u %u %zu\n", grid.x, grid.y, grid.z, block.x, block.y, block.z, lds_bytes);
+        std::lock_guard<std::mutex> lk(g_log_mu);
+        g_log += name;
+        g_log += rec;
+    }
     const int nthreads = (int)(block.x * block.y * block.z);
     if (nthreads % 64 != 0) { fprintf(stderr, "wavesim: block size must be a multiple of 64\n"); abort(); }
     const long nblocks = (long)grid.x * grid.y * grid.z;
@@ -166,3 +179,14 @@ void launch(dim3 grid, dim3 block, size_t lds_bytes, const std::function<void()>
 }
 
 }  // namespace wavesim
+
+// (not esmi_*: the product libraries' export list is the C-ABI of include/esmi.h)
+extern "C" const char* wavesim_launch_log() {
+    std::lock_guard<std::mutex> lk(wavesim::g_log_mu);
+    wavesim::g_log_read = wavesim::g_log;   // a copy that stays valid until the next call
+    return wavesim::g_log_read.c_str();
+}
+extern "C" void wavesim_launch_log_clear() {
+    std::lock_guard<std::mutex> lk(wavesim::g_log_mu);
+    wavesim::g_log.clear();
+}

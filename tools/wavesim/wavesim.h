@@ -58,7 +58,8 @@ void sync_block();
 // 64 lanes of the wave have deposited.  The table stays valid until this lane's next collective.
 const uint32_t* wave_exchange(const uint32_t* words, int n);
 int lane_id();
-void launch(dim3 grid, dim3 block, size_t lds_bytes, const std::function<void()>& body);
+// `name`: the kernel as written at the launch site; every launch is appended to the log read by wavesim_launch_log()
+void launch(const char* name, dim3 grid, dim3 block, size_t lds_bytes, const std::function<void()>& body);
 
 }  // namespace wavesim
 
