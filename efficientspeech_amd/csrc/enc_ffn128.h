@@ -12,9 +12,10 @@
 //     (LDS-DMA a step ahead, one workgroup barrier per step).  A set of the convolution = (tap, half of the output channels): its
 //     fragments are 16 runs of 4 KB in the packed array (esmi_pack_bfrag_f32: [tap][k group][slot][8 row tiles]) and land as a 128-row
 //     matrix;
-//   * row +-1 operands: DPP row shifts + the boundary rows of all 16 tiles in a 16 KB LDS exchange buffer (enc_pred128.h).
+//   * row +-1 operands: DPP row shifts + the boundary rows of all 16 tiles in a 16 KB LDS exchange buffer (reg_tile.h).
 #pragma once
-#include "enc_pred128.h"
+#include "enc_params.h"
+#include "reg_tile.h"
 
 namespace esmi {
 
@@ -27,64 +28,10 @@ static_assert(Ffn128Lds::total * 4 <= 160 * 1024, "enc_ffn128: LDS");
 inline int ffn128_lds_bytes() { return Ffn128Lds::total * (int)sizeof(float); }
 enum { GP_PROJB = 0, GP_LN1G = 128, GP_LN1B = 256, GP_MLP2B = 384, GP_LN2G = 512, GP_LN2B = 640, GP_FFNB = 768, GP_FFNB0 = 1024, GP_FFNB2 = 1280 };
 
-namespace g128 {
-using namespace c16;
-using namespace va64;
-using namespace p128;
-// one tap of a k = 3 convolution on ONE tile: c[nt] += W_j . X^T(row + j - 1), W = (tap, output half) as a 128-row matrix in LDS
-template <int J>
-__device__ __forceinline__ void conv_tap1(f32x4 (&c)[NT], const float* W, int lw, const f16x2p (&X)[KG], const unsigned* bnd, int tile, int ntiles, int g) {
-#pragma unroll
-    for (int G = 0; G < KG; ++G) {
-        f16x2p op;
-        if (J == 0) op = rows_dn(X[G], bnd_read8(bnd, tile - 1, 1, G, g, tile > 0));
-        else if (J == 1) op = X[G];
-        else op = rows_up(X[G], bnd_read8(bnd, tile + 1, 0, G, g, tile + 1 < ntiles));
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch) {
-            WFrags<4> wf;
-            wfrags_load<4, 4, 4>(wf, 0, W + 2 * ch * 256, lw, G);
-            f32x4 (&acc4)[4] = *reinterpret_cast<f32x4 (*)[4]>(&c[4 * ch]);
-            mma_all<4>(acc4, wf, op);
-        }
-    }
-}
-// acc[nt] += W[.., 32 G ..] . X[G]^T over the set's four k groups, one tile / two tiles per weight fragment
-__device__ __forceinline__ void set1(f32x4 (&acc)[NT], const float* W, int lw, const f16x2p* X) {
-#pragma unroll
-    for (int G = 0; G < KG; ++G) {
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch) {
-            WFrags<4> wf;
-            wfrags_load<4, 4, 4>(wf, 0, W + 2 * ch * 256, lw, G);
-            f32x4 (&acc4)[4] = *reinterpret_cast<f32x4 (*)[4]>(&acc[4 * ch]);
-            mma_all<4>(acc4, wf, X[G]);
-        }
-    }
-}
-__device__ __forceinline__ void set2(f32x4 (&a0)[NT], f32x4 (&a1)[NT], const float* W, int lw, const f16x2p* X0, const f16x2p* X1) {
-#pragma unroll
-    for (int G = 0; G < KG; ++G) {
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch) {
-            WFrags<4> wf;
-            wfrags_load<4, 4, 4>(wf, 0, W + 2 * ch * 256, lw, G);
-            f32x4 (&p0)[4] = *reinterpret_cast<f32x4 (*)[4]>(&a0[4 * ch]);
-            f32x4 (&p1)[4] = *reinterpret_cast<f32x4 (*)[4]>(&a1[4 * ch]);
-            mma_all<4>(p0, wf, X0[G]);
-            mma_all<4>(p1, wf, X1[G]);
-        }
-    }
-}
-}  // namespace g128
-
 __global__ __launch_bounds__(64 * 8, 1) void enc_post_attn128_kernel(const PostAttn128P p) {
-    using namespace c16;
-    using namespace va64;
-    using namespace p128;
-    using namespace g128;
+    using namespace rt;
     typedef Ffn128Lds M;
-    constexpr int C = 128;
+    constexpr int C = 128, KG = 4, NT = 8;
     ESMI_DYN_LDS(lds);
     const int nw = (int)(blockDim.x >> 6), w = uniform_i(wave_id());
     const int lane = lane_id(), i = lane & 15, g = lane >> 4;
@@ -107,19 +54,10 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_post_attn128_kernel(const PostA
             if (r >= 6) {
                 dma_frags(p.mlp2_w + (r - 6) * (64 * 256), dst, 64, w, nw, lane, rot);
             } else {
-                const int tap = r % 3, half = r / 3;
-                const float* src = p.ffn_w + tap * (128 * 256) + half * (4 * 256);
-                for (int f = w; f < 64; f += nw) {           // fragment (k group, slot, row tile) of the 128-row matrix <- row tile 4 half + tile of the 256-row one
-                    const int fr = (f + rot) & 63;
-                    lds_dma16(src + ((fr >> 2) * 8 + (fr & 3)) * 256 + 4 * lane, dst + fr * 256, lane);
-                }
+                const int tap = r % 3, half = r / 3;      // row tiles 4 half .. of the 256-row matrix
+                dma_cut(p.ffn_w + tap * (128 * 256) + half * (4 * 256), 8, dst, w, nw, lane, rot);
             }
         }
-    };
-    auto step_begin = [&](int k) __attribute__((always_inline)) {
-        wait_vm0();
-        wg_sync_lds();
-        if (k >= 1 && k + 1 < NSET) request(k + 1);
     };
     request(0);
     request(1);
@@ -163,15 +101,15 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_post_attn128_kernel(const PostA
 #pragma unroll
             for (int G = 0; G < KG; ++G) Xc[t][G] = global_bop(r_ctx, row_c[t], G);
         }
-        step_begin(0);
-        set2(a[0], a[1], wb[0], lw, Xc[0], Xc[1]);
+        step_begin(0, NSET, request);
+        set_gemm(a, wb[0], lw, Xc);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
 #pragma unroll
             for (int G = 0; G < KG; ++G) Xc[t][G] = global_bop(r_ctx, row_c[t], KG + G);
         }
-        step_begin(1);
-        set2(a[0], a[1], wb[1], lw, Xc[0], Xc[1]);
+        step_begin(1, NSET, request);
+        set_gemm(a, wb[1], lw, Xc);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             f32x4 gg[NT], bb[NT];
@@ -188,9 +126,9 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_post_attn128_kernel(const PostA
                 if (rz[t] || rout[t]) a[t][nt] = z4;      // (rows outside the sequence: the convolution's zero padding; never stored)
                 buf_st4(r_y1, row_x[t] == kBufOOB ? kBufOOB : row_x[t] + (unsigned)((16 * nt + 4 * g) * 4), a[t][nt]);
             }
-            to_bop8(a[t], Y[t], lower);
+            to_bop(a[t], Y[t], lower);
         }
-        bnd_publish8(bnd, tile0, i, g, Y);
+        bnd_publish(bnd, tile0, i, g, Y);
     }
     // ================================================================ per tile: conv (two halves of the hidden channels) -> GELU -> mlp2, + y1, LN2, mask
 #pragma unroll
@@ -202,12 +140,11 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_post_attn128_kernel(const PostA
             f32x4 m[NT];
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) m[nt] = z4;
-            step_begin(k0 + 3 * hf);
-            conv_tap1<0>(m, wb[(k0 + 3 * hf) & 1], lw, Y[t], bnd, tile0 + t, ntiles, g);
-            step_begin(k0 + 3 * hf + 1);
-            conv_tap1<1>(m, wb[(k0 + 3 * hf + 1) & 1], lw, Y[t], bnd, tile0 + t, ntiles, g);
-            step_begin(k0 + 3 * hf + 2);
-            conv_tap1<2>(m, wb[(k0 + 3 * hf + 2) & 1], lw, Y[t], bnd, tile0 + t, ntiles, g);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                step_begin(k0 + 3 * hf + j, NSET, request);
+                conv_tap(m, wb[(k0 + 3 * hf + j) & 1], lw, j, Y[t], bnd, tile0 + t, ntiles, g);
+            }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 const int c0 = 128 * hf + 16 * nt + 4 * g;
@@ -218,17 +155,17 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_post_attn128_kernel(const PostA
                     m[nt][e] = gelu_fast_f32(fmaf(m[nt][e], kF16WScaleInv, bias));
                 }
             }
-            to_bop8(m, Mo[hf], lower);
+            to_bop(m, Mo[hf], lower);
         }
         f32x4 z[NT], yr[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) z[nt] = z4;
-        step_begin(k0 + 6);
-        set1(z, wb[(k0 + 6) & 1], lw, Mo[0]);
+        step_begin(k0 + 6, NSET, request);
+        set_gemm(z, wb[(k0 + 6) & 1], lw, Mo[0]);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) yr[nt] = buf_ld4(r_y1, row_x[t] == kBufOOB ? kBufOOB : row_x[t] + (unsigned)((16 * nt + 4 * g) * 4));   // (written by this lane in step 1)
-        step_begin(k0 + 7);
-        set1(z, wb[(k0 + 7) & 1], lw, Mo[1]);
+        step_begin(k0 + 7, NSET, request);
+        set_gemm(z, wb[(k0 + 7) & 1], lw, Mo[1]);
         f32x4 gg[NT], bb[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {

@@ -2,35 +2,27 @@
 // ES) in one launch: y1 = mask(LN1(ctx Wp^T + b + x));  out = mask(LN2(mlp2(GELU(conv_k3(y1))) + y1))  (layers/blocks.py:22-29,65,
 // layers/networks.py:73-83; the MixFFN Linear is folded into its k = 3 convolution at pack time, esmi.h `ffn_cw`).
 // The per-op plan ran this as three GEMM launches with the rows going through HBM between them (87 us at B = 256, N = 256: 100 MB of
-// traffic for 0.5 GFLOP each).  Built from enc_va64.h's pieces: a wave owns NTILE 16-row tiles, activations stay in registers (to_bop),
+// traffic for 0.5 GFLOP each).  Built from reg_tile.h's pieces: a wave owns NTILE 16-row tiles, activations stay in registers (to_bop),
 // the convolution's row +-1 operands are DPP row shifts plus a boundary-row exchange, and all 80 KB of weights sit in LDS from the
 // entry barrier on (projection + mlp2 in one 48 KB buffer, the convolution's three taps in the other): two workgroup barriers in all.
 // In place: `out` may be the buffer `x` (a lane reads its own row of x long before it stores that row of out).
 #pragma once
-#include "enc_va64.h"
+#include "enc_params.h"
+#include "reg_tile.h"
 
 namespace esmi {
 
-struct PostAttn64P {
-    const float* ctx;        // (B, N, 64) attention context
-    const float* x;          // (B, N, 64) the block's input rows (residual)
-    float* out;              // (B, N, 64)
-    const float *proj_w, *ffn_w, *mlp2_w;   // esmi_pack_bfrag_f32 arrays (ffn_w: three taps)
-    const float *proj_b, *ln1_g, *ln1_b, *ffn_b, *ffn_b0, *ffn_b2, *mlp2_b, *ln2_g, *ln2_b;
-    const unsigned char* rowmask;            // (B, N) 1 = padding row, or NULL
-    int B, N;
-};
-struct Ffn64Lds {
-    static constexpr int w0 = 0, w1 = Va64Lds::wbuf, par = 2 * Va64Lds::wbuf, par_sz = 768;
-    static constexpr int bnd = par + par_sz, total = bnd + Va64Lds::bnd_sz;
+struct Ffn64Lds {   // floats / dwords
+    static constexpr int wbuf = 12 * 1024;                              // 48 KB: projection + mlp2 | the convolution's three taps
+    static constexpr int w0 = 0, w1 = wbuf, par = 2 * wbuf, par_sz = 768;
+    static constexpr int bnd = par + par_sz, bnd_sz = 2 * kRegTileMaxWaves * 2 * 64, total = bnd + bnd_sz;
 };
 enum { FP_PROJB = 0, FP_LN1G = 64, FP_LN1B = 128, FP_FFNB = 192, FP_FFNB0 = 256, FP_FFNB2 = 320, FP_MLP2B = 384, FP_LN2G = 448, FP_LN2B = 512 };
 inline int ffn64_lds_bytes() { return Ffn64Lds::total * (int)sizeof(float); }
 
 template <int NTILE>
-__global__ __launch_bounds__(64 * kVa64MaxWaves, 1) void enc_post_attn64_kernel(const PostAttn64P p) {
-    using namespace c16;
-    using namespace va64;
+__global__ __launch_bounds__(64 * kRegTileMaxWaves, 1) void enc_post_attn64_kernel(const PostAttn64P p) {
+    using namespace rt;
     typedef Ffn64Lds M;
     constexpr int C = 64;
     ESMI_DYN_LDS(lds);
@@ -87,7 +79,7 @@ __global__ __launch_bounds__(64 * kVa64MaxWaves, 1) void enc_post_attn64_kernel(
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) y[t][nt] = z4;
         }
-        gemm_tiles<NTILE, 2>(y, wA, lw, 0, Xc);
+        set_gemm(y, wA, lw, Xc);
 #pragma unroll
         for (int t = 0; t < NTILE; ++t) {
             f32x4 gg[4], bb[4];
@@ -103,7 +95,7 @@ __global__ __launch_bounds__(64 * kVa64MaxWaves, 1) void enc_post_attn64_kernel(
                 if (rz[t] || rout[t]) y[t][nt] = z4;      // (rows outside the sequence: the convolution's zero padding; never stored)
             to_bop(y[t], Y[t], lower);
         }
-        bnd_publish<NTILE>(bnd, tile0, i, g, Y);
+        bnd_publish(bnd, tile0, i, g, Y);
     }
     wg_sync_lds();
     // ---------------- MixFFN: (Linear folded into) dense conv k3 -> GELU -> mlp2, residual, LN2, mask
@@ -114,7 +106,8 @@ __global__ __launch_bounds__(64 * kVa64MaxWaves, 1) void enc_post_attn64_kernel(
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) { m[t][nt] = z4; z[t][nt] = z4; }
         }
-        conv3<NTILE>(m, wB, lw, Y, bnd, tile0, ntiles, g);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) conv_tap(m, wB + j * (16 * 256), lw, j, Y, bnd, tile0, ntiles, g);
         f16x2p Mo[NTILE][2];
 #pragma unroll
         for (int t = 0; t < NTILE; ++t) {
@@ -130,7 +123,7 @@ __global__ __launch_bounds__(64 * kVa64MaxWaves, 1) void enc_post_attn64_kernel(
             }
             to_bop(m[t], Mo[t], lower);
         }
-        gemm_tiles<NTILE, 2>(z, wA + 16 * 256, lw, 0, Mo);
+        set_gemm(z, wA + 16 * 256, lw, Mo);
 #pragma unroll
         for (int t = 0; t < NTILE; ++t) {
             f32x4 gg[4], bb[4];

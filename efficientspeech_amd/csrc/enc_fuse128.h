@@ -10,12 +10,13 @@
 // rows of the tile above from a 8 KB LDS exchange buffer).  Everything else is row-wise, so the (even, odd) arrangement is invisible
 // outside: the stores go to rows 2 n and 2 n + 1 of feat.
 //   * eight waves; products transposed (lane (i, g): row i, channels 16 nt + 4 g + (0..3) of tile nt), GEMM results become the next
-//     GEMM's operand in registers (p128::to_bop8);
+//     GEMM's operand in registers (reg_tile.h `to_bop`);
 //   * weights: 5 + k sets of 64 KB (Linear_1: two halves of K = 256; Linear_0; Linear_f's C0 half; the k taps; Linear_f's C1 half -- the
 //     order that keeps the fewest rows alive: 192 registers at the peak), two LDS buffers filled by LDS-DMA a step ahead, one workgroup
 //     barrier per step.
 #pragma once
-#include "enc_pred128.h"
+#include "enc_params.h"
+#include "reg_tile.h"
 
 namespace esmi {
 
@@ -30,48 +31,12 @@ static_assert(Fuse128Lds::total * 4 <= 160 * 1024, "enc_fuse128: LDS");
 inline int fuse128_lds_bytes() { return Fuse128Lds::total * (int)sizeof(float); }
 enum { FP_B0 = 0, FP_B1 = 128, FP_UPB = 256, FP_FB = 384 };
 
-namespace f128 {
-using namespace c16;
-using namespace va64;
-using namespace p128;
-// acc[nt] += W[.., 32 G ..] . X[G]^T over the set's four k groups (W: one 64 KB set in LDS), one tile
-__device__ __forceinline__ void set_gemm1(f32x4 (&acc)[NT], const float* W, int lw, const f16x2p* X) {
-#pragma unroll
-    for (int G = 0; G < KG; ++G) {
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch) {
-            WFrags<4> wf;
-            wfrags_load<4, 4, 4>(wf, 0, W + 2 * ch * 256, lw, G);
-            f32x4 (&acc4)[4] = *reinterpret_cast<f32x4 (*)[4]>(&acc[4 * ch]);
-            mma_all<4>(acc4, wf, X[G]);
-        }
-    }
-}
-// ... two tiles per weight fragment
-__device__ __forceinline__ void set_gemm2(f32x4 (&a0)[NT], f32x4 (&a1)[NT], const float* W, int lw, const f16x2p* X0, const f16x2p* X1) {
-#pragma unroll
-    for (int G = 0; G < KG; ++G) {
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch) {
-            WFrags<4> wf;
-            wfrags_load<4, 4, 4>(wf, 0, W + 2 * ch * 256, lw, G);
-            f32x4 (&p0)[4] = *reinterpret_cast<f32x4 (*)[4]>(&a0[4 * ch]);
-            f32x4 (&p1)[4] = *reinterpret_cast<f32x4 (*)[4]>(&a1[4 * ch]);
-            mma_all<4>(p0, wf, X0[G]);
-            mma_all<4>(p1, wf, X1[G]);
-        }
-    }
-}
-}  // namespace f128
-
 // KT = the transposed convolution's kernel size (3 or 5)
 template <int KT>
 __global__ __launch_bounds__(64 * 8, 1) void enc_fuse128_kernel(const FuseVaP p) {
-    using namespace c16;
-    using namespace va64;
-    using namespace p128;
-    using namespace f128;
+    using namespace rt;
     typedef Fuse128Lds M;
+    constexpr int DIM = 128, KG = 4, NT = 8;
     ESMI_DYN_LDS(lds);
     const int nw = (int)(blockDim.x >> 6), w = uniform_i(wave_id());
     const int lane = lane_id(), i = lane & 15, g = lane >> 4;
@@ -90,11 +55,6 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_fuse128_kernel(const FuseVaP p)
         const float* src = k < 2 ? p.mlp_w[1] + k * (64 * 256)
                                  : (k == 2 ? p.mlp_w[0] : (k == 3 ? p.fuse_w : (k < 4 + KT ? p.up_w[1] + (k - 4) * (64 * 256) : p.fuse_w + 64 * 256)));
         dma_frags(src, wb[k & 1], 64, w, nw, lane, rot);
-    };
-    auto step_begin = [&](int k) __attribute__((always_inline)) {
-        wait_vm0();
-        wg_sync_lds();
-        if (k >= 1 && k + 1 < NSET) request(k + 1);
     };
     request(0);
     request(1);
@@ -121,10 +81,10 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_fuse128_kernel(const FuseVaP p)
     // ================================================================ steps 0, 1: y1 = Linear_1(f1 row n) (K = 256: two sets)
     f16x2p Ya[KG];
     {
-        f16x2p Xa[2 * KG];
+        f16x2p Xa[2][KG];
         const unsigned oa = n_ok ? (unsigned)(n * 2 * DIM * 4) + gl_lane(lane) : kBufOOB;
 #pragma unroll
-        for (int ks = 0; ks < 2 * KG; ++ks) Xa[ks] = global_bop(r_f1, oa, ks);
+        for (int ks = 0; ks < 2 * KG; ++ks) Xa[ks / KG][ks % KG] = global_bop(r_f1, oa, ks);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const unsigned o0 = rout[t] ? kBufOOB : (unsigned)(pos[t] * DIM * 4) + gl_lane(lane);
@@ -134,21 +94,15 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_fuse128_kernel(const FuseVaP p)
         f32x4 a[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) a[nt] = z4;
-        step_begin(0);
-        set_gemm1(a, wb[0], lw, Xa);
-        step_begin(1);
-        set_gemm1(a, wb[1], lw, Xa + KG);
+        step_begin(0, NSET, request);
+        set_gemm(a, wb[0], lw, Xa[0]);
+        step_begin(1, NSET, request);
+        set_gemm(a, wb[1], lw, Xa[1]);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
             a[nt] = n_ok ? fmaf4(a[nt], kF16WScaleInv, ld4_lds(par + FP_B1 + 16 * nt + 4 * g)) : z4;      // rows that do not exist contribute nothing
-        to_bop8(a, Ya, lower);
-        if (i >= 14) {   // rows 14, 15 of the tile -> the tile below's rows n - 2, n - 1
-#pragma unroll
-            for (int G = 0; G < KG; ++G) {
-                *reinterpret_cast<u32x4*>(bnd + bnd_at8(w, i - 14, G, 0, g)) = Ya[G].h1;
-                *reinterpret_cast<u32x4*>(bnd + bnd_at8(w, i - 14, G, 1, g)) = Ya[G].h2;
-            }
-        }
+        to_bop(a, Ya, lower);
+        if (i >= 14) bnd_store<KG>(bnd, w, i - 14, g, Ya);   // rows 14, 15 of the tile -> the tile below's rows n - 2, n - 1
     }
     // ================================================================ step 2: Linear_0 on the level-0 rows of both tiles; step 3: Linear_f's C0 half
     f32x4 F[2][NT];
@@ -160,16 +114,16 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_fuse128_kernel(const FuseVaP p)
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) { a[t][nt] = z4; F[t][nt] = z4; }
         }
-        step_begin(2);
-        set_gemm2(a[0], a[1], wb[0], lw, X0[0], X0[1]);
+        step_begin(2, NSET, request);
+        set_gemm(a, wb[0], lw, X0);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) a[t][nt] = fmaf4(a[t][nt], kF16WScaleInv, ld4_lds(par + FP_B0 + 16 * nt + 4 * g));
-            to_bop8(a[t], C0[t], lower);
+            to_bop(a[t], C0[t], lower);
         }
-        step_begin(3);
-        set_gemm2(F[0], F[1], wb[1], lw, C0[0], C0[1]);
+        step_begin(3, NSET, request);
+        set_gemm(F, wb[1], lw, C0);
     }
     // ================================================================ steps 4 .. 3 + KT: the transposed convolution, tap j -> tile j & 1, rows n - (j >> 1);
     // step 4 + KT: Linear_f's C1 half, masked_fill, store
@@ -185,23 +139,23 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_fuse128_kernel(const FuseVaP p)
         for (int G = 0; G < KG; ++G) Ys[G] = Ya[G];
 #pragma unroll
         for (int j = 0; j < KT; ++j) {
-            step_begin(4 + j);
+            step_begin(4 + j, NSET, request);
             if (j >= 2 && (j & 1) == 0) {   // taps 2 s, 2 s + 1 read rows n - s: one more row down, the edge lane takes row 16 - s of the
                 const int s = j >> 1;       // tile above (zero above the sequence)
 #pragma unroll
-                for (int G = 0; G < KG; ++G) Ys[G] = rows_dn(Ys[G], bnd_read8(bnd, w - 1, 2 - s, G, g, w > 0));
+                for (int G = 0; G < KG; ++G) Ys[G] = rows_dn(Ys[G], bnd_read<KG>(bnd, w - 1, 2 - s, G, g, w > 0));
             }
-            set_gemm1(u[j & 1], wb[(4 + j) & 1], lw, Ys);
+            set_gemm(u[j & 1], wb[(4 + j) & 1], lw, Ys);
         }
         f16x2p C1[2][KG];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) u[t][nt] = fmaf4(u[t][nt], kF16WScaleInv, ld4_lds(par + FP_UPB + 16 * nt + 4 * g));
-            to_bop8(u[t], C1[t], lower);
+            to_bop(u[t], C1[t], lower);
         }
-        step_begin(4 + KT);
-        set_gemm2(F[0], F[1], wb[(4 + KT) & 1], lw, C1[0], C1[1]);
+        step_begin(4 + KT, NSET, request);
+        set_gemm(F, wb[(4 + KT) & 1], lw, C1);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const unsigned frow = rout[t] ? kBufOOB : (unsigned)(pos[t] * 4 * DIM * 4);

@@ -13,10 +13,11 @@
 //     step ahead, one workgroup barrier per step; the accumulators stay in registers across the three steps;
 //   * row +- 1 operands by DPP row shifts + a 16 KB LDS exchange buffer for the rows across tile boundaries (first and last row of every
 //     tile; one buffer serves the fused rows, then the hidden rows);
-//   * conv1's result becomes conv2's operand in registers (v_permlane32_swap, enc_va64.h `to_bop`).
+//   * conv1's result becomes conv2's operand in registers (v_permlane32_swap, reg_tile.h `to_bop`).
 // The fused rows come from feat[:, 0 .. dim) (the Fuse stage's launches write them there).
 #pragma once
-#include "enc_va64.h"
+#include "enc_params.h"
+#include "reg_tile.h"
 
 namespace esmi {
 
@@ -31,73 +32,10 @@ static_assert(Pred128Lds::total * 4 <= 160 * 1024, "enc_pred128: LDS");
 inline int pred128_lds_bytes() { return Pred128Lds::total * (int)sizeof(float); }
 enum { PP_C1B = 0, PP_LN1G = 128, PP_LN1B = 256, PP_C2B = 384, PP_LINW = 512, PP_LN2G = 640, PP_LN2B = 768, PP_EDGE = 896 };
 
-namespace p128 {
-using namespace c16;
-using namespace va64;
-constexpr int DIM = 128, KG = 4, NT = 8;
-__device__ __forceinline__ void to_bop8(const f32x4 (&v)[NT], f16x2p (&out)[KG], bool lower) {
-#pragma unroll
-    for (int G = 0; G < KG; ++G) {
-        f32x4 recv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) recv[e] = swap32_f(lower ? v[2 * G + 1][e] : v[2 * G][e]);
-        out[G] = split_f16x2(lower ? v[2 * G] : recv, lower ? recv : v[2 * G + 1]);
-    }
-}
-__device__ __forceinline__ int bnd_at8(int tile, int side, int G, int piece, int g) { return ((tile * 2 + side) * (2 * KG) + G * 2 + piece) * 16 + 4 * g; }
-__device__ __forceinline__ void bnd_publish8(unsigned* bnd, int tile0, int i, int g, const f16x2p (&X)[2][KG]) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        if (i == 0 || i == 15) {
-            const int side = i == 0 ? 0 : 1;
-#pragma unroll
-            for (int G = 0; G < KG; ++G) {
-                *reinterpret_cast<u32x4*>(bnd + bnd_at8(tile0 + t, side, G, 0, g)) = X[t][G].h1;
-                *reinterpret_cast<u32x4*>(bnd + bnd_at8(tile0 + t, side, G, 1, g)) = X[t][G].h2;
-            }
-        }
-    }
-}
-__device__ __forceinline__ f16x2p bnd_read8(const unsigned* bnd, int tile, int side, int G, int g, bool exists) {
-    f16x2p o = zero_bop();
-    if (exists) {
-        o.h1 = *reinterpret_cast<const u32x4*>(bnd + bnd_at8(tile, side, G, 0, g));
-        o.h2 = *reinterpret_cast<const u32x4*>(bnd + bnd_at8(tile, side, G, 1, g));
-    }
-    return o;
-}
-// one tap of a k = 3 convolution: c[t][nt] += W_j . X^T(row + j - 1) over the four k groups; W = the tap's 64 KB in LDS
-__device__ __forceinline__ void conv_tap(f32x4 (&c)[2][NT], const float* W, int lw, int j, const f16x2p (&X)[2][KG], const unsigned* bnd,
-                                         int tile0, int ntiles, int g) {
-#pragma unroll
-    for (int G = 0; G < KG; ++G) {
-        f16x2p op[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int tile = tile0 + t;
-            if (j == 0) op[t] = rows_dn(X[t][G], bnd_read8(bnd, tile - 1, 1, G, g, tile > 0));
-            else if (j == 1) op[t] = X[t][G];
-            else op[t] = rows_up(X[t][G], bnd_read8(bnd, tile + 1, 0, G, g, tile + 1 < ntiles));
-        }
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch) {      // four 16-channel output tiles at a time (the fragments of all eight are 64 registers)
-            WFrags<4> wf;
-            wfrags_load<4, 4, 4>(wf, 0, W + 2 * ch * 256, lw, G);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                f32x4 (&acc4)[4] = *reinterpret_cast<f32x4 (*)[4]>(&c[t][4 * ch]);
-                mma_all<4>(acc4, wf, op[t]);
-            }
-        }
-    }
-}
-}  // namespace p128
-
 __global__ __launch_bounds__(64 * 8, 1) void enc_pred128_kernel(const Pred128P p) {
-    using namespace c16;
-    using namespace va64;
-    using namespace p128;
+    using namespace rt;
     typedef Pred128Lds M;
+    constexpr int DIM = 128, KG = 4, NT = 8;
     ESMI_DYN_LDS(lds);
     const int nw = (int)(blockDim.x >> 6), w = uniform_i(wave_id());
     const int lane = lane_id(), i = lane & 15, g = lane >> 4;
@@ -114,11 +52,6 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_pred128_kernel(const Pred128P p
     // step k = 0..5: tap k % 3 of conv1 (k < 3) / conv2, in buffer k & 1
     auto request = [&](int k) __attribute__((always_inline)) {
         dma_frags((k < 3 ? d.conv1_w : d.conv2_w) + (k % 3) * (64 * 256), wb[k & 1], 64, w, nw, lane, rot);
-    };
-    auto step_begin = [&](int k) __attribute__((always_inline)) {
-        wait_vm0();
-        wg_sync_lds();
-        if (k >= 1 && k + 1 < 6) request(k + 1);
     };
     request(0);
     request(1);
@@ -144,7 +77,7 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_pred128_kernel(const Pred128P p
 #pragma unroll
         for (int G = 0; G < KG; ++G) X[t][G] = global_bop(r_feat, o0, G);
     }
-    bnd_publish8(bnd, tile0, i, g, X);
+    bnd_publish(bnd, tile0, i, g, X);
     f32x4 c[2][NT];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -154,7 +87,7 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_pred128_kernel(const Pred128P p
     // ---------------- conv1 (three taps), ReLU, LayerNorm 1, ReLU -> the hidden rows as conv2's operand
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        step_begin(j);
+        step_begin(j, 6, request);
         if (j == 0 && q < 2 && w == 0) {   // bucket edges (dim - 1 of them), +inf behind: two floats per lane
             const float* bins = d.bins;
             par[PP_EDGE + lane] = bins[lane];
@@ -175,16 +108,16 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_pred128_kernel(const Pred128P p
         layernorm<NT>(c[t], gg, bb);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) c[t][nt] = rout[t] ? z4 : relu4(c[t][nt]);
-        to_bop8(c[t], H[t], lower);
+        to_bop(c[t], H[t], lower);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) c[t][nt] = z4;
     }
     wg_sync_lds();                 // every wave is through its last read of the fused rows' boundary rows: the buffer takes the hidden rows'
-    bnd_publish8(bnd, tile0, i, g, H);
+    bnd_publish(bnd, tile0, i, g, H);
     // ---------------- conv2 (three taps), ReLU, Linear(dim, 1) on the pre-norm2 rows
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        step_begin(3 + j);
+        step_begin(3 + j, 6, request);
         conv_tap(c, wb[(3 + j) & 1], lw, j, H, bnd, tile0, ntiles, g);
     }
     const BufRsrc r_pred = make_rsrc(p.preds[q] + (long)b * p.T, (long)p.T * 4);

@@ -12,7 +12,7 @@
 //     lane (i, g) holds row i and, per 16-channel tile nt, channels 16 nt + 4 g + (0..3));
 //   * a GEMM's output becomes the next GEMM's second operand IN REGISTERS: that operand wants channels {c0..c0+3, c0+8..c0+11},
 //     c0 = 32 G + 16 (g >> 1) + 4 (g & 1), of the lane's row -- the lane's own four channels of tile 2 G (g < 2) or 2 G + 1 (g >= 2)
-//     plus its partner's (lane ^ 32): one v_permlane32_swap per register (`to_bop`), then the f16 split;
+//     plus its partner's (lane ^ 32): one v_permlane32_swap per register (reg_tile.h `to_bop`), then the f16 split;
 //   * the k = 3 convolutions take their row +-1 operands by DPP row shifts (v_mov_dpp row_shr:1 / row_shl:1 inside the 16 lanes that
 //     hold a tile's rows for one g); the rows across a tile boundary come from a 4 KB LDS exchange buffer (first and last row of
 //     every tile), written at the end of the producing step -- the only activation bytes in LDS;
@@ -24,12 +24,11 @@
 //     through LDS; taps that do not apply to a row get a zero operand.
 // Weights: the arrays esmi_pack_bfrag_f32 makes (chain16.h header: NTW = 2 tiles of 32 rows, 16 KiB per 64 x 64 matrix or tap).
 #pragma once
-#include "chain16.h"
-#include "enc_fuse_va.h"
+#include "enc_params.h"
+#include "reg_tile.h"
 
 namespace esmi {
 
-constexpr int kVa64MaxWaves = 8;
 constexpr int kVa64Dim = 64;
 
 struct Va64Lds {   // floats / dwords
@@ -37,7 +36,7 @@ struct Va64Lds {   // floats / dwords
     static constexpr int w0 = 0, w1 = wbuf;
     static constexpr int par = 2 * wbuf;                                // parameter vectors, see VP_*
     static constexpr int par_sz = 512 + 3 * 512 + 768;                  // (+ the decoder head's bias | gain | shift)
-    static constexpr int bnd_sz = 2 * kVa64MaxWaves * 2 * 64;           // [tile][first | last][k group 2][piece 2][16 dwords]
+    static constexpr int bnd_sz = 2 * kRegTileMaxWaves * 2 * 64;      // [tile][first | last][k group 2][piece 2][16 dwords]
     static constexpr int bndF = par + par_sz;
     static constexpr int bndH = bndF + bnd_sz;
     static constexpr int sdur = bndH + bnd_sz;                          // [256] ints
@@ -49,108 +48,9 @@ inline int va64_lds_bytes() { return Va64Lds::total * (int)sizeof(float); }
 enum { VP_MLPB0 = 0, VP_MLPB1 = 64, VP_UPB1 = 128, VP_FUSEB = 192, VP_LN2G = 256, VP_LN2B = 320, VP_EDGE = 384 /* pitch, energy: 63 edges, +inf */,
        VP_PRED = 512 /* + 512 q: conv1_b, ln1_g, ln1_b, conv2_b | lin_w, 3 unused */, VP_HEADB = 2048, VP_HEADG = 2304, VP_HEADBE = 2560 };
 
-namespace va64 {
-using namespace c16;
-
-// rows one down / one up inside the 16 lanes that hold a tile's rows for one g (row_dn_u / row_up_u, wavesim_shim.h): the lane at the
-// tile's edge takes `edge` (the neighbouring tile's row, or zero outside the sequence)
-__device__ __forceinline__ f16x2p rows_dn(const f16x2p& x, const f16x2p& edge) {
-    f16x2p o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { o.h1[e] = row_dn_u(x.h1[e], edge.h1[e]); o.h2[e] = row_dn_u(x.h2[e], edge.h2[e]); }
-    return o;
-}
-__device__ __forceinline__ f16x2p rows_up(const f16x2p& x, const f16x2p& edge) {
-    f16x2p o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { o.h1[e] = row_up_u(x.h1[e], edge.h1[e]); o.h2[e] = row_up_u(x.h2[e], edge.h2[e]); }
-    return o;
-}
-__device__ __forceinline__ f16x2p zero_bop() {
-    f16x2p o;
-    o.h1 = u32x4{0u, 0u, 0u, 0u};
-    o.h2 = u32x4{0u, 0u, 0u, 0u};
-    return o;
-}
-// D^T rows (4 tiles of 16 channels) -> the second operand of the next GEMM's two k groups (see the header)
-__device__ __forceinline__ void to_bop(const f32x4 (&v)[4], f16x2p (&out)[2], bool lower) {
-#pragma unroll
-    for (int G = 0; G < 2; ++G) {
-        f32x4 recv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) recv[e] = swap32_f(lower ? v[2 * G + 1][e] : v[2 * G][e]);
-        out[G] = split_f16x2(lower ? v[2 * G] : recv, lower ? recv : v[2 * G + 1]);
-    }
-}
-// boundary rows: dword index of (tile, side, k group, piece) for lane group g
-__device__ __forceinline__ int bnd_at(int tile, int side, int G, int piece, int g) { return ((tile * 2 + side) * 4 + G * 2 + piece) * 16 + 4 * g; }
-template <int NTILE>
-__device__ __forceinline__ void bnd_publish(unsigned* bnd, int tile0, int i, int g, const f16x2p (&X)[NTILE][2]) {
-#pragma unroll
-    for (int t = 0; t < NTILE; ++t) {
-        if (i == 0 || i == 15) {
-            const int side = i == 0 ? 0 : 1;
-#pragma unroll
-            for (int G = 0; G < 2; ++G) {
-                *reinterpret_cast<u32x4*>(bnd + bnd_at(tile0 + t, side, G, 0, g)) = X[t][G].h1;
-                *reinterpret_cast<u32x4*>(bnd + bnd_at(tile0 + t, side, G, 1, g)) = X[t][G].h2;
-            }
-        }
-    }
-}
-__device__ __forceinline__ f16x2p bnd_read(const unsigned* bnd, int tile, int side, int G, int g, bool exists) {
-    f16x2p o = zero_bop();
-    if (exists) {
-        o.h1 = *reinterpret_cast<const u32x4*>(bnd + bnd_at(tile, side, G, 0, g));
-        o.h2 = *reinterpret_cast<const u32x4*>(bnd + bnd_at(tile, side, G, 1, g));
-    }
-    return o;
-}
-
-// c[t][nt] += sum over the three taps and the two k groups of W_j . X^T(row + j - 1), W = one k = 3 convolution (48 KB) in LDS;
-// every weight fragment is read once for all NTILE tiles of the wave
-template <int NTILE>
-__device__ __forceinline__ void conv3(f32x4 (&c)[NTILE][4], const float* W, int lw, const f16x2p (&X)[NTILE][2], const unsigned* bnd, int tile0,
-                                      int ntiles, int g) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        f16x2p op[NTILE][2];        // the tap's operand rows (shifted one tap at a time: both shifts of both tiles at once are 64 registers)
-#pragma unroll
-        for (int t = 0; t < NTILE; ++t) {
-            const int tile = tile0 + t;
-#pragma unroll
-            for (int G = 0; G < 2; ++G) {
-                if (j == 0) op[t][G] = rows_dn(X[t][G], bnd_read(bnd, tile - 1, 1, G, g, tile > 0));
-                else if (j == 1) op[t][G] = X[t][G];
-                else op[t][G] = rows_up(X[t][G], bnd_read(bnd, tile + 1, 0, G, g, tile + 1 < ntiles));
-            }
-        }
-#pragma unroll
-        for (int G = 0; G < 2; ++G) {
-            WFrags<4> wf;
-            wfrags_load<4, 2, 4>(wf, 0, W + j * (16 * 256), lw, G);
-#pragma unroll
-            for (int t = 0; t < NTILE; ++t) mma_all<4>(c[t], wf, op[t][G]);
-        }
-    }
-}
-// acc[t][nt] += W[.., 32 (G0 + ks) ..] . X[t][ks]^T for ks < KS: W a packed matrix of NTW = 2 row tiles in LDS
-template <int NTILE, int KS>
-__device__ __forceinline__ void gemm_tiles(f32x4 (&acc)[NTILE][4], const float* W, int lw, int G0, const f16x2p (&X)[NTILE][KS]) {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        WFrags<4> wf;
-        wfrags_load<4, 2, 4>(wf, 0, W, lw, G0 + ks);
-#pragma unroll
-        for (int t = 0; t < NTILE; ++t) mma_all<4>(acc[t], wf, X[t][ks]);
-    }
-}
-}  // namespace va64
-
 template <int NTILE>
 __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
-    using namespace c16;
-    using namespace va64;
+    using namespace rt;
     typedef Va64Lds M;
     constexpr int DIM = kVa64Dim;
     ESMI_DYN_LDS(lds);
@@ -187,13 +87,6 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
         }
     };
     const int nset = p.h0 ? 9 + 8 * NTILE : 9;
-    // step k begins: this wave's share of set k has landed, every wave is through step k - 1 (the other buffer is free, the boundary
-    // rows written in step k - 1 are visible); then set k + 1 is requested into the buffer step k - 1 used
-    auto step_begin = [&](int k) __attribute__((always_inline)) {
-        wait_vm0();
-        wg_sync_lds();
-        if (k >= 1 && k + 1 < nset) request(k + 1);
-    };
 
     // ---------------- entry: the rows' own inputs, the first two weight sets and every parameter vector on their way
     request(0);
@@ -249,7 +142,7 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
 
     // ================================================================ step 0: Linear of level 0; Linear of level 1 on row n = pos >> 1 (every level-1 row
     // is computed by the two positions it feeds: the transposed convolution below then needs no gather)
-    step_begin(0);
+    step_begin(0, nset, request);
     f16x2p C0[NTILE][2], Ya[NTILE][2];
     {
         f32x4 a0[NTILE][4], aa[NTILE][4];
@@ -258,7 +151,7 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) { a0[t][nt] = z4; aa[t][nt] = z4; }
         }
-        gemm_tiles<NTILE, 2>(a0, wb[0], lw, 0, X0);
+        set_gemm(a0, wb[0], lw, X0);
 #pragma unroll
         for (int t = 0; t < NTILE; ++t) {
             f32x4 v0[4];
@@ -267,7 +160,7 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
             to_bop(v0, C0[t], lower);
         }
         sched_fence();    // (level 0 is through before level 1 starts: both at once is what the two-tile instantiation cannot hold)
-        gemm_tiles<NTILE, 4>(aa, wb[0] + 16 * 256, lw, 0, Xa);
+        set_gemm(aa, wb[0] + 16 * 256, lw, Xa);
 #pragma unroll
         for (int t = 0; t < NTILE; ++t) {
             f32x4 va[4];
@@ -276,14 +169,14 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
                 va[nt] = na_ok[t] ? fmaf4(aa[t][nt], kF16WScaleInv, ld4_lds(par + VP_MLPB1 + 16 * nt + 4 * g)) : z4;   // rows that do not exist contribute nothing
             to_bop(va, Ya[t], lower);
         }
-        bnd_publish<NTILE>(bndH, tile0, i, g, Ya);    // (the hidden rows' exchange buffer is free until step 3)
+        bnd_publish(bndH, tile0, i, g, Ya);    // (the hidden rows' exchange buffer is free until step 3)
     }
     // ================================================================ step 1: ConvTranspose1d(stride 2, k = 3), cropped to T:
     // out[pos] = W_0 y1[pos/2] + W_2 y1[pos/2 - 1] (pos even) | W_1 y1[(pos-1)/2] (pos odd); a tap that does not apply gets a zero operand.
     // y1[pos/2 - 1] of an even position is what the position above it computed (its n is (pos - 1) >> 1): one row shift.
     const int e_i = lane < DIM - 1 ? lane : DIM - 2;
     const float edge_p = p.pred[0].bins[e_i], edge_e = p.pred[1].bins[e_i];      // bucket edges (dim - 1 of them), requested across the barrier
-    step_begin(1);
+    step_begin(1, nset, request);
     if (w == 0) {   // ... and written with +inf behind them (read seven barriers later)
         par[VP_EDGE + lane] = lane < DIM - 1 ? edge_p : INFINITY;
         par[VP_EDGE + 64 + lane] = lane < DIM - 1 ? edge_e : INFINITY;
@@ -301,20 +194,19 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
 #pragma unroll
         for (int t = 0; t < NTILE; ++t) {
 #pragma unroll
-            for (int G = 0; G < 2; ++G) Yb[t][G] = rows_dn(Ya[t][G], bnd_read(bndH, tile0 + t - 1, 1, G, g, tile0 + t > 0));
+            for (int G = 0; G < 2; ++G) Yb[t][G] = rows_dn(Ya[t][G], bnd_read<2>(bndH, tile0 + t - 1, 1, G, g, tile0 + t > 0));
         }
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
 #pragma unroll
             for (int G = 0; G < 2; ++G) {
-                WFrags<4> wf;
-                wfrags_load<4, 2, 4>(wf, 0, wb[1] + j * (16 * 256), lw, G);
+                f16x2p op[NTILE];
 #pragma unroll
                 for (int t = 0; t < NTILE; ++t) {
                     const bool even = (pos[t] & 1) == 0;
-                    const f16x2p op = j == 0 ? (even ? Ya[t][G] : zb) : (j == 1 ? (even ? zb : Ya[t][G]) : (even ? Yb[t][G] : zb));
-                    mma_all<4>(u[t], wf, op);
+                    op[t] = j == 0 ? (even ? Ya[t][G] : zb) : (j == 1 ? (even ? zb : Ya[t][G]) : (even ? Yb[t][G] : zb));
                 }
+                kgroup(u, wb[1] + j * (16 * 256), lw, G, op);
             }
         }
 #pragma unroll
@@ -326,7 +218,7 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
         }
     }
     // ================================================================ step 2: Linear(2 dim, dim) on the concatenation, masked_fill
-    step_begin(2);
+    step_begin(2, nset, request);
     f16x2p F[NTILE][2];
     {
         f32x4 a[NTILE][4];
@@ -335,8 +227,8 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) a[t][nt] = z4;
         }
-        gemm_tiles<NTILE, 2>(a, wb[0], lw, 0, C0);
-        gemm_tiles<NTILE, 2>(a, wb[0], lw, 2, C1);
+        set_gemm(a, wb[0], lw, C0);
+        set_gemm(a, wb[0], lw, C1, 2);
 #pragma unroll
         for (int t = 0; t < NTILE; ++t) {
             f32x4 fz[4];
@@ -348,7 +240,7 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
             }
             to_bop(fz, F[t], lower);
         }
-        bnd_publish<NTILE>(bndF, tile0, i, g, F);
+        bnd_publish(bndF, tile0, i, g, F);
     }
     // ================================================================ steps 3..8: per predictor conv1 (k = 3) -> ReLU -> LayerNorm -> ReLU, then
     // conv2 (k = 3) -> ReLU -> Linear(dim, 1) on the pre-norm2 rows
@@ -365,7 +257,7 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
                 tv_p[t] = buf_ld(r_pt, trow); tv_e[t] = buf_ld(r_et, trow); tv_d[t] = buf_ld(r_dt, trow);
             }
         }
-        step_begin(3 + 2 * q);
+        step_begin(3 + 2 * q, nset, request);
         {
             f32x4 c[NTILE][4];
 #pragma unroll
@@ -373,7 +265,8 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt) c[t][nt] = z4;
             }
-            conv3<NTILE>(c, wb[(3 + 2 * q) & 1], lw, F, bndF, tile0, ntiles, g);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) conv_tap(c, wb[(3 + 2 * q) & 1] + j * (16 * 256), lw, j, F, bndF, tile0, ntiles, g);
 #pragma unroll
             for (int t = 0; t < NTILE; ++t) {
                 f32x4 v[4], gg[4], bb[4];
@@ -388,9 +281,9 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
                 for (int nt = 0; nt < 4; ++nt) v[nt] = rout[t] ? z4 : relu4(v[nt]);
                 to_bop(v, H[t], lower);
             }
-            bnd_publish<NTILE>(bndH, tile0, i, g, H);
+            bnd_publish(bndH, tile0, i, g, H);
         }
-        step_begin(4 + 2 * q);
+        step_begin(4 + 2 * q, nset, request);
         {
             f32x4 c[NTILE][4];
 #pragma unroll
@@ -398,7 +291,8 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt) c[t][nt] = z4;
             }
-            conv3<NTILE>(c, wb[(4 + 2 * q) & 1], lw, H, bndH, tile0, ntiles, g);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) conv_tap(c, wb[(4 + 2 * q) & 1] + j * (16 * 256), lw, j, H, bndH, tile0, ntiles, g);
 #pragma unroll
             for (int t = 0; t < NTILE; ++t) {
                 float s = 0.0f;
@@ -505,16 +399,10 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
 #pragma unroll
             for (int G = 0; G < 8; ++G) {
                 const int k = 9 + 8 * t + G;
-                step_begin(k);
+                step_begin(k, nset, request);
                 const f16x2p op = G < 2 ? F[t][G] : (G < 6 ? EM[G - 2] : DF[t][G - 6]);
                 const float* W = wb[k & 1];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    WFrags<4> wf;
-                    wfrags_load<4, 8, 4>(wf, 0, W + 2 * c * 256, lw8, 0);
-                    f32x4 (&acc4)[4] = *reinterpret_cast<f32x4 (*)[4]>(&hh[4 * c]);
-                    mma_all<4>(acc4, wf, op);
-                }
+                kgroup(hh, W, lw8, 0, op);
             }
             // bias, tanh, LayerNorm over the 256 channels of the row (two-pass), store
             float s1 = 0.0f;
@@ -574,7 +462,7 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
 }
 
 template <int NTILE>
-__global__ __launch_bounds__(64 * kVa64MaxWaves, 1) void enc_va64_kernel(const FuseVaP p) {
+__global__ __launch_bounds__(64 * kRegTileMaxWaves, 1) void enc_va64_kernel(const FuseVaP p) {
     enc_va64_body<NTILE>(p);
 }
 

@@ -3,7 +3,6 @@
 // clang++ with -DESMI_WAVESIM into libesmi_sim.so (CPU wave simulator used only by tests).
 #include "launch.h"
 #include "mel_decoder.h"   // esmi_decoder_shape helpers used by the one-call forward
-#include "enc_ffn64.h"
 
 using namespace esmi;
 ESMI_TU_RANGE_SETTER(abi)

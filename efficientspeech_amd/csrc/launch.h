@@ -15,6 +15,7 @@
 #include "enc_attn_ffn.h"
 #include "enc_fuse_va.h"
 #include "enc_merge_qkv.h"
+#include "enc_params.h"
 #include "esmi_dev.h"
 #include "small_kernels.h"
 
@@ -41,6 +42,14 @@ inline int raise_lds_limit(const void* fn, AttrOnce& once) {
     }
     return ESMI_OK;
 }
+// raise_lds_limit once per call site, then ESMI_LAUNCH; returns the error from the enclosing launcher.  (A macro: ESMI_LAUNCH
+// stringifies the kernel for the simulator's launch log.)
+#define ESMI_LAUNCH_LDS(kern, grid, block, lds, stream, ...)                                                                   \
+    do {                                                                                                                       \
+        static AttrOnce once_;                                                                                                 \
+        if (int rc_ = raise_lds_limit(reinterpret_cast<const void*>(kern), once_)) return rc_;                                 \
+        ESMI_LAUNCH(kern, grid, block, lds, stream, __VA_ARGS__);                                                              \
+    } while (0)
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 inline int conv_out_len(int n, int k, int stride, int pad) { return (n + 2 * pad - k) / stride + 1; }
@@ -66,7 +75,6 @@ bool enc_va16_ok(const FuseVaP& p, int dim, int kernel);
 int launch_enc_all16(const EncAttnFfnP& b0, const EncAttnFfnP& b1, int c_in1, const FuseVaP& va, int dim, int kernel, hipStream_t st);
 // tu_enc_va64.hip / tu_enc_pred128.hip (round 6: activations in registers, weights streamed through LDS; one workgroup per utterance)
 int launch_enc_va64(const FuseVaP& p, int dim, int kernel, hipStream_t st);   // enc_va64.h: Fuse + variance adaptor of a dim = 64 model, T <= 256
-struct PostAttn64P;
 int launch_enc_post_attn64(const PostAttn64P& p, hipStream_t st);   // enc_ffn64.h: proj + LN1 + MixFFN + LN2 of a C = 64 one-head block, N <= 256
 int launch_enc_pred128(const Pred128P& p, int dim, hipStream_t st);   // enc_pred128.h: three predictors + tail + scan, dim = 128, T <= 256
 int launch_enc_fuse128(const FuseVaP& p, int dim, int kernel, hipStream_t st);   // enc_fuse128.h: the Fuse stage of the same models

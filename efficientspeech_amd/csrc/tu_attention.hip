@@ -39,9 +39,7 @@ int launch_attn(const AttnP& p_in, hipStream_t st) {
         const size_t lds = attn_lds_bytes(p.N, p.C);
         dim3 g2((unsigned)(p.B * p.h));
 #define ESMI_ATTN_LDS(NKT, CKV) do { \
-            static AttrOnce once; \
-            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(attn_lds_kernel<NKT, CKV>), once)) return rc; \
-            ESMI_LAUNCH((attn_lds_kernel<NKT, CKV>), g2, dim3(64 * NKT), lds, st, p); \
+            ESMI_LAUNCH_LDS((attn_lds_kernel<NKT, CKV>), g2, dim3(64 * NKT), lds, st, p); \
         } while (0)
         const int ck = p.C < 128 ? p.C : 128;
         if (nkt <= 4) {

@@ -67,22 +67,17 @@ int launch_convgemm(ConvGemmP p, hipStream_t st) {
         // when the epilogue needs whole rows in one wave
         const int nh = full_row ? 1 : 2, n_items = (int)((rows + 31) / 32) * nh, want = (n_items + kPwWaves - 1) / kPwWaves;
         const dim3 grid((unsigned)(want < 256 ? want : 256));
-        static AttrOnce once[8];
-#define ESMI_PW_CASE(KS_, NT_, AMP_, slot)                                                                                     \
-    do {                                                                                                                       \
-        if (int rc = raise_lds_limit(reinterpret_cast<const void*>(pwgemm_kernel<KS_, NT_, AMP_>), once[slot])) return rc;        \
-        ESMI_LAUNCH((pwgemm_kernel<KS_, NT_, AMP_>), grid, dim3(64 * kPwWaves), pwgemm_lds_bytes<KS_>(), st, p, n_items);        \
-    } while (0)
+#define ESMI_PW_CASE(KS_, NT_, AMP_) ESMI_LAUNCH_LDS((pwgemm_kernel<KS_, NT_, AMP_>), grid, dim3(64 * kPwWaves), pwgemm_lds_bytes<KS_>(), st, p, n_items)
         const int variant = (p.c_in == 128 ? 0 : 4) + (full_row ? 2 : 0) + (p.amp ? 1 : 0);
         switch (variant) {
-            case 0: ESMI_PW_CASE(8, 2, false, 0); break;
-            case 1: ESMI_PW_CASE(8, 2, true, 1); break;
-            case 2: ESMI_PW_CASE(8, 4, false, 2); break;
-            case 3: ESMI_PW_CASE(8, 4, true, 3); break;
-            case 4: ESMI_PW_CASE(5, 2, false, 4); break;
-            case 5: ESMI_PW_CASE(5, 2, true, 5); break;
-            case 6: ESMI_PW_CASE(5, 4, false, 6); break;
-            default: ESMI_PW_CASE(5, 4, true, 7); break;
+            case 0: ESMI_PW_CASE(8, 2, false); break;
+            case 1: ESMI_PW_CASE(8, 2, true); break;
+            case 2: ESMI_PW_CASE(8, 4, false); break;
+            case 3: ESMI_PW_CASE(8, 4, true); break;
+            case 4: ESMI_PW_CASE(5, 2, false); break;
+            case 5: ESMI_PW_CASE(5, 2, true); break;
+            case 6: ESMI_PW_CASE(5, 4, false); break;
+            default: ESMI_PW_CASE(5, 4, true); break;
         }
 #undef ESMI_PW_CASE
         return launch_status();
@@ -106,26 +101,22 @@ int launch_convgemm(ConvGemmP p, hipStream_t st) {
         dim3 g1((unsigned)((nx + 7) / 8 * 8 * ny));
         const bool pre = p.Wp != nullptr && aligned16(p.Wp);
         const int lds_bytes = wide ? convgemm_dma_bytes<8>(1, p.k, p.dil, pre) : convgemm_dma_bytes<4>(mt, p.k, p.dil, pre);
-        static AttrOnce once[12];
-#define ESMI_DMA_CASE(NT_, MT_, AMP_, PRE_, slot)                                                                              \
-    do {                                                                                                                       \
-        if (int rc = raise_lds_limit(reinterpret_cast<const void*>(convgemm_dma_kernel<NT_, MT_, NWV, AMP_, PRE_>), once[slot])) return rc; \
-        ESMI_LAUNCH((convgemm_dma_kernel<NT_, MT_, NWV, AMP_, PRE_>), g1, dim3(64 * NWV), lds_bytes, st, p, nx, ny);           \
-    } while (0)
+#define ESMI_DMA_CASE(NT_, MT_, AMP_, PRE_) \
+    ESMI_LAUNCH_LDS((convgemm_dma_kernel<NT_, MT_, NWV, AMP_, PRE_>), g1, dim3(64 * NWV), lds_bytes, st, p, nx, ny)
         const int variant = (wide ? 8 : (mt == 2 ? 4 : 0)) + (p.amp ? 2 : 0) + (pre ? 1 : 0);
         switch (variant) {
-            case 0: ESMI_DMA_CASE(4, 1, false, false, 0); break;
-            case 1: ESMI_DMA_CASE(4, 1, false, true, 1); break;
-            case 2: ESMI_DMA_CASE(4, 1, true, false, 2); break;
-            case 3: ESMI_DMA_CASE(4, 1, true, true, 3); break;
-            case 4: ESMI_DMA_CASE(4, 2, false, false, 4); break;
-            case 5: ESMI_DMA_CASE(4, 2, false, true, 5); break;
-            case 6: ESMI_DMA_CASE(4, 2, true, false, 6); break;
-            case 7: ESMI_DMA_CASE(4, 2, true, true, 7); break;
-            case 8: ESMI_DMA_CASE(8, 1, false, false, 8); break;
-            case 9: ESMI_DMA_CASE(8, 1, false, true, 9); break;
-            case 10: ESMI_DMA_CASE(8, 1, true, false, 10); break;
-            default: ESMI_DMA_CASE(8, 1, true, true, 11); break;
+            case 0: ESMI_DMA_CASE(4, 1, false, false); break;
+            case 1: ESMI_DMA_CASE(4, 1, false, true); break;
+            case 2: ESMI_DMA_CASE(4, 1, true, false); break;
+            case 3: ESMI_DMA_CASE(4, 1, true, true); break;
+            case 4: ESMI_DMA_CASE(4, 2, false, false); break;
+            case 5: ESMI_DMA_CASE(4, 2, false, true); break;
+            case 6: ESMI_DMA_CASE(4, 2, true, false); break;
+            case 7: ESMI_DMA_CASE(4, 2, true, true); break;
+            case 8: ESMI_DMA_CASE(8, 1, false, false); break;
+            case 9: ESMI_DMA_CASE(8, 1, false, true); break;
+            case 10: ESMI_DMA_CASE(8, 1, true, false); break;
+            default: ESMI_DMA_CASE(8, 1, true, true); break;
         }
 #undef ESMI_DMA_CASE
         return launch_status();

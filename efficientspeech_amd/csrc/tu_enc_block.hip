@@ -23,9 +23,7 @@ int launch_enc_block(const EncAttnFfnP& p, int expansion, int c_in, bool split2,
             EncAttnFfnP q = p;
             q.wgs_per_b = 1; q.useful = useful; q.halo = 0;
             dim3 grid(p.B), block(128 * nw);
-            static AttrOnce once;
-            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(enc_attn_ffn_split_kernel<2, 2, 1, 1, 1, 2>), once)) return rc;
-            ESMI_LAUNCH((enc_attn_ffn_split_kernel<2, 2, 1, 1, 1, 2>), grid, block, lds, st, q);   // N <= 64 here: NKT = 2
+            ESMI_LAUNCH_LDS((enc_attn_ffn_split_kernel<2, 2, 1, 1, 1, 2>), grid, block, lds, st, q);   // N <= 64 here: NKT = 2
             return launch_status();
         }
     }
@@ -39,9 +37,7 @@ int launch_enc_block(const EncAttnFfnP& p, int expansion, int c_in, bool split2,
     dim3 grid(p.B), block(64 * nw);
 #define ESMI_EB(NKT, NC, E, NCI, KT, ST) \
     if (nkt == NKT && nc == NC && expansion == E && nci == NCI && p.m.k == KT && p.m.stride == ST) {                           \
-        static AttrOnce once; /* per instantiation */                                                                          \
-        if (int rc = raise_lds_limit(reinterpret_cast<const void*>(enc_attn_ffn_kernel<NKT, NC, E, NCI, KT, ST>), once)) return rc; \
-        ESMI_LAUNCH((enc_attn_ffn_kernel<NKT, NC, E, NCI, KT, ST>), grid, block, lds, st, q);                                  \
+        ESMI_LAUNCH_LDS((enc_attn_ffn_kernel<NKT, NC, E, NCI, KT, ST>), grid, block, lds, st, q);                                  \
         return launch_status();                                                                                                \
     }
     // tiny block 0 / small block 0 / tiny block 1 (when the split kernel does not apply)

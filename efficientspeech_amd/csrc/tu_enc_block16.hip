@@ -54,9 +54,7 @@ int launch_enc_all16(const EncAttnFfnP& b0, const EncAttnFfnP& b1, int c_in1, co
     q.b0 = b0; q.b1 = b1; q.va = va;
     int lds = B016Lds::total > B116Lds::total ? B016Lds::total : B116Lds::total;
     lds = (lds > Va16Lds::total ? lds : Va16Lds::total) * (int)sizeof(float);
-#define ESMI_ALL(NKT) { static AttrOnce once;                                                                              \
-        if (int rc = raise_lds_limit(reinterpret_cast<const void*>(enc_all16_kernel<NKT>), once)) return rc;                \
-        ESMI_LAUNCH((enc_all16_kernel<NKT>), dim3(b0.B), dim3(64 * nw), lds, st, q); return launch_status(); }
+#define ESMI_ALL(NKT) { ESMI_LAUNCH_LDS((enc_all16_kernel<NKT>), dim3(b0.B), dim3(64 * nw), lds, st, q); return launch_status(); }
     if (nw <= 2) ESMI_ALL(2)
     if (nw <= 4) ESMI_ALL(4)
     ESMI_ALL(8)
@@ -74,9 +72,7 @@ int launch_enc_block16(const EncAttnFfnP& p, int expansion, int c_in, hipStream_
     q.wgs_per_b = 1; q.halo = 0;
     if (b0_16_ok(p)) {
         const int nw = (p.N + 15) / 16, lds = B016Lds::total * (int)sizeof(float);
-#define ESMI_B0(NKT) { static AttrOnce once;                                                                              \
-        if (int rc = raise_lds_limit(reinterpret_cast<const void*>(enc_b0_16_kernel<NKT>), once)) return rc;               \
-        ESMI_LAUNCH((enc_b0_16_kernel<NKT>), dim3(p.B), dim3(64 * nw), lds, st, q); return launch_status(); }
+#define ESMI_B0(NKT) { ESMI_LAUNCH_LDS((enc_b0_16_kernel<NKT>), dim3(p.B), dim3(64 * nw), lds, st, q); return launch_status(); }
         if (nw <= 2) ESMI_B0(2)
         if (nw <= 4) ESMI_B0(4)
         ESMI_B0(8)
@@ -84,9 +80,7 @@ int launch_enc_block16(const EncAttnFfnP& p, int expansion, int c_in, hipStream_
     }
     if (b1_16_ok(p, c_in)) {
         const int nrt = (p.N + 15) / 16, lds = B116Lds::total * (int)sizeof(float);
-        static AttrOnce once;
-        if (int rc = raise_lds_limit(reinterpret_cast<const void*>(enc_b1_16_kernel), once)) return rc;
-        ESMI_LAUNCH(enc_b1_16_kernel, dim3(p.B), dim3(128 * nrt), lds, st, q);
+        ESMI_LAUNCH_LDS(enc_b1_16_kernel, dim3(p.B), dim3(128 * nrt), lds, st, q);
         return launch_status();
     }
     return ESMI_ERR_UNSUPPORTED;

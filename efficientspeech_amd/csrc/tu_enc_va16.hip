@@ -19,9 +19,7 @@ int launch_enc_va16(const FuseVaP& p, int dim, int kernel, hipStream_t st) {
 #if ESMI_CHAIN_SPLIT
     if (!enc_va16_ok(p, dim, kernel)) return ESMI_ERR_UNSUPPORTED;
     const int nw = (p.T + 15) / 16;
-    static AttrOnce once;
-    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(enc_va16_kernel<3>), once)) return rc;
-    ESMI_LAUNCH((enc_va16_kernel<3>), dim3(p.B), dim3(64 * nw), va16_lds_bytes(), st, p);
+    ESMI_LAUNCH_LDS((enc_va16_kernel<3>), dim3(p.B), dim3(64 * nw), va16_lds_bytes(), st, p);
     return launch_status();
 #else
     (void)p; (void)dim; (void)kernel; (void)st;

@@ -78,13 +78,9 @@ inline bool wgrad_on_mfma(const ConvDesc& c) {
 int launch_wgrad_mfma(const ConvDesc& c, const float* x, const float* dy, float* part, float* pb, long chunks, long ps, int* amax, hipStream_t st) {
     const dim3 grid(wgrad_tiles(c), (unsigned)(((chunks + 3) / 4 + 7) & ~7L));
     if (c.transposed) {
-        static AttrOnce once;
-        if (int rc = raise_lds_limit(reinterpret_cast<const void*>(train_conv_wgrad_mfma_kernel<true>), once)) return rc;
-        ESMI_LAUNCH(train_conv_wgrad_mfma_kernel<true>, grid, dim3(256), kWgradLdsBytes, st, c, x, dy, part, pb, chunks, ps, wgrad_chunk(c), amax);
+        ESMI_LAUNCH_LDS(train_conv_wgrad_mfma_kernel<true>, grid, dim3(256), kWgradLdsBytes, st, c, x, dy, part, pb, chunks, ps, wgrad_chunk(c), amax);
     } else {
-        static AttrOnce once;
-        if (int rc = raise_lds_limit(reinterpret_cast<const void*>(train_conv_wgrad_mfma_kernel<false>), once)) return rc;
-        ESMI_LAUNCH(train_conv_wgrad_mfma_kernel<false>, grid, dim3(256), kWgradLdsBytes, st, c, x, dy, part, pb, chunks, ps, wgrad_chunk(c), amax);
+        ESMI_LAUNCH_LDS(train_conv_wgrad_mfma_kernel<false>, grid, dim3(256), kWgradLdsBytes, st, c, x, dy, part, pb, chunks, ps, wgrad_chunk(c), amax);
     }
     return launch_status();
 }
