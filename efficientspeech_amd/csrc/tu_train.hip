@@ -20,9 +20,7 @@ int conv_desc_ok(const esmi_conv_desc* d, ConvDesc* o) {
     *o = ConvDesc{d->B, d->n_in, d->c_in, d->n_out, d->c_out, d->k, d->stride, d->pad, d->groups, d->transposed ? 1 : 0};
     return ESMI_OK;
 }
-}  // namespace
 
-namespace {
 int reduce_flush(esmi_reduce_queue* q, hipStream_t st) {
     if (!q || q->count <= 0) return ESMI_OK;
     if (q->count > ESMI_REDUCE_QUEUE_ITEMS) return ESMI_ERR_ARG;
@@ -54,48 +52,76 @@ int reduce_or_defer(esmi_reduce_queue* q, const float* part, long n, long stride
     q->items[q->count++] = esmi_reduce_item{part, n, stride, chunks, out, n0, out1};
     return ESMI_OK;
 }
+
+// ---- the weight gradient: a first stage writes one partial row [weight partials (nw) | bias partials (c_out)] per chunk of rows into
+// the workspace, reduce_or_defer sums them.  WgradPlan is the one description of that layout.
 inline bool wgrad_depthwise(const ConvDesc& c) { return !c.transposed && c.groups == c.c_in && c.c_in == c.c_out && c.k <= 8; }
-inline bool wgrad_on_mfma(const ConvDesc& c);
-inline unsigned wgrad_tiles(const ConvDesc& c) { return (unsigned)(((c.c_out + 127) / 128) * ((c.c_in + 31) / 32) * c.k); }
-inline int wgrad_chunk(const ConvDesc& c) {   // rows per partial sum: fewer for small weights, whose parallelism must come from the chunks
-    if (wgrad_on_mfma(c)) {
-        // rows per wave, a multiple of 16: as many as give the chip at most two 4-wave workgroups per CU, i.e. ONE round of workgroups
-        // (round 5; before: 96 rows whatever the size -- 800 workgroups = 1.6 rounds for a decoder convolution at B = 128, 34 workgroups
-        // of 6 trips each for the encoder-side ones)
-        const long rows = (long)c.B * c.n_out, want = (rows * wgrad_tiles(c) + 2048 * 16 - 1) / (2048 * 16);
-        return 16 * (int)(want < 1 ? 1 : want > 64 ? 64 : want);
-    }
-    if (wgrad_depthwise(c)) return kTrainChunkDw;
-    const long nw = (long)(c.transposed ? c.c_in * c.c_out : c.c_out * (c.c_in / c.groups)) * c.k;
-    return nw < 1024 ? 32 : kTrainChunk;
-}
 inline bool wgrad_on_mfma(const ConvDesc& c) {
     // (train_ops.h train_conv_wgrad_mfma_kernel: 32-bit byte offsets into both tensors, one utterance boundary per 16-row trip at most)
     const long xb = (long)c.B * c.n_in * c.c_in * 4, yb = (long)c.B * c.n_out * c.c_out * 4;
     return c.groups == 1 && c.c_in >= 8 && c.c_out >= 8 && (c.c_out & 3) == 0 && c.n_out >= 16 && c.n_out < (1 << 23) && xb < 0x7FFFFFFFL && yb < 0x7FFFFFFFL;
 }
-// the matrix-pipe weight gradient (train_ops.h): gridDim = (weight tiles, row groups rounded up to a multiple of 8: XCD-aware order)
-int launch_wgrad_mfma(const ConvDesc& c, const float* x, const float* dy, float* part, float* pb, long chunks, long ps, int* amax, hipStream_t st) {
-    const dim3 grid(wgrad_tiles(c), (unsigned)(((chunks + 3) / 4 + 7) & ~7L));
-    if (c.transposed) {
-        ESMI_LAUNCH_LDS(train_conv_wgrad_mfma_kernel<true>, grid, dim3(256), kWgradLdsBytes, st, c, x, dy, part, pb, chunks, ps, wgrad_chunk(c), amax);
+inline unsigned wgrad_tiles(const ConvDesc& c) { return (unsigned)(((c.c_out + 127) / 128) * ((c.c_in + 31) / 32) * c.k); }
+struct WgradPlan {
+    bool mfma, depthwise;   // the kernel family: matrix pipe, depthwise, else one thread per weight element
+    long nw, rows;          // weight elements; rows (B * n_out) the sums run over
+    int chunk;              // rows per partial sum
+    long chunks, ps;        // partial rows the first stage writes, floats between them
+    long reduce_rows;       // partial rows the reduction reads
+};
+WgradPlan wgrad_plan(const ConvDesc& c) {
+    WgradPlan p;
+    p.mfma = wgrad_on_mfma(c);
+    p.depthwise = wgrad_depthwise(c);
+    p.nw = (long)(c.transposed ? c.c_in * c.c_out : c.c_out * (c.c_in / c.groups)) * c.k;
+    p.rows = (long)c.B * c.n_out;
+    if (p.mfma) {
+        // rows per wave, a multiple of 16: as many as give the chip at most two 4-wave workgroups per CU, i.e. ONE round of workgroups
+        // (round 5; before: 96 rows whatever the size -- 800 workgroups = 1.6 rounds for a decoder convolution at B = 128, 34 workgroups
+        // of 6 trips each for the encoder-side ones)
+        const long want = (p.rows * wgrad_tiles(c) + 2048 * 16 - 1) / (2048 * 16);
+        p.chunk = 16 * (int)(want < 1 ? 1 : want > 64 ? 64 : want);
+    } else if (p.depthwise) {
+        p.chunk = kTrainChunkDw;
     } else {
-        ESMI_LAUNCH_LDS(train_conv_wgrad_mfma_kernel<false>, grid, dim3(256), kWgradLdsBytes, st, c, x, dy, part, pb, chunks, ps, wgrad_chunk(c), amax);
+        p.chunk = p.nw < 1024 ? 32 : kTrainChunk;   // fewer rows for small weights, whose parallelism must come from the chunks
     }
-    return launch_status();
+    p.chunks = train_chunks(p.rows, p.chunk);
+    p.ps = p.nw + c.c_out;
+    p.reduce_rows = p.mfma ? (p.chunks + 3) / 4 : p.chunks;   // the matrix-pipe kernel already summed its four waves: one partial row per workgroup
+    return p;
 }
+// first stage + reduction.  amax (matrix-pipe family only): the kernel leaves max|dy| there for the data-gradient GEMM's operand scale
+int conv_wgrad(const ConvDesc& c, const WgradPlan& p, const float* x, const float* dy, float* dw, float* dbias, float* part, int* amax,
+               esmi_reduce_queue* defer, hipStream_t st) {
+    float* pb = dbias ? part + p.nw : nullptr;
+    if (p.mfma) {   // dense: one wave per (128 output channels x 32 input channels, tap, chunk) on the fp32 MFMA; bias partials from the tap 0, ci0 = 0 waves
+        const dim3 grid(wgrad_tiles(c), (unsigned)((p.reduce_rows + 7) & ~7L));   // row groups rounded up to a multiple of 8: XCD-aware order
+        if (c.transposed) {
+            ESMI_LAUNCH_LDS(train_conv_wgrad_mfma_kernel<true>, grid, dim3(256), kWgradLdsBytes, st, c, x, dy, part, pb, p.chunks, p.ps, p.chunk, amax);
+        } else {
+            ESMI_LAUNCH_LDS(train_conv_wgrad_mfma_kernel<false>, grid, dim3(256), kWgradLdsBytes, st, c, x, dy, part, pb, p.chunks, p.ps, p.chunk, amax);
+        }
+    } else if (p.depthwise && (c.c_out & 3) == 0 && c.stride == 1 && c.n_in == c.n_out) {
+        ESMI_LAUNCH(train_conv_wgrad_dw4_kernel, dim3((unsigned)((c.c_out + 127) / 128), (unsigned)p.chunks), dim3(256), kDwSub * 9 * 128 * sizeof(float),
+                    st, c, x, dy, part, pb, p.ps);
+    } else if (p.depthwise) {
+        ESMI_LAUNCH(train_conv_wgrad_dw_kernel, dim3(grid1d(c.c_out, 64), (unsigned)p.chunks), dim3(64), 0, st, c, x, dy, part, pb, p.ps);
+    } else {
+        ESMI_LAUNCH(train_conv_wgrad_kernel, dim3(grid1d(p.nw, 64), (unsigned)p.chunks), dim3(64), 0, st, c, x, dy, part, p.ps, p.chunk);
+        if (int rc = launch_status()) return rc;
+        if (dbias) ESMI_LAUNCH(train_colsum_kernel, dim3(grid1d(c.c_out, 64), (unsigned)p.chunks), dim3(64), 0, st, dy, p.rows, c.c_out, pb, p.ps, p.chunk);
+    }
+    if (int rc = launch_status()) return rc;
+    // weight and bias partials in ONE reduction: elements >= nw of a partial row are the bias sums
+    return reduce_or_defer(defer, part, dbias ? p.ps : p.nw, p.ps, p.reduce_rows, dw, p.nw, dbias, st);
 }
-// Dense convolutions (groups == 1) of the training step run on the matrix pipe through the inference path's implicit GEMM
-// (convgemm.h) when the caller gives scratch for the tap-major copy of the weight: the forward as it is, the data gradient as
+
+// ---- Dense convolutions (groups == 1) of the training step run on the matrix pipe through the inference path's implicit GEMM
+// (convgemm.h) when there is room for the tap-major copy of the weight: the forward as it is, the data gradient as
 // the transposed problem -- d(Conv1d) is a ConvTranspose1d of dy with the same (Cout, Cin, k) tensor read as (Cin', Cout', k),
 // d(ConvTranspose1d) is a Conv1d of dy with (Cin, Cout, k) read as (Cout', Cin', k).  Everything else (depthwise, channel
-// counts the GEMM does not take, no scratch) runs the one-thread-per-element kernels of train_ops.h.
-size_t esmi_train_conv_workspace_bytes(const esmi_conv_desc* d) {
-    ConvDesc c;
-    if (conv_desc_ok(d, &c) || c.groups != 1) return 0;
-    return align256((size_t)c.k * c.c_out * c.c_in * sizeof(float)) + 256;   // + the data gradient's absmax / scale slots
-}
-namespace {
+// counts the GEMM does not take, no room) runs the one-thread-per-element kernels of train_ops.h.
 // how the GEMM of one direction reads the weight tensor: (supported, needs a copy, read as ConvTranspose1d, taps flipped)
 struct GemmWeight { bool ok, copy; int as_convT; bool flipped; int cin, cout; };
 GemmWeight gemm_weight(const ConvDesc& c, bool grad) {
@@ -110,56 +136,74 @@ GemmWeight gemm_weight(const ConvDesc& c, bool grad) {
     g.copy = !(c.k == 1 && !g.as_convT && !grad);   // a Linear's (Cout, Cin) IS its tap-major form
     return g;
 }
-// one of the two implicit-GEMM problems of a dense conv: returns ESMI_ERR_UNSUPPORTED when the GEMM does not take the shape
-// (have_absmax: max|in| already sits in the workspace's absmax slot -- the weight-gradient pass of esmi_train_conv_bwd_f32 left it)
-// prepacked: `wt` already holds this step's copy (esmi_train_pack_weights_f32, which also cleared the absmax slot)
-struct ConvLnArgs { const float *res, *g, *b; const unsigned char* rowmask; int relu_out; float *pre, *mean, *rstd; };
-int train_conv_gemm(const ConvDesc& c, bool grad, const float* in, const float* w, const float* bias, float* out, float* wt,
-                    bool amp, hipStream_t st, bool have_absmax = false, bool pack_only = false, bool prepacked = false, int act = 0,
-                    const ConvLnArgs* ln = nullptr) {
-    const GemmWeight g = gemm_weight(c, grad);
-    if (!g.ok || !wt) return ESMI_ERR_UNSUPPORTED;
-    // (the fused conv + LayerNorm epilogue exists for 32 / 64 / 128 output channels: refuse BEFORE anything is enqueued -- the caller's
-    // two-launch fallback then packs once, not twice)
-    if (ln && g.cout != 32 && g.cout != 64 && g.cout != 128) return ESMI_ERR_UNSUPPORTED;
-    const int cin = g.cin, cout = g.cout, as_convT = g.as_convT;
-    const bool as_flipped_conv = g.flipped;
+// where the GEMM's copy of the weight lives: this step's copy behind the descriptor (esmi_train_pack_weights_f32 made it and cleared
+// its absmax slot), else the caller's workspace (to be packed by the call), else nowhere (wt == nullptr: no GEMM)
+struct WeightCopy { float* wt; bool packed; };
+WeightCopy weight_copy(const esmi_conv_desc* d, bool grad, void* workspace, size_t workspace_bytes) {
+    if (float* pre = grad ? d->packed_grad : d->packed_fwd) return {pre, true};
+    if (workspace && workspace_bytes >= esmi_train_conv_workspace_bytes(d)) return {static_cast<float*>(workspace), false};
+    return {nullptr, false};
+}
+// the absmax / scale slots behind a weight copy (esmi_train_conv_workspace_bytes)
+inline int* absmax_slot(float* wt, const ConvDesc& c) {
+    return reinterpret_cast<int*>(reinterpret_cast<char*>(wt) + align256((size_t)c.k * c.c_out * c.c_in * sizeof(float)));
+}
+// the tap-major copy of the weight for one direction; the data gradient's pack also zeroes the absmax slot
+int pack_weight(const ConvDesc& c, const GemmWeight& g, bool grad, const float* w, float* wt, hipStream_t st) {
     const long n = (long)c.k * c.c_out * c.c_in;
-    int* amax = reinterpret_cast<int*>(reinterpret_cast<char*>(wt) + align256((size_t)n * sizeof(float)));
-    const float* wuse = wt;
-    if (!g.copy) {
-        wuse = w;                                   // no copy
-    } else if (!have_absmax && !prepacked) {   // (with have_absmax the pack ran in the pack_only call that preceded the weight-gradient pass)
-        ESMI_LAUNCH(pack_conv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, wt, cout, cin, c.k, as_convT, grad ? amax : nullptr,
-                    as_flipped_conv ? 1 : 0);
-        if (int rc = launch_status()) return rc;
-    }
-    if (pack_only) return ESMI_OK;
+    ESMI_LAUNCH(pack_conv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, wt, g.cout, g.cin, c.k, g.as_convT,
+                grad ? absmax_slot(wt, c) : nullptr, g.flipped ? 1 : 0);
+    return launch_status();
+}
+// max|dy| on the device; the GEMM kernels derive the power-of-two scales from it (convgemm.h conv_pow2_scales)
+int measure_absmax(const ConvDesc& c, const float* dy, int* amax, hipStream_t st) {
+    const long len = (long)c.B * c.n_out * c.c_out, blocks = (len + 256L * 8 - 1) / (256L * 8);
+    ESMI_LAUNCH(absmax_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, st, dy, len, amax);
+    return launch_status();
+}
+struct ConvLnArgs { const float *res, *g, *b; const unsigned char* rowmask; int relu_out; float *pre, *mean, *rstd; };
+// one of the two implicit-GEMM problems of a dense conv.  wg: the weight as the GEMM reads it; io_scale (data gradient): the slot max|dy| sits in
+int launch_conv_gemm(const ConvDesc& c, const GemmWeight& g, bool grad, const float* in, const float* wg, const float* bias, float* out,
+                     bool amp, const int* io_scale, int act, const ConvLnArgs* ln, hipStream_t st) {
     ConvGemmP p = conv_defaults();
-    if (grad && have_absmax) {
-        p.io_scale = reinterpret_cast<const float*>(amax);
-    } else if (grad) {   // max|dy| on the device; the GEMM kernels derive the power-of-two scales from it (convgemm.h conv_pow2_scales)
-        const long len = (long)c.B * c.n_out * c.c_out, blocks = (len + 256L * 8 - 1) / (256L * 8);
-        ESMI_LAUNCH(absmax_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, st, in, len, amax);
-        if (int rc = launch_status()) return rc;
-        p.io_scale = reinterpret_cast<const float*>(amax);
-    }
-    p.mode = (as_convT && !as_flipped_conv) ? MODE_CONVT : MODE_CONV;
-    p.k = c.k; p.stride = c.stride; p.pad = as_flipped_conv ? c.k - 1 - c.pad : c.pad;
-    p.B = c.B; p.n_in = grad ? c.n_out : c.n_in; p.n_out = grad ? c.n_in : c.n_out; p.c_in = cin; p.c_out = cout;
-    p.A = in; p.lda = cin; p.W = wuse; p.bias = bias; p.out = out; p.ldo = cout;
+    p.io_scale = reinterpret_cast<const float*>(io_scale);
+    p.mode = (g.as_convT && !g.flipped) ? MODE_CONVT : MODE_CONV;
+    p.k = c.k; p.stride = c.stride; p.pad = g.flipped ? c.k - 1 - c.pad : c.pad;
+    p.B = c.B; p.n_in = grad ? c.n_out : c.n_in; p.n_out = grad ? c.n_in : c.n_out; p.c_in = g.cin; p.c_out = g.cout;
+    p.A = in; p.lda = g.cin; p.W = wg; p.bias = bias; p.out = out; p.ldo = g.cout;
     p.amp = amp ? 1 : 0;
     p.act = act;
     p.pw_ok = 1;
     if (ln) {   // act(conv + bias) + res -> LayerNorm (+ ReLU, + row mask) in the GEMM's epilogue; the pre-norm tensor, mean, rstd kept
-        p.res = ln->res; p.ldr = cout; p.r_coff = 0;
+        p.res = ln->res; p.ldr = g.cout; p.r_coff = 0;
         p.ln_g = ln->g; p.ln_b = ln->b; p.rowmask = ln->rowmask; p.post_relu = ln->relu_out;
         p.ln_pre = ln->pre; p.ln_mean = ln->mean; p.ln_rstd = ln->rstd;
     }
     return launch_convgemm(p, st);
 }
+// one direction on its own: pack unless the step already did -> (data gradient) max|dy| -> GEMM.  ESMI_ERR_UNSUPPORTED when the GEMM
+// does not take the shape or there is no room for the weight's copy.
+int conv_gemm(const esmi_conv_desc* d, const ConvDesc& c, bool grad, const float* in, const float* w, const float* bias, float* out,
+              WeightCopy wc, hipStream_t st, const ConvLnArgs* ln = nullptr) {
+    const GemmWeight g = gemm_weight(c, grad);
+    if (!g.ok || !wc.wt) return ESMI_ERR_UNSUPPORTED;
+    // (the fused conv + LayerNorm epilogue exists for 32 / 64 / 128 output channels: refuse BEFORE anything is enqueued -- the caller's
+    // two-launch fallback then packs once, not twice)
+    if (ln && g.cout != 32 && g.cout != 64 && g.cout != 128) return ESMI_ERR_UNSUPPORTED;
+    if (g.copy && !wc.packed)
+        if (int rc = pack_weight(c, g, grad, w, wc.wt, st)) return rc;
+    int* amax = grad ? absmax_slot(wc.wt, c) : nullptr;
+    if (grad)
+        if (int rc = measure_absmax(c, in, amax, st)) return rc;
+    return launch_conv_gemm(c, g, grad, in, g.copy ? wc.wt : w, bias, out, d->precision == 16, amax, grad ? 0 : d->act, ln, st);
+}
 }  // namespace
 
+size_t esmi_train_conv_workspace_bytes(const esmi_conv_desc* d) {
+    ConvDesc c;
+    if (conv_desc_ok(d, &c) || c.groups != 1) return 0;
+    return align256((size_t)c.k * c.c_out * c.c_in * sizeof(float)) + 256;   // + the data gradient's absmax / scale slots
+}
 int esmi_train_pack_weights_f32(const esmi_conv_desc* descs, const float* const* weights, int n, esmi_stream_t stream) {
     if (n < 0 || (n > 0 && (!descs || !weights))) return ESMI_ERR_ARG;
     PackBatch b;
@@ -184,8 +228,7 @@ int esmi_train_pack_weights_f32(const esmi_conv_desc* descs, const float* const*
             if (!dst) continue;
             const GemmWeight g = gemm_weight(c, grad != 0);
             if (!g.ok || !g.copy) continue;         // the direction does not run as a GEMM / reads the tensor as it is
-            int* amax = reinterpret_cast<int*>(reinterpret_cast<char*>(dst) + align256((size_t)nw * sizeof(float)));
-            b.items[b.count++] = PackItem{weights[i], dst, grad ? amax : nullptr, g.cout, g.cin, c.k, g.as_convT, g.flipped ? 1 : 0};
+            b.items[b.count++] = PackItem{weights[i], dst, grad ? absmax_slot(dst, c) : nullptr, g.cout, g.cin, c.k, g.as_convT, g.flipped ? 1 : 0};
             nmax = nw > nmax ? nw : nmax;
             if (b.count == kPackBatch) if (int rc = flush()) return rc;
         }
@@ -199,21 +242,16 @@ int esmi_train_conv_ln_fwd_f32(const esmi_conv_desc* d, const float* x, const fl
     if (int rc = conv_desc_ok(d, &c)) return rc;
     if (!x || !w || !ln_g || !ln_b || !y_pre || !y || !mean || !rstd || d->act < 0 || d->act > ACT_TANH) return ESMI_ERR_ARG;
     if (c.stride != 1 || c.transposed || c.n_in != c.n_out) return ESMI_ERR_UNSUPPORTED;
-    if (!(d->packed_fwd || (workspace && workspace_bytes >= esmi_train_conv_workspace_bytes(d)))) return ESMI_ERR_UNSUPPORTED;
-    float* wt = d->packed_fwd ? d->packed_fwd : static_cast<float*>(workspace);
     const ConvLnArgs ln{res, ln_g, ln_b, rowmask, relu_out ? 1 : 0, y_pre, mean, rstd};
-    return train_conv_gemm(c, false, x, w, bias, y, wt, d->precision == 16, S(stream), false, false, d->packed_fwd != nullptr, d->act, &ln);
+    return conv_gemm(d, c, false, x, w, bias, y, weight_copy(d, false, workspace, workspace_bytes), S(stream), &ln);
 }
 int esmi_train_conv_fwd_f32(const esmi_conv_desc* d, const float* x, const float* w, const float* bias, float* y, void* workspace,
                             size_t workspace_bytes, esmi_stream_t stream) {
     ConvDesc c;
     if (int rc = conv_desc_ok(d, &c)) return rc;
     if (!x || !w || !y || d->act < 0 || d->act > ACT_TANH) return ESMI_ERR_ARG;
-    if (d->packed_fwd || (workspace && workspace_bytes >= esmi_train_conv_workspace_bytes(d))) {
-        float* wt = d->packed_fwd ? d->packed_fwd : static_cast<float*>(workspace);
-        const int rc = train_conv_gemm(c, false, x, w, bias, y, wt, d->precision == 16, S(stream), false, false, d->packed_fwd != nullptr, d->act);
-        if (rc != ESMI_ERR_UNSUPPORTED) return rc;
-    }
+    const int rc = conv_gemm(d, c, false, x, w, bias, y, weight_copy(d, false, workspace, workspace_bytes), S(stream));
+    if (rc != ESMI_ERR_UNSUPPORTED) return rc;
     const long n = (long)c.B * c.n_out * c.c_out;
     if (wgrad_depthwise(c) && c.stride == 1 && (c.c_out & 3) == 0) {
         ESMI_LAUNCH(train_conv_dw_kernel, grid1d((long)c.B * ((c.n_out + kDwRows - 1) / kDwRows) * (c.c_out / 4)), dim3(256), 0, S(stream), c, x, w, bias, y, 0);
@@ -232,11 +270,8 @@ int esmi_train_conv_dgrad_f32(const esmi_conv_desc* d, const float* dy, const fl
     ConvDesc c;
     if (int rc = conv_desc_ok(d, &c)) return rc;
     if (!dy || !w || !dx) return ESMI_ERR_ARG;
-    if (d->packed_grad || (workspace && workspace_bytes >= esmi_train_conv_workspace_bytes(d))) {
-        float* wt = d->packed_grad ? d->packed_grad : static_cast<float*>(workspace);
-        const int rc = train_conv_gemm(c, true, dy, w, nullptr, dx, wt, d->precision == 16, S(stream), false, false, d->packed_grad != nullptr);
-        if (rc != ESMI_ERR_UNSUPPORTED) return rc;
-    }
+    const int rc = conv_gemm(d, c, true, dy, w, nullptr, dx, weight_copy(d, true, workspace, workspace_bytes), S(stream));
+    if (rc != ESMI_ERR_UNSUPPORTED) return rc;
     const long n = (long)c.B * c.n_in * c.c_in;
     if (wgrad_depthwise(c) && c.stride == 1 && (c.c_out & 3) == 0) {
         ESMI_LAUNCH(train_conv_dw_kernel, grid1d((long)c.B * ((c.n_in + kDwRows - 1) / kDwRows) * (c.c_in / 4)), dim3(256), 0, S(stream), c, dy, w, nullptr, dx, 1);
@@ -248,43 +283,16 @@ int esmi_train_conv_dgrad_f32(const esmi_conv_desc* d, const float* dy, const fl
 size_t esmi_train_conv_wgrad_workspace_bytes(const esmi_conv_desc* d) {
     ConvDesc c;
     if (conv_desc_ok(d, &c)) return 0;
-    const long nw = (long)(c.transposed ? c.c_in * c.c_out : c.c_out * (c.c_in / c.groups)) * c.k;
-    const long chunks = train_chunks((long)c.B * c.n_out, wgrad_chunk(c));
-    return (size_t)chunks * (size_t)(nw + c.c_out) * sizeof(float);
+    const WgradPlan p = wgrad_plan(c);
+    return (size_t)p.chunks * (size_t)p.ps * sizeof(float);
 }
-static int conv_wgrad_impl(const esmi_conv_desc* d, const float* x, const float* dy, float* dw, float* dbias, void* workspace,
-                           size_t workspace_bytes, esmi_reduce_queue* defer, esmi_stream_t stream) {
+int esmi_train_conv_wgrad_f32(const esmi_conv_desc* d, const float* x, const float* dy, float* dw, float* dbias, void* workspace,
+                              size_t workspace_bytes, esmi_stream_t stream) {
     ConvDesc c;
     if (int rc = conv_desc_ok(d, &c)) return rc;
     if (!x || !dy || !dw || !workspace) return ESMI_ERR_ARG;
     if (workspace_bytes < esmi_train_conv_wgrad_workspace_bytes(d)) return ESMI_ERR_WORKSPACE;
-    const long nw = (long)(c.transposed ? c.c_in * c.c_out : c.c_out * (c.c_in / c.groups)) * c.k;
-    const bool mfma = wgrad_on_mfma(c), depthwise = wgrad_depthwise(c);
-    const long rows = (long)c.B * c.n_out, chunks = train_chunks(rows, wgrad_chunk(c));
-    float* part = static_cast<float*>(workspace);   // [chunk][weight partials (nw) | bias partials (c_out)]
-    float* pb = part + nw;
-    const long ps = nw + c.c_out;
-    if (mfma) {   // dense: one wave per (128 output channels x 32 input channels, tap, chunk) on the fp32 MFMA; bias partials from the tap 0, ci0 = 0 waves
-        if (int rc = launch_wgrad_mfma(c, x, dy, part, dbias ? pb : nullptr, chunks, ps, nullptr, S(stream))) return rc;
-    } else if (depthwise && (c.c_out & 3) == 0 && c.stride == 1 && c.n_in == c.n_out) {
-        ESMI_LAUNCH(train_conv_wgrad_dw4_kernel, dim3((unsigned)((c.c_out + 127) / 128), (unsigned)chunks), dim3(256), kDwSub * 9 * 128 * sizeof(float),
-                    S(stream), c, x, dy, part, dbias ? pb : nullptr, ps);
-    } else if (depthwise) {
-        ESMI_LAUNCH(train_conv_wgrad_dw_kernel, dim3(grid1d(c.c_out, 64), (unsigned)chunks), dim3(64), 0, S(stream), c, x, dy, part,
-                    dbias ? pb : nullptr, ps);
-    } else {
-        ESMI_LAUNCH(train_conv_wgrad_kernel, dim3(grid1d(nw, 64), (unsigned)chunks), dim3(64), 0, S(stream), c, x, dy, part, ps, wgrad_chunk(c));
-        if (int rc = launch_status()) return rc;
-        if (dbias) ESMI_LAUNCH(train_colsum_kernel, dim3(grid1d(c.c_out, 64), (unsigned)chunks), dim3(64), 0, S(stream), dy, rows, c.c_out, pb, ps, wgrad_chunk(c));
-    }
-    if (int rc = launch_status()) return rc;
-    // weight and bias partials in ONE reduction: elements >= nw of a partial row are the bias sums
-    // (the matrix-pipe kernel already summed its four waves: one partial row per workgroup)
-    return reduce_or_defer(defer, part, dbias ? ps : nw, ps, mfma ? (chunks + 3) / 4 : chunks, dw, nw, dbias, S(stream));
-}
-int esmi_train_conv_wgrad_f32(const esmi_conv_desc* d, const float* x, const float* dy, float* dw, float* dbias, void* workspace,
-                              size_t workspace_bytes, esmi_stream_t stream) {
-    return conv_wgrad_impl(d, x, dy, dw, dbias, workspace, workspace_bytes, nullptr, stream);
+    return conv_wgrad(c, wgrad_plan(c), x, dy, dw, dbias, static_cast<float*>(workspace), nullptr, nullptr, S(stream));
 }
 int esmi_train_reduce_flush_f32(esmi_reduce_queue* q, esmi_stream_t stream) {
     if (!q) return ESMI_ERR_ARG;
@@ -299,46 +307,42 @@ int esmi_train_conv_bwd_f32(const esmi_conv_desc* d, const float* x, const float
     if (int rc = conv_desc_ok(d, &c)) return rc;
     if (!x || !dy || !w || !dx || !dw || !workspace) return ESMI_ERR_ARG;
     if (workspace_bytes < esmi_train_conv_bwd_workspace_bytes(d)) return ESMI_ERR_WORKSPACE;
+    // the workspace: [weight-gradient partials | the data-gradient GEMM's weight copy, unless the step packed one]
     const size_t wg_bytes = align256(esmi_train_conv_wgrad_workspace_bytes(d)), gemm_bytes = esmi_train_conv_workspace_bytes(d);
-    char* ws = static_cast<char*>(workspace);
-    const bool pre = d->packed_grad != nullptr;
-    float* wt = pre ? d->packed_grad : reinterpret_cast<float*>(ws + wg_bytes);
-    // dense shapes whose two gradients both run on the matrix pipe: tap-major weight copy (zeroes the absmax slot) -> weight gradient
-    // (leaves max|dy| in the slot) -> data-gradient GEMM scaled by it.  Everything else: the two stand-alone entry points.
-    const bool fused = gemm_bytes > 0 && wgrad_on_mfma(c) &&
-                       train_conv_gemm(c, true, dy, w, nullptr, dx, wt, d->precision == 16, S(stream), false, true, pre) == ESMI_OK;
-    if (!fused) {
-        if (c.c_out == 1 && c.k == 1 && c.stride == 1 && c.pad == 0 && c.groups == 1 && !c.transposed && c.n_in == c.n_out && wgrad_chunk(c) <= 64) {
-            // a Linear down to one channel: the three gradients in one launch (train_ops.h train_lin1_bwd_kernel)
-            const long rows = (long)c.B * c.n_out, chunks = train_chunks(rows, wgrad_chunk(c));
-            float* part = reinterpret_cast<float*>(ws);
-            const long ps = c.c_in + 1;
-            const bool al16 = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(w)) & 15) == 0;
-            float* pbias = dbias ? part + c.c_in : nullptr;
-#define ESMI_LIN1(LPR) ESMI_LAUNCH(train_lin1_bwd4_kernel<LPR>, dim3((unsigned)chunks), dim3(64), 0, S(stream), x, dy, w, rows, dx, part, pbias, ps)
-            if (al16 && wgrad_chunk(c) == 32 && c.c_in == 16) ESMI_LIN1(4);
-            else if (al16 && wgrad_chunk(c) == 32 && c.c_in == 32) ESMI_LIN1(8);
-            else if (al16 && wgrad_chunk(c) == 32 && c.c_in == 64) ESMI_LIN1(16);
-            else if (al16 && wgrad_chunk(c) == 32 && c.c_in == 128) ESMI_LIN1(32);
-            else if (al16 && wgrad_chunk(c) == 32 && c.c_in == 256) ESMI_LIN1(64);
-            else
-                ESMI_LAUNCH(train_lin1_bwd_kernel, dim3((unsigned)chunks), dim3(64), 0, S(stream), x, dy, w, rows, c.c_in, dx, part, pbias, ps, wgrad_chunk(c));
-#undef ESMI_LIN1
-            if (int rc = launch_status()) return rc;
-            return reduce_or_defer(defer, part, dbias ? ps : (long)c.c_in, ps, chunks, dw, c.c_in, dbias, S(stream));
-        }
-        if (int rc = esmi_train_conv_dgrad_f32(d, dy, w, dx, gemm_bytes ? wt : nullptr, gemm_bytes, stream)) return rc;
-        return conv_wgrad_impl(d, x, dy, dw, dbias, workspace, wg_bytes, defer, stream);
+    float* part = static_cast<float*>(workspace);
+    const WeightCopy wc = weight_copy(d, true, static_cast<char*>(workspace) + wg_bytes, gemm_bytes);
+    const WgradPlan p = wgrad_plan(c);
+    const GemmWeight g = gemm_weight(c, true);
+    if (gemm_bytes > 0 && p.mfma && g.ok) {
+        // dense shapes whose two gradients both run on the matrix pipe: tap-major weight copy (zeroes the absmax slot) -> weight gradient
+        // (leaves max|dy| in the slot) -> its reduction -> data-gradient GEMM scaled by it
+        int* amax = absmax_slot(wc.wt, c);
+        if (!wc.packed)
+            if (int rc = pack_weight(c, g, true, w, wc.wt, S(stream))) return rc;
+        if (int rc = conv_wgrad(c, p, x, dy, dw, dbias, part, amax, defer, S(stream))) return rc;
+        return launch_conv_gemm(c, g, true, dy, wc.wt, nullptr, dx, d->precision == 16, amax, 0, nullptr, S(stream));
     }
-    const long nw = (long)(c.transposed ? c.c_in * c.c_out : c.c_out * (c.c_in / c.groups)) * c.k;
-    int* amax = reinterpret_cast<int*>(reinterpret_cast<char*>(wt) + align256((size_t)nw * sizeof(float)));
-    const long rows = (long)c.B * c.n_out, chunks = train_chunks(rows, wgrad_chunk(c));
-    float* part = reinterpret_cast<float*>(ws);
-    float* pb = part + nw;
-    const long ps = nw + c.c_out;
-    if (int rc = launch_wgrad_mfma(c, x, dy, part, dbias ? pb : nullptr, chunks, ps, amax, S(stream))) return rc;
-    if (int rc = reduce_or_defer(defer, part, dbias ? ps : nw, ps, (chunks + 3) / 4, dw, nw, dbias, S(stream))) return rc;
-    return train_conv_gemm(c, true, dy, w, nullptr, dx, wt, d->precision == 16, S(stream), true, false, pre);
+    if (c.c_out == 1 && c.k == 1 && c.stride == 1 && c.pad == 0 && c.groups == 1 && !c.transposed && c.n_in == c.n_out && p.chunk <= 64) {
+        // a Linear down to one channel: the three gradients in one launch (train_ops.h train_lin1_bwd_kernel); its partial rows are
+        // [weight partials (c_in) | bias partial]
+        const long ps = c.c_in + 1;
+        const bool al16 = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(w)) & 15) == 0;
+        float* pbias = dbias ? part + c.c_in : nullptr;
+#define ESMI_LIN1(LPR) ESMI_LAUNCH(train_lin1_bwd4_kernel<LPR>, dim3((unsigned)p.chunks), dim3(64), 0, S(stream), x, dy, w, p.rows, dx, part, pbias, ps)
+        if (al16 && p.chunk == 32 && c.c_in == 16) ESMI_LIN1(4);
+        else if (al16 && p.chunk == 32 && c.c_in == 32) ESMI_LIN1(8);
+        else if (al16 && p.chunk == 32 && c.c_in == 64) ESMI_LIN1(16);
+        else if (al16 && p.chunk == 32 && c.c_in == 128) ESMI_LIN1(32);
+        else if (al16 && p.chunk == 32 && c.c_in == 256) ESMI_LIN1(64);
+        else
+            ESMI_LAUNCH(train_lin1_bwd_kernel, dim3((unsigned)p.chunks), dim3(64), 0, S(stream), x, dy, w, p.rows, c.c_in, dx, part, pbias, ps, p.chunk);
+#undef ESMI_LIN1
+        if (int rc = launch_status()) return rc;
+        return reduce_or_defer(defer, part, dbias ? ps : (long)c.c_in, ps, p.chunks, dw, c.c_in, dbias, S(stream));
+    }
+    // everything else: the two gradients as the stand-alone entry points run them
+    if (int rc = esmi_train_conv_dgrad_f32(d, dy, w, dx, gemm_bytes ? wc.wt : nullptr, gemm_bytes, stream)) return rc;
+    return conv_wgrad(c, p, x, dy, dw, dbias, part, nullptr, defer, S(stream));
 }
 int esmi_train_layernorm_fwd_f32(const float* x, const float* g, const float* b, int64_t rows, int C, float* y, float* mean,
                                  float* rstd, const float* res, float* xsum, const uint8_t* rowmask, int relu_out, esmi_stream_t stream) {

@@ -10,7 +10,9 @@ as the TAPE only (which operator's backward runs when, and the accumulation of g
 The operators take the model's own `nn.Parameter`s in checkpoint layout, so `Phoneme2Mel.state_dict()` after N steps is a
 reference-compatible checkpoint and the inference path (`networks.py`) picks the updated weights up through its pack cache.
 """
+import contextlib
 import ctypes as C
+import dataclasses
 
 import torch
 
@@ -19,9 +21,6 @@ from .networks import _ptr, _mask_u8
 
 ACT_RELU, ACT_GELU, ACT_TANH = 1, 2, 3
 USE_MATRIX_PIPE = True    # dense convolutions (forward and data gradient) through the implicit-GEMM kernels; False: plain fp32 kernels
-USE_MATRIX_PIPE_DGRAD = True   # (development) False: only the forward GEMMs on the matrix pipe
-PRECISION = 32            # 16: the reference's `--precision 16` -- the dense GEMMs (forward, data gradient) round their operands to
-#                           binary16 (one MFMA product instead of three); set by TrainStep(precision=16) around its step
 
 
 def _rt(t):
@@ -32,23 +31,42 @@ def _new(shape, like, dtype=torch.float32):
     return torch.empty(shape, dtype=dtype, device=like.device)
 
 
-_REDUCE_Q = None          # (esmi_reduce_queue, [workspaces kept alive]) while TrainStep's backward runs: the second stages of the chunked
-#                           parameter-gradient reductions are queued and run as ONE launch before the optimizer (62 launches otherwise)
+@dataclasses.dataclass
+class _Step:
+    """What a running `TrainStep` tells the operators; `TrainStep._fwd_bwd` turns the last three on as the step gets there."""
+    precision: int                  # 16: the reference's `--precision 16` -- the dense GEMMs (forward, data gradient) round their operands to
+    #                                 binary16 (one MFMA product instead of three)
+    loss_seed: object               # what the backward is seeded with: False = 1, else the device scalar (the loss scale) -- the loss kernel
+    #                                 writes its gradients already multiplied by it and `_Loss.backward` passes them on as they are
+    packed_valid: bool = False      # once the step's pack launch has been enqueued: `param._esmi_packed` holds this step's GEMM copies
+    direct_grads: bool = False      # only around the backward: ONE backward per zeroed buffer, so overwriting == accumulating
+    reduce_queue: object = None     # only around the backward: (esmi_reduce_queue, [workspaces kept alive]) -- the second stages of the chunked
+    #                                 parameter-gradient reductions are queued and run as ONE launch before the optimizer (62 launches otherwise)
+
+
+_STEP = None              # the `_Step` of the `TrainStep` whose step is running; None outside one: precision 32, fresh gradient tensors, nothing
+#                           deferred, no packed copies, `_Loss.backward` scaling by the incoming seed.  A plain module variable on purpose, not a
+#                           thread-local: on the GPU `total.backward()` runs the operators' `backward` on autograd's device thread
+
+
+@contextlib.contextmanager
+def _step_context(precision, loss_seed):
+    global _STEP
+    outer, _STEP = _STEP, _Step(precision, loss_seed)
+    try:
+        yield _STEP
+    finally:
+        _STEP = outer
 
 
 def _defer(ws, *direct):
     """The queue to hand to an operator's backward, or None: only gradients that go straight into the flat buffer may be late
     (autograd would read a returned tensor at once); the partial sums in `ws` must outlive the flush."""
-    if _REDUCE_Q is None or not all(direct):
+    q = _STEP.reduce_queue if _STEP is not None else None
+    if q is None or not all(direct):
         return None
-    _REDUCE_Q[1].append(ws)
-    return C.byref(_REDUCE_Q[0])
-
-
-_DIRECT_GRADS = False     # True only while TrainStep._body runs: ONE backward per zeroed buffer, so overwriting == accumulating
-_LOSS_SEED = None         # while TrainStep's step runs: False = the backward is seeded with 1, or the device scalar it is seeded with (the loss
-#                           scale): the loss kernel writes its gradients already multiplied by it and `_Loss.backward` passes them on as they are
-_PACKED_VALID = False     # True only while TrainStep._fwd_bwd runs, after its pack launch: `param._esmi_packed` holds this step's GEMM copies
+    q[1].append(ws)
+    return C.byref(q[0])
 
 
 def _grad_buffer(param):
@@ -58,9 +76,59 @@ def _grad_buffer(param):
     (gradient accumulation through the wrapper's public route) adds up as torch semantics require.  The direct write is valid
     inside `TrainStep` because the buffer is zeroed per step and every parameter of this model feeds exactly one operator."""
     view = getattr(param, "_esmi_grad_view", None)
-    if _DIRECT_GRADS and view is not None and param.grad is not None and param.grad.data_ptr() == view.data_ptr():   # still the buffer autograd would add to
+    direct = _STEP is not None and _STEP.direct_grads
+    if direct and view is not None and param.grad is not None and param.grad.data_ptr() == view.data_ptr():   # still the buffer autograd would add to
         return view, True
     return torch.empty_like(param), False
+
+
+# --------------------------------------------------------------------------- what _Conv, _LayerNorm and _ConvLN are made of
+def _conv_desc(lib, x, w0, w, n_out, stride, pad, groups, transposed, act):
+    """-> (d, ws, nws): the `ConvDesc` of a convolution of x (B, n_in, Cin) by the Parameter `w0` (`w`: contiguous) and what its forward
+    GEMM copies the weight into -- this step's packed copies (made by TrainStep's one pack launch) in `d`, else the workspace `ws`."""
+    B, n_in, c_in = x.shape
+    w3 = w if w.dim() == 3 else w.unsqueeze(-1)
+    c_out, k = (w3.shape[1] if transposed else w3.shape[0]), w3.shape[2]
+    precision = 16 if (_STEP is not None and _STEP.precision == 16) else 0
+    d = _lib.ConvDesc(B, n_in, c_in, n_out, c_out, k, stride, pad, groups, 1 if transposed else 0, precision, act)
+    packed = getattr(w0, "_esmi_packed", None) if (USE_MATRIX_PIPE and _STEP is not None and _STEP.packed_valid) else None
+    if packed is not None:
+        d.packed_fwd, d.packed_grad = _ptr(packed[0]), _ptr(packed[1])
+    nws = lib.esmi_train_conv_workspace_bytes(C.byref(d)) if (USE_MATRIX_PIPE and packed is None) else 0
+    return d, (_new((nws,), x, torch.uint8) if nws else None), nws
+
+
+def _conv_backward(lib, st, d, x, w, dy, w0, b0):
+    """The convolution's two gradients -> (dx, dw, db); dw / db are None where the gradient went straight into the flat buffer of the
+    Parameter (`w0`, `b0`: the Parameter objects themselves)."""
+    dx = torch.empty_like(x)
+    dw, w_direct = _grad_buffer(w0)
+    db, b_direct = _grad_buffer(b0) if b0 is not None else (None, True)
+    if USE_MATRIX_PIPE:
+        # one call for both gradients: the weight-gradient pass leaves max|dy| behind for the data-gradient GEMM's operand scale
+        nws = lib.esmi_train_conv_bwd_workspace_bytes(C.byref(d))
+        ws = _new((nws,), w, torch.uint8)
+        lib.esmi_train_conv_bwd_f32(C.byref(d), _ptr(x), _ptr(dy), _ptr(w), _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), nws,
+                                    _defer(ws, w_direct, b_direct), st)
+    else:
+        lib.esmi_train_conv_dgrad_f32(C.byref(d), _ptr(dy), _ptr(w), _ptr(dx), None, 0, st)
+        nws = lib.esmi_train_conv_wgrad_workspace_bytes(C.byref(d))
+        ws = _new((nws,), w, torch.uint8)
+        lib.esmi_train_conv_wgrad_f32(C.byref(d), _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), nws, st)
+    return dx, (None if w_direct else dw), (None if b_direct else db)
+
+
+def _layer_norm_backward(lib, st, x, g, mean, rstd, mask, y_relu, dy, in_act, g0, b0):
+    """The norm's backward (with the row mask, the norm's ReLU and the activation `in_act` in front of it) -> (dx, dg, db); dg / db are
+    None where the gradient went straight into the flat buffer of the Parameter (`g0`, `b0`)."""
+    rows, Cc = x.numel() // x.shape[-1], x.shape[-1]
+    dx = torch.empty_like(x)
+    (dg, g_direct), (db, b_direct) = _grad_buffer(g0), _grad_buffer(b0)
+    nws = lib.esmi_train_layernorm_bwd_workspace_bytes(rows, Cc)
+    ws = _new((nws,), x, torch.uint8)
+    lib.esmi_train_layernorm_bwd_f32(_ptr(x), _ptr(g), _ptr(mean), _ptr(rstd), _ptr(dy), rows, Cc, _ptr(dx), _ptr(dg), _ptr(db),
+                                     _ptr(ws), nws, _defer(ws, g_direct, b_direct), _ptr(mask), in_act, _ptr(y_relu), st)
+    return dx, (None if g_direct else dg), (None if b_direct else db)
 
 
 # --------------------------------------------------------------------------- operators (autograd = the tape)
@@ -77,16 +145,8 @@ class _Conv(torch.autograd.Function):
         w0 = w
         x, w = x.contiguous(), w.contiguous()
         lib, st = _rt(x)
-        B, n_in, c_in = x.shape
-        w3 = w if w.dim() == 3 else w.unsqueeze(-1)
-        c_out, k = (w3.shape[1] if transposed else w3.shape[0]), w3.shape[2]
-        d = _lib.ConvDesc(B, n_in, c_in, n_out, c_out, k, stride, pad, groups, 1 if transposed else 0, 16 if PRECISION == 16 else 0, act)
-        packed = getattr(w0, "_esmi_packed", None) if (_PACKED_VALID and USE_MATRIX_PIPE) else None
-        if packed is not None:                  # this step's GEMM copies, made by TrainStep's one pack launch
-            d.packed_fwd, d.packed_grad = _ptr(packed[0]), (_ptr(packed[1]) if USE_MATRIX_PIPE_DGRAD else None)
-        y = _new((B, n_out, c_out), x)
-        nws = lib.esmi_train_conv_workspace_bytes(C.byref(d)) if (USE_MATRIX_PIPE and packed is None) else 0
-        ws = _new((nws,), x, torch.uint8) if nws else None
+        d, ws, nws = _conv_desc(lib, x, w0, w, n_out, stride, pad, groups, transposed, act)
+        y = _new((d.B, n_out, d.c_out), x)
         lib.esmi_train_conv_fwd_f32(C.byref(d), _ptr(x), _ptr(w), _ptr(b), _ptr(y), _ptr(ws), nws, st)
         ctx.save_for_backward(x, w, *((y,) if ctx.act_here else ()))
         ctx.d, ctx.params = d, (w0, b)          # the Parameter objects themselves: their flat gradient views are the outputs
@@ -97,27 +157,11 @@ class _Conv(torch.autograd.Function):
         x, w = ctx.saved_tensors[:2]
         dy = dy.contiguous()
         lib, st = _rt(dy)
-        d = ctx.d
         if ctx.act_here:
             da = torch.empty_like(dy)
-            lib.esmi_train_act_bwd_f32(_ptr(ctx.saved_tensors[2]), _ptr(dy), dy.numel(), d.act, _ptr(da), st)
+            lib.esmi_train_act_bwd_f32(_ptr(ctx.saved_tensors[2]), _ptr(dy), dy.numel(), ctx.d.act, _ptr(da), st)
             dy = da
-        dx = torch.empty_like(x)
-        w0, b0 = ctx.params
-        dw, w_direct = _grad_buffer(w0)
-        db, b_direct = _grad_buffer(b0) if b0 is not None else (None, True)
-        if USE_MATRIX_PIPE and USE_MATRIX_PIPE_DGRAD:
-            # one call for both gradients: the weight-gradient pass leaves max|dy| behind for the data-gradient GEMM's operand scale
-            nws = lib.esmi_train_conv_bwd_workspace_bytes(C.byref(d))
-            ws = _new((nws,), w, torch.uint8)
-            lib.esmi_train_conv_bwd_f32(C.byref(d), _ptr(x), _ptr(dy), _ptr(w), _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), nws,
-                                        _defer(ws, w_direct, b_direct), st)
-        else:
-            lib.esmi_train_conv_dgrad_f32(C.byref(d), _ptr(dy), _ptr(w), _ptr(dx), None, 0, st)
-            nws = lib.esmi_train_conv_wgrad_workspace_bytes(C.byref(d))
-            ws = _new((nws,), w, torch.uint8)
-            lib.esmi_train_conv_wgrad_f32(C.byref(d), _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), nws, st)
-        return dx, (None if w_direct else dw), (None if b_direct else db), None, None, None, None, None, None, None
+        return _conv_backward(lib, st, ctx.d, x, w, dy, *ctx.params) + (None,) * 7
 
 
 class _LayerNorm(torch.autograd.Function):
@@ -145,17 +189,10 @@ class _LayerNorm(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        x, g, mean, rstd, mask, y_relu = ctx.saved_tensors
         dy = dy.contiguous()
         lib, st = _rt(dy)
-        rows, Cc = x.numel() // x.shape[-1], x.shape[-1]
-        dx = torch.empty_like(x)
-        (dg, g_direct), (db, b_direct) = _grad_buffer(ctx.params[0]), _grad_buffer(ctx.params[1])
-        nws = lib.esmi_train_layernorm_bwd_workspace_bytes(rows, Cc)
-        ws = _new((nws,), x, torch.uint8)
-        lib.esmi_train_layernorm_bwd_f32(_ptr(x), _ptr(g), _ptr(mean), _ptr(rstd), _ptr(dy), rows, Cc, _ptr(dx), _ptr(dg), _ptr(db),
-                                         _ptr(ws), nws, _defer(ws, g_direct, b_direct), _ptr(mask), ctx.in_act, _ptr(y_relu), st)
-        return dx, (None if g_direct else dg), (None if b_direct else db), (dx if ctx.has_res else None), None, None, None
+        dx, dg, db = _layer_norm_backward(lib, st, *ctx.saved_tensors, dy, ctx.in_act, *ctx.params)
+        return dx, dg, db, (dx if ctx.has_res else None), None, None, None
 
 
 class _ConvLN(torch.autograd.Function):
@@ -171,17 +208,9 @@ class _ConvLN(torch.autograd.Function):
         w0 = w
         x, w = x.contiguous(), w.contiguous()
         lib, st = _rt(x)
-        B, n, c_in = x.shape
-        w3 = w if w.dim() == 3 else w.unsqueeze(-1)
-        c_out, k = w3.shape[0], w3.shape[2]
-        d = _lib.ConvDesc(B, n, c_in, n, c_out, k, 1, pad, groups, 0, 16 if PRECISION == 16 else 0, act)
-        packed = getattr(w0, "_esmi_packed", None) if (_PACKED_VALID and USE_MATRIX_PIPE) else None
-        if packed is not None:
-            d.packed_fwd, d.packed_grad = _ptr(packed[0]), (_ptr(packed[1]) if USE_MATRIX_PIPE_DGRAD else None)
-        rows = B * n
-        y_pre, y, mean, rstd = _new((B, n, c_out), x), _new((B, n, c_out), x), _new((rows,), x), _new((rows,), x)
-        nws = lib.esmi_train_conv_workspace_bytes(C.byref(d)) if (USE_MATRIX_PIPE and packed is None) else 0
-        ws = _new((nws,), x, torch.uint8) if nws else None
+        d, ws, nws = _conv_desc(lib, x, w0, w, x.shape[1], 1, pad, groups, False, act)
+        rows, c_out = d.B * d.n_out, d.c_out
+        y_pre, y, mean, rstd = _new((d.B, d.n_out, c_out), x), _new((d.B, d.n_out, c_out), x), _new((rows,), x), _new((rows,), x)
         if res is not None:
             res = res.contiguous()
         fused = False
@@ -198,38 +227,18 @@ class _ConvLN(torch.autograd.Function):
             lib.esmi_train_layernorm_fwd_f32(_ptr(tmp), _ptr(g), _ptr(beta), rows, c_out, _ptr(y), _ptr(mean), _ptr(rstd),
                                              _ptr(res), _ptr(y_pre) if res is not None else None, _ptr(mask), 1 if relu_out else 0, st)
         ctx.save_for_backward(x, w, y_pre, g, mean, rstd, mask, y if relu_out else None)
-        ctx.d, ctx.params, ctx.has_res, ctx.act = d, (w0, b, g, beta), res is not None, act
+        ctx.d, ctx.params, ctx.has_res = d, (w0, b, g, beta), res is not None
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, w, y_pre, g, mean, rstd, mask, y_relu = ctx.saved_tensors
+        x, w, *norm_saved = ctx.saved_tensors
         dy = dy.contiguous()
         lib, st = _rt(dy)
-        d = ctx.d
-        rows, Cc = y_pre.numel() // y_pre.shape[-1], y_pre.shape[-1]
         w0, b0, g0, beta0 = ctx.params
-        dpre = torch.empty_like(y_pre)
-        (dg, g_direct), (dbt, bt_direct) = _grad_buffer(g0), _grad_buffer(beta0)
-        nws = lib.esmi_train_layernorm_bwd_workspace_bytes(rows, Cc)
-        ws = _new((nws,), x, torch.uint8)
-        lib.esmi_train_layernorm_bwd_f32(_ptr(y_pre), _ptr(g), _ptr(mean), _ptr(rstd), _ptr(dy), rows, Cc, _ptr(dpre), _ptr(dg), _ptr(dbt),
-                                         _ptr(ws), nws, _defer(ws, g_direct, bt_direct), _ptr(mask), ctx.act, _ptr(y_relu), st)
-        dx = torch.empty_like(x)
-        dw, w_direct = _grad_buffer(w0)
-        db, b_direct = _grad_buffer(b0) if b0 is not None else (None, True)
-        if USE_MATRIX_PIPE and USE_MATRIX_PIPE_DGRAD:
-            nws = lib.esmi_train_conv_bwd_workspace_bytes(C.byref(d))
-            ws = _new((nws,), w, torch.uint8)
-            lib.esmi_train_conv_bwd_f32(C.byref(d), _ptr(x), _ptr(dpre), _ptr(w), _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), nws,
-                                        _defer(ws, w_direct, b_direct), st)
-        else:
-            lib.esmi_train_conv_dgrad_f32(C.byref(d), _ptr(dpre), _ptr(w), _ptr(dx), None, 0, st)
-            nws = lib.esmi_train_conv_wgrad_workspace_bytes(C.byref(d))
-            ws = _new((nws,), w, torch.uint8)
-            lib.esmi_train_conv_wgrad_f32(C.byref(d), _ptr(x), _ptr(dpre), _ptr(dw), _ptr(db), _ptr(ws), nws, st)
-        return (dx, (None if w_direct else dw), (None if b_direct else db), None, None, None, (None if g_direct else dg),
-                (None if bt_direct else dbt), (dpre if ctx.has_res else None), None, None)
+        dpre, dg, dbeta = _layer_norm_backward(lib, st, *norm_saved, dy, ctx.d.act, g0, beta0)
+        dx, dw, db = _conv_backward(lib, st, ctx.d, x, w, dpre, w0, b0)
+        return dx, dw, db, None, None, None, dg, dbeta, (dpre if ctx.has_res else None), None, None
 
 
 class _Act(torch.autograd.Function):
@@ -411,7 +420,7 @@ class _Loss(torch.autograd.Function):
         out = _new((5,), mel_pred)
         grads = [torch.empty_like(t) for t in (mel_pred, pitch_pred, energy_pred, dur_pred)]
         scratch = _new((1536,), mel_pred)          # ESMI_TRAIN_LOSS_SCRATCH_FLOATS; held until the call has been enqueued
-        seed = _LOSS_SEED                          # None: unknown here (scaled in backward); False: 1; else the device scalar
+        seed = _STEP.loss_seed if _STEP is not None else None      # None: unknown here (scaled in backward); False: 1; else the device scalar
         a = _lib.TrainLossArgs(_ptr(mel_pred), _ptr(mel), _ptr(pitch_pred), _ptr(pitch), _ptr(energy_pred), _ptr(energy),
                                _ptr(dur_pred), _ptr(dur), _ptr(mel_mask), _ptr(ph_mask), B, T, L, nm, _ptr(out),
                                *[_ptr(g) for g in grads], _ptr(scratch), _ptr(seed) if torch.is_tensor(seed) else None)
@@ -599,21 +608,20 @@ class FlatParams:
     def __init__(self, net):
         named = [(k, p) for k, p in net.named_parameters() if p.requires_grad and not k.startswith(_UNREACHED)]
         self.names = [k for k, _ in named]
-        pad4 = lambda k: (k + 3) & ~3                                     # noqa: E731  every tensor starts 16-byte aligned
-        n = sum(pad4(p.numel()) for _, p in named)
+        self.params = [p for _, p in named]
+        self.slices, n = [], 0                      # each parameter's elements in the flat buffers
+        for p in self.params:
+            self.slices.append(slice(n, n + p.numel()))
+            n = (n + p.numel() + 3) & ~3            # every tensor starts 16-byte aligned
         dev = named[0][1].device
         self.data = torch.zeros(n, dtype=torch.float32, device=dev)          # (pad elements stay 0 under AdamW: g = 0, p = 0)
         self.grad = torch.zeros(n, dtype=torch.float32, device=dev)
         self.m, self.v = torch.zeros_like(self.data), torch.zeros_like(self.data)
-        off = 0
-        for _, p in named:
-            k = p.numel()
-            self.data[off:off + k].copy_(p.detach().reshape(-1))
-            p.data = self.data[off:off + k].view(p.shape)
-            p.grad = self.grad[off:off + k].view(p.shape)
+        for p, sl in zip(self.params, self.slices):
+            self.data[sl].copy_(p.detach().reshape(-1))
+            p.data = self.data[sl].view(p.shape)
+            p.grad = self.grad[sl].view(p.shape)
             p._esmi_grad_view = p.grad              # operators' backward passes write here directly (see _grad_buffer)
-            off += pad4(k)
-        self.params = [p for _, p in named]
 
     def zero_grad(self):
         self.grad.zero_()
@@ -628,8 +636,8 @@ class TrainStep:
     graph=True captures the step into one hipGraph the first time a batch SHAPE is seen and replays it for every later batch of
     that shape (inputs are copied into the graph's static buffers; step count, learning rate and the loss scaler live in device
     memory): the whole step on one GPU, everything up to the gradient all-reduce when data-parallel (the collective and the
-    optimizer launch then follow eagerly).  With ~330 launches per step the eager step is bound by the host's dispatch (5.6 ms at
-    B = 128); the replay runs at the kernels' own pace (4.9 ms)."""
+    optimizer launch then follow eagerly).  The eager step is bound by the host's dispatch of its ~180-220 launches (pinned row by row in
+    tests/test_train_dispatch.py); the replay runs at the kernels' own pace (both are `bench.py`'s `train_step` leg)."""
 
     def __init__(self, net, lr=1e-3, weight_decay=1e-6, betas=(0.9, 0.999), eps=1e-8, group=None, world_size=1, graph=False,
                  precision=32, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
@@ -653,7 +661,8 @@ class TrainStep:
         self._graphs = {}
         self._one = torch.ones(1, dtype=torch.float32, device=dev)
         self._build_pack_list()
-        if self.graph or precision == 16:
+        self._on_device = self.graph or precision == 16     # the optimizer reads step count and learning rate from device memory
+        if self._on_device:
             self._step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
             self._lr_dev = torch.full((8,), lr, dtype=torch.float32, device=dev)   # ESMI_TRAIN_ADAMW_HYPER_FLOATS: [0] = lr
 
@@ -701,14 +710,12 @@ class TrainStep:
         no state, as in torch."""
         f = self.flat
         index = {id(p): j for j, p in enumerate(self.net.parameters())}
-        state, off = {}, 0
+        state = {}
         t_now = self.t                          # (precision 16: a device read -- once, not per parameter)
-        for p in f.params:
-            k = p.numel()
+        for p, sl in zip(f.params, f.slices):
             if t_now > 0:
-                state[index[id(p)]] = {"step": torch.tensor(float(t_now)), "exp_avg": f.m[off:off + k].view(p.shape).clone(),
-                                       "exp_avg_sq": f.v[off:off + k].view(p.shape).clone()}
-            off += (k + 3) & ~3
+                state[index[id(p)]] = {"step": torch.tensor(float(t_now)), "exp_avg": f.m[sl].view(p.shape).clone(),
+                                       "exp_avg_sq": f.v[sl].view(p.shape).clone()}
         group = {"lr": self.lr, "initial_lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "decoupled_weight_decay": True, "params": list(range(len(index)))}
@@ -751,15 +758,13 @@ class TrainStep:
             raise RuntimeError("optimizer state was saved for a different parameter list")
         f.m.zero_()
         f.v.zero_()
-        steps, off = set(), 0
-        for p in f.params:
-            k = p.numel()
+        steps = set()
+        for p, sl in zip(f.params, f.slices):
             st = o["state"].get(index[id(p)])
             if st is not None:
-                f.m[off:off + k].copy_(st["exp_avg"].reshape(-1))
-                f.v[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
+                f.m[sl].copy_(st["exp_avg"].reshape(-1))
+                f.v[sl].copy_(st["exp_avg_sq"].reshape(-1))
                 steps.add(int(st["step"]))
-            off += (k + 3) & ~3
         if len(steps) > 1:
             raise RuntimeError(f"per-parameter step counts differ: {sorted(steps)}")
         self.t = steps.pop() if steps else 0
@@ -819,62 +824,50 @@ class TrainStep:
     def _fwd_bwd(self, x, y):
         """Forward, loss, backward, and the one launch that finishes every parameter gradient: everything up to the exchange.
         Capturable as a hipGraph (no host reads, no collectives)."""
-        global _DIRECT_GRADS, PRECISION, _REDUCE_Q, _PACKED_VALID, _LOSS_SEED
         f = self.flat
         f.zero_grad()
         rq = (_lib.ReduceQueue(), [])
         amp = self.precision == 16
-        old_precision, PRECISION = PRECISION, self.precision
         lib0, st0 = _rt(f.data)
-        try:
+        with _step_context(self.precision, self._scaler[:1] if amp else False) as now:
             if USE_MATRIX_PIPE and self._pack_n:   # every operator of this step reads these copies of the current weights
                 lib0.esmi_train_pack_weights_f32(self._pack_descs, self._pack_w, self._pack_n, st0)
-                _PACKED_VALID = True
-            _LOSS_SEED = self._scaler[:1] if amp else False
+                now.packed_valid = True
             parts, total = training_loss(self.net, x, y)
-            _DIRECT_GRADS = True                   # one backward on a zeroed buffer: operators write parameter gradients in place
-            _REDUCE_Q = rq
-            if amp:
-                total.backward(gradient=self._scaler[0].reshape(total.shape))     # GradScaler.scale(loss).backward(): the seed is the device-side scale
-            else:
-                total.backward(gradient=self._one.reshape(total.shape))
-        finally:
-            _DIRECT_GRADS = False
-            _REDUCE_Q = None
-            _PACKED_VALID = False
-            _LOSS_SEED = None
-            PRECISION = old_precision
+            # one backward on a zeroed buffer: operators write parameter gradients in place and queue their reductions' second stages
+            now.direct_grads, now.reduce_queue = True, rq
+            seed = self._scaler[0] if amp else self._one     # GradScaler.scale(loss).backward(): the seed is the device-side scale
+            total.backward(gradient=seed.reshape(total.shape))
         lib0.esmi_train_reduce_flush_f32(C.byref(rq[0]), st0)      # every queued parameter-gradient reduction in one launch
         rq[1].clear()
         return loss_vector(parts, total)
 
-    def _optimize(self, lr, on_device):
-        """The exchange (one all-reduce of the flat gradient buffer when data-parallel) and the optimizer launch.  `on_device`: step
-        count / learning rate (/ the loss scaler's state) are read from device memory (graph replay, precision 16)."""
+    def _optimize(self, lr):
+        """The exchange (one all-reduce of the flat gradient buffer when data-parallel) and the optimizer launch, which reads step
+        count / learning rate (/ the loss scaler's state) from device memory under graph replay and precision 16."""
         f = self.flat
         if self.world > 1:
             import torch.distributed as dist
             dist.all_reduce(f.grad, op=dist.ReduceOp.SUM, group=self.group)
             f.grad.div_(self.world)                # DDP averages (train.py:66-70 runs Lightning's default DDP strategy)
         lib, st = _rt(f.data)
-        if self.precision == 16:
+        amp = self.precision == 16
+        if amp:
             # GradScaler.step + .update on the device: max|g| of the (still scaled) gradients -- absmax's integer max orders inf and
             # nan above every finite magnitude -- decides inside the optimizer launch whether the update runs (on g / scale) or is
             # skipped with the scale backed off; nothing is read back.
             lib.esmi_absmax_f32(_ptr(f.grad), f.grad.numel(), _ptr(self._absmax), st)
+        if self._on_device:
+            absmax, scaler = (_ptr(self._absmax), _ptr(self._scaler)) if amp else (None, None)
             lib.esmi_train_adamw_graph_f32(_ptr(f.data), _ptr(f.grad), _ptr(f.m), _ptr(f.v), f.data.numel(), _ptr(self._lr_dev),
-                                           self.betas[0], self.betas[1], self.eps, self.wd, _ptr(self._step_dev), _ptr(self._absmax),
-                                           _ptr(self._scaler), st)
-        elif on_device:
-            lib.esmi_train_adamw_graph_f32(_ptr(f.data), _ptr(f.grad), _ptr(f.m), _ptr(f.v), f.data.numel(), _ptr(self._lr_dev),
-                                           self.betas[0], self.betas[1], self.eps, self.wd, _ptr(self._step_dev), None, None, st)
+                                           self.betas[0], self.betas[1], self.eps, self.wd, _ptr(self._step_dev), absmax, scaler, st)
         else:
             lib.esmi_train_adamw_f32(_ptr(f.data), _ptr(f.grad), _ptr(f.m), _ptr(f.v), f.data.numel(), lr, self.betas[0],
                                      self.betas[1], self.eps, self.wd, self.t, 1.0, st)
 
-    def _body(self, x, y, lr, graph):
+    def _body(self, x, y, lr):
         losses = self._fwd_bwd(x, y)
-        self._optimize(lr, graph)
+        self._optimize(lr)
         return losses
 
     def step(self, x, y, lr=None):
@@ -884,15 +877,13 @@ class TrainStep:
         if self.precision != 16:
             self._t += 1                           # (precision 16 counts on the device: a skipped step does not advance it)
         lr = self.lr if lr is None else lr
-        on_device = self.graph or self.precision == 16
-        if on_device:
+        if self._on_device:
             self._lr_dev[:1].fill_(lr)
         if not self.graph:
-            out = self._body(x, y, lr, False)
+            out = self._body(x, y, lr)
             self._invalidate_packed()
             return out
         whole = self.world == 1                    # the collective stays outside a graph
-        captured = self._body if whole else (lambda sx, sy, lr_, g_: self._fwd_bwd(sx, sy))
         key = tuple((k, tuple(v.shape)) for k, v in sorted({**x, **{"y." + k: v for k, v in y.items()}}.items()) if torch.is_tensor(v))
         ent = self._graphs.get(key)
         if ent is None:
@@ -901,11 +892,11 @@ class TrainStep:
             side = torch.cuda.Stream(device=self.flat.data.device)          # one eager step on a side stream warms the allocator
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                out = self._body(sx, sy, lr, True)
+                out = self._body(sx, sy, lr)
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                static_out = captured(sx, sy, lr, True)
+                static_out = self._body(sx, sy, lr) if whole else self._fwd_bwd(sx, sy)
             self._graphs[key] = (g, sx, sy, static_out)
             self._invalidate_packed()
             return out.clone()                     # (the capture itself does not execute: this batch's step ran eagerly above)
@@ -917,7 +908,7 @@ class TrainStep:
             sy[k].copy_(v)
         g.replay()
         if not whole:
-            self._optimize(lr, True)
+            self._optimize(lr)
         self._invalidate_packed()
         return static_out.clone()
 
