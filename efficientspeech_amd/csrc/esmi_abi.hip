@@ -2,7 +2,7 @@
 // Built by `hipcc --offload-arch=gfx950` into libesmi.so (product) and, unchanged, by the host
 // clang++ with -DESMI_WAVESIM into libesmi_sim.so (CPU wave simulator used only by tests).
 #include "launch.h"
-#include "mel_decoder.h"   // esmi_decoder_shape helpers used by the one-call forward
+#include "dec_layout.h"   // the decoder's build knob (esmi_build_config) and host-side helpers
 
 using namespace esmi;
 ESMI_TU_RANGE_SETTER(abi)

@@ -6,25 +6,35 @@
 //   n_blocks x { x = skip; block_depth x [ x = LN(tanh(Conv1x1(dwConv_k(x)))) ]; skip = LN_s(x + skip) }
 //   mel  = Linear(dx2, n_mel)(skip)
 //
-// One 512-thread workgroup (8 waves) owns a 128-frame window of one utterance: TL = 128 - 2*halo
-// frames are kept, halo = (k/2)*n_blocks*block_depth frames per side are recomputed so that no
-// activation ever leaves the CU.  Activations live in ONE LDS tile [132][DX2+4] fp32 (two zero rows
-// per side = the depthwise conv's in-window padding; +4 floats/row keep the 16-byte row-fragment
-// reads bank-conflict free).
+// One 512-thread workgroup (8 waves) owns a 128-row tile of one utterance; activations live in ONE LDS tile [132][DX2+4] fp32 (two
+// zero rows per side = the depthwise conv's in-window padding; +4 floats/row keep the 16-byte row-fragment reads bank-conflict free)
+// and never leave the CU.  The first stage (Linear + Tanh + LN) normally runs at PHONEME rate on the encoder side (`h0`); the kernel
+// then only gathers.  Two forms of one kernel:
+//  * dx2 = 128 (tiny), the WINDOW form: two workgroups per CU, every window its own workgroup with both halos recomputed -- 128 - 2*halo
+//    frames are kept, halo = (k/2)*n_blocks*block_depth; LayerNorm by row owners.
+//  * dx2 = 256 (small, base), the CHUNK WALK: one workgroup per CU walks a segment of an utterance chunk by chunk; each conv layer's
+//    k/2 rows in front of a chunk are carried from the previous chunk, the tile's frame base steps back at every block boundary (BLOCK
+//    SKEW: DecWalk, dec_layout.h) so that a chunk advances by 128 - block_depth*k/2 frames, and the LayerNorm runs ON THE K LOOP'S
+//    ACCUMULATORS (three barriers per layer instead of four).  Without a workspace it runs the window form.
 //
-// Weight-stationary GEMMs (ESMI_DEC_SPLIT: exact-fp32 MFMA, or fp32-accurate split products on the bf16 / f16 matrix pipe).  Wave w = (mh = w>>2, ns = w&3)
+// Weight-stationary GEMMs (ESMI_DEC_SPLIT: exact-fp32 MFMA, or fp32-accurate split products on the f16 matrix pipe).  Wave w = (mh = w>>2, ns = w&3)
 // owns rows [64mh, 64mh+64) x columns [ns*DX2/4, +DX2/4).  For each 128-channel K chunk it loads
 // its weight slice ONCE into registers (16 coalesced 16-byte loads per 32-column tile, from the
 // pre-packed blob) and streams the A fragments of its 64 rows from LDS: the K loop touches no
 // global memory.  (Round-1 ablation: with one wave owning 32 full rows, re-streaming the weights
 // from L2 for every 32 rows cost 150 us of a 675 us kernel.)
 //
-// Per conv layer, five short phases separated by workgroup barriers:
-//   1. depthwise k-tap conv IN PLACE on the tile (each thread: 4 channels x 8 or 16 rows, window in
-//      registers);  2. K loop (MFMA only + ds_read_b128);  3. bias + tanh, accumulators -> tile;
-//   4. LayerNorm by row-owner threads (16 threads = one DPP row per tile row, 4 rows per thread so that the gain / shift
-//      vectors are read once per 4 rows; the rows' values and the skip tensor in registers; block end: LN_s(x + skip));
+// Per conv layer, phases separated by workgroup barriers:
+//   1. depthwise k-tap conv IN PLACE on the tile (each thread: 4 channels x 8 or 16 rows, window in registers; the output already split
+//      into the K loop's two f16 operand planes);  2. K loop (MFMA only + ds_read_b128), then bias + tanh on the accumulators;
+//   3. dx2 = 128: accumulators -> tile, then LayerNorm by row-owner threads (16 threads = one DPP row per tile row, 4 rows per thread so
+//      that the gain / shift vectors are read once per 4 rows; the rows' values and the skip tensor in registers; block end:
+//      LN_s(x + skip)); dx2 = 256: row statistics through an LDS exchange, accumulators normalised in place and stored once;
 //      rows outside [0, L) are forced to 0.
+//
+// In this file: the phases that are free functions (the row owners' LayerNorm arithmetic, the operand-plane store, the clock stamp),
+// then the kernel.  The other phases are `[&]` lambdas or straight-line code inside the kernel: moving them changes the generated
+// code of a kernel that sits at its register limit (profiles/dec_refactor_isa.md lists what was tried).
 //
 // Fidelity notes (SURVEY.md §7 "hard parts"):
 //  * frames in [mel_len[b], L) are PADDING FRAMES: zero input rows, but computed like any other frame,
@@ -35,191 +45,24 @@
 #pragma once
 #include <type_traits>
 
-#include "esmi_dev.h"
-#include "small_kernels.h"
+#include "dec_layout.h"
 
-// Build knob: the contraction form (two libraries of one ABI are built from it, __graft_entry__.py)
-#ifndef ESMI_DEC_SPLIT      // contraction of the pointwise GEMMs (esmi_dev.h):
-#define ESMI_DEC_SPLIT 2    //   0: v_mfma_f32_32x32x2_f32 (exact fp32; the libesmi_fp32mfma.so build)
-#endif                      //   2: fp32 split into 2 f16 (weights pre-scaled by 2^8), 3 products on v_mfma_f32_32x32x16_f16
-#if ESMI_DEC_SPLIT != 0 && ESMI_DEC_SPLIT != 2
-#error "ESMI_DEC_SPLIT must be 0 (fp32 MFMA) or 2 (split f16x2)"
-#endif
 // Fixed choices (each the measured best on MI355X; the alternatives and their times are in HISTORY.md 3.1, not in the build):
 //  * dx2 = 128: 4 waves per SIMD (128 VGPRs, two workgroups per CU); weight slices of 4 k-steps (split build) / 8 (fp32 build) loaded then
 //    used, no hand-pipelined ring (a ring measured 169 -> 172 / 174 us: the neighbour workgroup already fills the L2 round trips);
 //  * dx2 = 256 (one workgroup per CU, nobody fills the gaps): the K loop's weight fragments run 2 steps ahead in a VGPR ring
 //    (small ES decoder 1774 -> 1687 us; depth 4 spills: 1736), the A fragments one item ahead; 8 waves per window (16: 2.43 vs 1.87 ms).
-constexpr int kDecWps128 = 4, kDecWeightRing256 = 2, kDecARing = 1;
-#ifndef ESMI_DEC_MEL_NT     // dx2 = 256: the chunk's mel rows leave as streaming (non-temporal) stores
-#define ESMI_DEC_MEL_NT 1
-#endif
-#ifndef ESMI_DEC_H0_NT      // dx2 = 256: the h0 row gather as streaming loads
-#define ESMI_DEC_H0_NT 1    // (base ES, B = 512: HBM traffic per launch 1051 MB with plain stores and loads, 576 MB with streaming mel stores,
-#endif                      //  541 MB with both, against 386 MB algorithmic: profiles/r06_probes/decoder256_traffic_ab.txt)
-#ifndef ESMI_DEC_CUM_LDS    // the utterance's duration scan is copied into LDS (one round trip) and the frame -> phoneme search runs there
-#define ESMI_DEC_CUM_LDS 1  // (0: a binary search in global memory, log2(T) dependent L2 round trips per chunk: profiles/r06_dec_budget.md)
-#endif
-#ifndef ESMI_DEC_LN_ACC     // dx2 = 256: LayerNorm on the K loop's accumulators -- per-(row, column slice) sums through a 1 KB-per-32-rows LDS exchange,
-#define ESMI_DEC_LN_ACC 1   // normalised in registers, stored once (0: tanh rows -> tile -> barrier -> row owners read, normalise, write back)
-#endif
-#define ESMI_DEC_TANH tanh_fast_f32
-#define ESMI_DEC_RSQRT rsqrt_fast_f32   // v_rsq_f32 (1 ulp)
-
+//  * dx2 = 256: the chunk's mel rows leave as streaming (non-temporal) stores and the h0 row gather runs as streaming loads (base ES,
+//    B = 512: HBM traffic per launch 1051 MB with plain stores and loads, 576 MB with streaming mel stores, 541 MB with both, against
+//    386 MB algorithmic: profiles/r06_probes/decoder256_traffic_ab.txt);
+//  * the utterance's duration scan is copied into LDS (one round trip) and the frame -> phoneme search runs there (a binary search in
+//    global memory is log2(T) dependent L2 round trips per chunk: profiles/r06_dec_budget.md); a scan row that does not fit the tile
+//    is searched in global memory;
+//  * dx2 = 256: LayerNorm on the K loop's accumulators -- per-(row, column slice) sums through a 1 KB-per-32-rows LDS exchange, normalised
+//    in registers, stored once (dx2 = 128: tanh rows -> tile -> barrier -> row owners read, normalise, write back).
 namespace esmi {
 
-constexpr int kDecRows = 128;     // frames per workgroup window
-constexpr int kDecPadRows = 2;    // zero rows above/below the window in LDS (>= k/2)
-constexpr int kDecThreads = 512;  // 8-wave windows (the dx2 = 128 kernel and the host-side launch default)
-constexpr int kMelCols = 96;      // n_mel <= 96 (three 32-column MFMA tiles)
-
-struct DecLayout {  // offsets in floats into the packed blob
-    long proj_w, proj_b, proj_g, proj_beta;
-    long layer0, layer_stride;                 // per conv layer
-    long l_dw, l_dwb, l_pw, l_pwb, l_g, l_b;   // relative to the layer base
-    long skip0;                                // per block: gain[dx2], bias[dx2]
-    long mel_w, mel_b;
-    long total;
-};
-
-inline DecLayout dec_layout(int d4, int dx2, int kd, int n_blocks, int block_depth) {
-    DecLayout L;
-    long o = 0;
-    constexpr long kWNum = 2;   // matrix storage in units of DX2*DX2/2 floats: two f16 planes or fp32 (the same bytes)
-    L.proj_w = o; o += (long)d4 * dx2 * kWNum / 2;
-    L.proj_b = o; o += dx2;                    // proj_b, proj_g, proj_beta contiguous
-    L.proj_g = o; o += dx2;
-    L.proj_beta = o; o += dx2;
-    L.l_dw = 0;                                // per layer: taps[kd][dx2], dw_b, pw_b, ln_g, ln_b contiguous ...
-    L.l_dwb = (long)kd * dx2;
-    L.l_pwb = L.l_dwb + dx2;
-    L.l_g = L.l_pwb + dx2;
-    L.l_b = L.l_g + dx2;
-    L.l_pw = L.l_b + dx2;                      // ... then the packed pointwise matrix
-    L.layer_stride = L.l_pw + (long)dx2 * dx2 * kWNum / 2;
-    L.layer0 = o; o += L.layer_stride * n_blocks * block_depth;
-    L.skip0 = o; o += 2L * dx2 * n_blocks;
-    L.mel_w = o; o += (long)dx2 * dx2 * kWNum / 2;   // packed like a dx2 x dx2 matrix, rows >= n_mel zero
-    L.mel_b = o; o += dx2;                     // zero padded
-    L.total = o;
-    return L;
-}
-
-// Weight-stationary B-fragment packing of a (N, K) row-major matrix, K a multiple of 128, for a
-// workgroup whose 4 column slices are WCOLS = 32*NTW wide:
-//   dst[(((((c*4 + ns)*NTW + ntw)*16 + kc)*64 + lane)*4 + s] =
-//       W[ns*WCOLS + 32*ntw + (lane&31)][128*c + 8*kc + 4*(lane>>5) + s]      (0 for rows >= N)
-static __global__ void pack_bslice_kernel(const float* __restrict__ src, float* __restrict__ dst, int N, int K, int NTW) {
-    const long n = (long)(K / 128) * 4 * NTW * 16 * 256;
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
-        const int s = (int)(e & 3);
-        const int lane = (int)((e >> 2) & 63);
-        long q = e >> 8;
-        const int kc = (int)(q & 15); q >>= 4;
-        const int ntw = (int)(q % NTW); q /= NTW;
-        const int ns = (int)(q & 3);
-        const int c = (int)(q >> 2);
-        const int row = ns * 32 * NTW + 32 * ntw + (lane & 31);
-        const int col = 128 * c + 8 * kc + 4 * (lane >> 5) + s;
-        dst[e] = row < N ? src[(long)row * K + col] : 0.0f;
-    }
-}
-
-// The same slices as two binary16 planes of 2^8 * W (round to nearest; esmi_dev.h) in the B layout of v_mfma_f32_32x32x16_f16:
-// per (chunk c, column slice ns, tile ntw, 16-channel step s, plane p) 64 lanes x 4 dwords,
-//   row = ns*32*NTW + 32*ntw + (lane&31),  k0 = 128*c + 16*s + 8*(lane>>5) + 2*w       (0 for rows >= N)
-//   dst[((((((c*4 + ns)*NTW + ntw)*8 + s)*2 + p)*64 + lane)*4 + w] = {plane_p(W[row][k0 + 1]), plane_p(W[row][k0])}
-static __global__ void pack_bslice2h_kernel(const float* __restrict__ src, unsigned* __restrict__ dst, int N, int K, int NTW) {
-    const long n = (long)(K / 128) * 4 * NTW * 8 * 2 * 256;
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
-        const int wd = (int)(e & 3);
-        const int lane = (int)((e >> 2) & 63);
-        long q = e >> 8;
-        const int pl = (int)(q & 1); q >>= 1;
-        const int st = (int)(q & 7); q >>= 3;
-        const int ntw = (int)(q % NTW); q /= NTW;
-        const int ns = (int)(q & 3);
-        const int c = (int)(q >> 2);
-        const int row = ns * 32 * NTW + 32 * ntw + (lane & 31);
-        const int k0 = 128 * c + 16 * st + 8 * (lane >> 5) + 2 * wd;
-        unsigned half[2];
-        for (int j = 0; j < 2; ++j) {
-            const float x = (row < N ? src[(long)row * K + k0 + j] : 0.0f) * kF16WScale;
-            const unsigned h1 = f32_to_f16_bits(x, false);
-            half[j] = pl == 0 ? h1 : f32_to_f16_bits(x - f16_bits_to_f32(h1), false);
-        }
-        dst[e] = half[0] | (half[1] << 16);
-    }
-}
-
-// The same layout as the kernel sees it: everything inside a conv layer is a compile-time offset (DX2, KD are template parameters), and
-// the few run-time offsets are 32-bit (the blob is a few MB).  The kernel used to take the 16 64-bit fields of DecLayout as arguments:
-// 32 SGPRs live across the layer loop, which is where the dx2 = 256 kernel's SGPR spills (48) and its uniform values in VGPRs came from.
-template <int DX2, int KD>
-struct DecLay {
-    static constexpr int l_dwb = KD * DX2, l_pwb = l_dwb + DX2, l_g = l_pwb + DX2, l_b = l_g + DX2, l_pw = l_b + DX2,
-                         layer_stride = l_pw + DX2 * DX2;
-    int proj_b, layer0, skip0, mel_w, mel_b, total;
-    __host__ __device__ DecLay(int d4, int n_blocks, int block_depth) {
-        proj_b = d4 * DX2;
-        layer0 = proj_b + 3 * DX2;
-        skip0 = layer0 + layer_stride * n_blocks * block_depth;
-        mel_w = skip0 + 2 * DX2 * n_blocks;
-        mel_b = mel_w + DX2 * DX2;
-        total = mel_b + DX2;
-    }
-    // (the host's dec_layout() is the one the packer writes by; the launcher checks that the two agree)
-    bool matches(const DecLayout& L) const {
-        return L.proj_w == 0 && L.proj_b == proj_b && L.proj_g == proj_b + DX2 && L.proj_beta == proj_b + 2 * DX2 && L.layer0 == layer0 &&
-               L.layer_stride == layer_stride && L.l_dw == 0 && L.l_dwb == l_dwb && L.l_pwb == l_pwb && L.l_g == l_g && L.l_b == l_b &&
-               L.l_pw == l_pw && L.skip0 == skip0 && L.mel_w == mel_w && L.mel_b == mel_b && L.total == total;
-    }
-};
-
-struct MelDecP {
-    const float* blob;
-    int d4, n_blocks, block_depth, n_mel;
-    const float* x;        // (B,T,d4) phoneme-rate (cum != NULL) or (B,L,d4) frame-rate
-    const float* h0;       // optional (cum != NULL): (B,T,dx2) = LN(tanh(proj(x))) already computed at PHONEME rate
-    const int* cum;        // (B,T) inclusive duration cumsum or NULL
-    const int* mel_len;    // (B) or NULL
-    const int* lmax_dev;   // device scalar or NULL
-    int lmax_host;
-    int apply_mask;
-    int B, T, L_out;
-    float* mel;            // (B, L_out, n_mel)
-    int halo;              // rows a window loses per side without carried state: (k/2) * conv layers
-    int seg_len;           // frames per segment (a workgroup's share of an utterance)
-    int n_seg;             // segments per utterance
-    float* carry_ws;       // dx2 = 256 with multi-chunk segments: per workgroup `ws_stride` floats of scratch ([conv layer slot][k/2][dx2],
-                           // then [block boundary][kDecBlockCarry4 float4]), else NULL
-    int ws_stride;
-    int carry_lds_layers;  // conv-layer carry slots kept in LDS behind the tile (what fits); the rest live in `carry_ws`
-    int skew;              // dx2 = 256 chunk walk: the tile's frame base steps back by block_depth * k/2 rows at every block boundary
-                           // (a chunk then loses block_depth * k/2 rows on its right instead of the whole halo), see the chunk loop
-    long long* trace;      // development only (-DESMI_DEC_TRACE): [wave][stamp] shader-clock stamps of block (1,0)
-};
-// measurement aid (esmi_mel_decoder_clock_probe, include/esmi.h): two {shader clock, 100 MHz clock} stamps per launch, see the chunk
-// loop.  A device global per translation unit (like the range flag), not a kernel argument: the kernel is at its register limit.
-ESMI_DEVICE_GLOBAL_PTR(long long, g_dec_clk);
-static inline int store_dec_clock_pointer(long long* slots) { return ESMI_STORE_DEVICE_GLOBAL_PTR(g_dec_clk, slots); }
-
-// block skew: a block boundary hands (block_depth + 1) * k/2 rows of dx2 floats to the next chunk, one float4 per thread
-constexpr int kDecBlockCarry4 = 512;
-// conv layers whose carried rows (k/2 rows of dx2 floats each) fit in LDS behind the tile and the parameter slots (dx2 = 256 only)
-template <int DX2>
-__host__ __device__ constexpr int dec_lds_floats(int kd);
-template <int DX2>
-inline int dec_carry_lds_layers(int kd, int n_layers) {
-    if (DX2 <= 128) return 0;
-    const int free_f = 160 * 1024 / 4 - dec_lds_floats<DX2>(kd), per = (kd / 2) * DX2;
-    const int n = free_f / per;
-    return n < n_layers ? n : n_layers;
-}
-template <int DX2>
-__host__ __device__ constexpr int dec_lds_floats(int kd) {
-    return (kDecRows + 2 * kDecPadRows) * (DX2 + 4) + (kd + 6) * DX2 + kDecRows + (ESMI_DEC_LN_ACC && DX2 > 128 ? 2 * kDecRows * 8 : 0);
-}
+constexpr int kDecWps128 = 4, kDecWeightRing256 = 2;
 
 // max_b mel_len[b], by every wave for itself: one coalesced read, no extra launch, no atomics; the result is made
 // wave-uniform (SGPR) at once.
@@ -230,6 +73,77 @@ __device__ __forceinline__ int batch_max_len(const int* __restrict__ mel_len, in
     float f = row_max32((float)v);      // lengths are far below 2^24: exact in fp32
     f = fmaxf(f, swap32_f(f));
     return uniform_i((int)f);
+}
+
+// ================================================================== row-owner LayerNorm: the arithmetic
+// LayerNorm of one row of DX2 channels: this thread's NV float4 of it in v[], gain / shift of the same channels in g[] / be[]
+// (two-pass; TPR = 16 threads per row, one DPP row: the statistics are 4 DPP adds)
+template <int DX2, int NV>
+__device__ __forceinline__ void dec_ln_regs(f32x4 (&v)[NV], const f32x4 (&g)[NV], const f32x4 (&be)[NV]) {
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
+    s = row_sum_n<16>(s);
+    const float mean = s * (1.0f / DX2);
+    float q = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            v[k][e] -= mean;
+            q = fmaf(v[k][e], v[k][e], q);
+        }
+    }
+    q = row_sum_n<16>(q);
+    const float rstd = rsqrt_fast_f32(q * (1.0f / DX2) + 1e-5f);   // v_rsq_f32 (1 ulp)
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[k][e] = fmaf(v[k][e] * rstd, g[k][e], be[k][e]);
+    }
+}
+// a row owner's NV float4 (channel groups c + 16 k) of a parameter vector or of a tile row at `pv`
+template <int NV>
+__device__ __forceinline__ void dec_owner_ld(const float* pv, f32x4 (&o)[NV]) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k) o[k] = *reinterpret_cast<const f32x4*>(pv + 4 * 16 * k);
+}
+// four floats -> the two f16 operand planes of a tile row of DX2 channels (row = [DX2 halves h1 | DX2 halves h2 | pad]; esmi_dev.h):
+// `base + off` is the dword of the four channels in the first plane
+template <int DX2>
+__device__ __forceinline__ void dec_store_planes(unsigned* base, int off, const f32x4& v) {
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    unsigned h1a, h2a, h1b, h2b;
+    split_f16_pair(v[0], v[1], h1a, h2a);
+    split_f16_pair(v[2], v[3], h1b, h2b);
+    unsigned* rowp = base + off;   // (formed here, behind the conversions, where the compiler has always seen it)
+    *reinterpret_cast<u32x2*>(rowp) = u32x2{h1a, h1b};
+    *reinterpret_cast<u32x2*>(rowp + DX2 / 2) = u32x2{h2a, h2b};
+}
+
+// measurement aid (g_dec_clk, dec_layout.h): the FIRST workgroup stamps {shader clock, 100 MHz clock} when it starts -> slot 0, and again
+// -> slot 1 at the start of each later chunk (dx2 = 256) / in front of its mel stage (dx2 = 128, one chunk).  (slot 1 - slot 0) is a
+// long stretch of the workgroup's life: shader ticks / 100 MHz ticks = the clock the CU ran at.  Both stamps come from ONE workgroup:
+// the s_memtime counters of different CUs are not comparable (a first version differenced two workgroups and read 9 GHz on some
+// boxes).  No stamp at the very end of the kernel (it costs a spilled register) nor inside the one-chunk kernel's chunk loop (the
+// store un-hoists the loop's address arithmetic: 28 spills).
+__device__ __forceinline__ void dec_clk_stamp(int ck_) {
+    long long* const clk = g_dec_clk;
+    if (clk && threadIdx.x == 0) {
+        if (blockIdx.x == 0) {
+            const int slot = ck_ == 0 ? 0 : 1;
+            clk[2 * slot] = clock_shader();
+            clk[2 * slot + 1] = clock_real100();
+        }
+    }
+}
+template <int MT, int NTW>
+__device__ __forceinline__ void dec_zero_acc(f32x16 (&acc)[MT][NTW]) {
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+#pragma unroll
+        for (int t = 0; t < NTW; ++t) acc[mt][t] = zero16();
+    }
 }
 
 // NW waves per window (8 or 16): wave (mh = w>>2, ns = w&3) owns rows [128/MH*mh, +128/MH) x columns [ns*DX2/4, +DX2/4).
@@ -253,10 +167,12 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
     constexpr int CG = DX2 / 4;             // 4-channel groups per row
     constexpr int RS = kDecRows / (kDecThreads / CG);  // rows per depthwise strip (8 or 16)
     constexpr int NV = DX2 / (4 * TPR);     // float4 per LayerNorm thread and row (channel groups c + 16k, c = lane % 16)
+    constexpr bool STREAM = DX2 > 128;      // the chunk walk (see the chunk loop)
+    constexpr bool LNA = DX2 > 128;         // LayerNorm on the accumulators (see ln_acc)
     ESMI_DYN_LDS(lds);
     // per-layer small parameters in LDS: [taps KD*DX2 | dw_b] (group A: read by the depthwise phase) and
     // [pw_b | ln_g | ln_b | skip_g | skip_b] (group B: read by the tanh / LayerNorm phases).  Single buffer: layer l+1's
-    // group A is fetched at the start of layer l's tanh phase and committed at its end, group B of layer l during layer l's
+    // group A is fetched at the start of layer l's tanh phase, group B of layer l during layer l's
     // depthwise phase -- each when no reader of the old contents is left; the global-memory latency hides behind the phase.
     constexpr int PB = (KD + 6) * DX2;
     constexpr int P_DWB = KD * DX2, P_PWB = P_DWB + DX2, P_G = P_PWB + DX2, P_B = P_G + DX2, P_SG = P_B + DX2,
@@ -337,61 +253,38 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
             stage(lay.mel_b, pbuf, DX2 / 4);
         }
     };
-    auto commit_A = [&](int) __attribute__((always_inline)) {};
-    auto commit_B = [&](int) __attribute__((always_inline)) {};
 
-    constexpr bool STREAM = DX2 > 128;
     // STREAM: the k/2 input rows of every conv layer in front of the next chunk are carried: in LDS behind the tile (`carry_lds_layers`
     // slots), else in a global scratch row set of this workgroup (written and read back by the same thread, one chunk apart: no fence)
     float* const cws = STREAM && p.carry_ws ? p.carry_ws + ((long)seg * p.B + b) * p.ws_stride : nullptr;
-    constexpr bool LNA = ESMI_DEC_LN_ACC && DX2 > 128;                // LayerNorm on the accumulators (see ln_acc below)
     float* const stat = reinterpret_cast<float*>(src + kDecRows);     // LNA: [2 exchanges][kDecRows][NS] x (sum, sum of squares)
     float* const cbuf = stat + (LNA ? 2 * kDecRows * NS * 2 : 0);     // [carry_lds_layers][PAD][DX2]
     float cnext = 0.0f;                      // the carried element of the NEXT conv layer, requested one phase ahead
-    // BLOCK SKEW (round 6).  Inside a block the tile's rows keep their frames (the skip tensor lives in the row owners' registers), so
-    // every conv layer costs k/2 valid rows on the right: `sh` = block_depth * k/2 per block.  At a block boundary nothing is held in
-    // registers across it except that skip tensor -- which IS the tile at that moment -- so the block-end LayerNorm writes its rows `sh`
-    // rows further down, the top `sh` rows (and the next conv layer's k/2 pad rows) come from the previous chunk's same boundary (the
-    // block carry, scratch), and the owners re-read their skip rows: the next block starts with 128 valid rows again, `sh` frames
-    // earlier.  A chunk therefore advances by keep = 128 - sh frames (base ES 122, small 124) instead of 128 - halo (110 / 116);
-    // tile row r of block b holds frame g0 + (n_blocks - 1 - b) * sh + r.
+    // BLOCK SKEW (round 6; DecWalk, dec_layout.h, has the arithmetic and the host derives the segments by it)
     const bool skew = STREAM && cws && p.skew;
-    const int sh = skew ? PAD * p.block_depth : 0;
-    const int off_last = sh * (p.n_blocks - 1);
+    const DecWalk wk(skew, PAD, p.n_blocks, p.block_depth, p.halo);
+    const int sh = wk.sh, off_last = wk.lead();
     const int bc_n4 = (sh + PAD) * CG;                                // float4 per block carry (<= kDecBlockCarry4: one per thread)
     float* const bcw = skew ? cws + n_layers * (PAD * DX2) : nullptr; // [block boundary][kDecBlockCarry4] float4
     // rows in front of the segment's first output frame: none at the start of an utterance (frames < 0 are zero rows); a segment that
     // starts inside an utterance has nothing carried in and recomputes what its first chunk lacks
-    const int hl0 = s0 > 0 ? (skew ? 2 * p.halo - sh : p.halo) : off_last;
-    const int keep = skew ? kDecRows - sh : kDecRows - p.halo;   // tile rows of a chunk that stay valid through every layer
+    const int hl0 = s0 > 0 ? wk.lost() : off_last;
+    const int keep = wk.keep();   // tile rows of a chunk that stay valid through every layer
     bool edge_window = false;
     int fb_cur = 0;                          // frame of tile row 0 in the current block (wave-uniform)
-    // measurement aid (g_dec_clk above): the FIRST workgroup stamps {shader clock, 100 MHz clock} when it starts -> slot 0, and again
-    // -> slot 1 at the start of each later chunk (dx2 = 256) / in front of its mel stage (dx2 = 128, one chunk).  (slot 1 - slot 0) is a
-    // long stretch of the workgroup's life: shader ticks / 100 MHz ticks = the clock the CU ran at.  Both stamps come from ONE workgroup:
-    // the s_memtime counters of different CUs are not comparable (a first version differenced two workgroups and read 9 GHz on some
-    // boxes).  No stamp at the very end of the kernel (it costs a spilled register) nor inside the one-chunk kernel's chunk loop (the
-    // store un-hoists the loop's address arithmetic: 28 spills).
-    auto clk_stamp = [&](int ck_) __attribute__((always_inline)) {
-        long long* const clk = g_dec_clk;
-        if (clk && threadIdx.x == 0) {
-            if (blockIdx.x == 0) {
-                const int slot = ck_ == 0 ? 0 : 1;
-                clk[2 * slot] = clock_shader();
-                clk[2 * slot + 1] = clock_real100();
-            }
-        }
-    };
-    if constexpr (!STREAM) clk_stamp(0);
-    for (int ck = 0;; ++ck) {
-    if constexpr (STREAM) {
-        // the thread indices pass through an opaque move per chunk: otherwise everything derived from them is loop-invariant, LICM
-        // hoists it all out of the chunk loop and the kernel spills (46 VGPRs measured)
+    // ---- the lane's place.  STREAM re-derives it per chunk and per layer:
+    // the thread indices pass through an opaque move per chunk: otherwise everything derived from them is loop-invariant, LICM
+    // hoists it all out of the chunk loop and the kernel spills (46 VGPRs measured); per layer it keeps the layer's address arithmetic
+    // from being hoisted and spilled
+    auto lane_refresh = [&]() __attribute__((always_inline)) {
         tid = opaque_i(tid);
         lane = tid & 63; i = lane & 31; h = lane >> 5;
         tid16 = (unsigned)tid * 16u; lane16 = (unsigned)lane * 16u;
-    }
-    if constexpr (STREAM) clk_stamp(ck);
+    };
+    if constexpr (!STREAM) dec_clk_stamp(0);
+    for (int ck = 0;; ++ck) {
+    if constexpr (STREAM) lane_refresh();
+    if constexpr (STREAM) dec_clk_stamp(ck);
     g0 = s0 - hl0 + ck * keep;
     f0 = g0 + off_last;
     f_lo = max(g0, s0);
@@ -437,7 +330,7 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
     // LayerNorm behind it the prologue was 12.8 % of a dx2 = 128 workgroup's life (profiles/r06_dec_budget.md).  Now the utterance's scan
     // row is copied into the (still unused) tile by all threads, next to the other loads of the prologue, and searched there.
     int* const cum_s = reinterpret_cast<int*>(xs + kDecPadRows * LDSROW);
-    const bool cum_lds = ESMI_DEC_CUM_LDS && p.cum && p.T <= kDecRows * LDSROW;
+    const bool cum_lds = p.cum && p.T <= kDecRows * LDSROW;   // (else: searched in global memory)
     if (cum_lds) {
         const int* crow = p.cum + b * p.T;
         for (int e = tid; e < p.T; e += kDecThreads) cum_s[e] = crow[e];
@@ -451,7 +344,6 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
         reinterpret_cast<f32x4*>(pbuf + P_PWB)[tid] = blob_ld(lay.proj_b, tid16);
     carry_load(0);
     fetch_A(0);
-    commit_A(0);
 #ifdef ESMI_DEC_TRACE
     ESMI_STAMP_AT(52);   // prologue loads issued
 #endif
@@ -490,6 +382,15 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
     // 17.8 % of the kernel's LDS cycles were bank conflicts, profiles/r01_l).
     constexpr int LNPER = 16 / RPT;         // waves that share one residue class of rows mod 16
     int ln_c = lane & (TPR - 1), ln_row0 = 64 * (w / LNPER) + 16 * (lane / TPR) + RPT * (w % LNPER);
+    // the owner's first row, its channel group 0, in the tile; its RPT x NV float4 from there
+    auto owner_ptr = [&]() __attribute__((always_inline)) { return xs + opaque_i((kDecPadRows + ln_row0) * LDSROW + 4 * ln_c); };
+    auto owner_load = [&](f32x4 (&v)[RPT][NV], const float* ln_ptr) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < RPT; ++j) {
+#pragma unroll
+            for (int k = 0; k < NV; ++k) v[j][k] = *reinterpret_cast<const f32x4*>(ln_ptr + j * LDSROW + 4 * TPR * k);
+        }
+    };
     // rows of the tile that lie outside [0, L) for the block whose tile row 0 holds frame `fbase`
     auto set_edge = [&](int fbase) __attribute__((always_inline)) {
         edge_window = fbase < 0 || fbase + kDecRows > L;   // some window rows lie outside [0, L) (SGPR: a scalar branch)
@@ -506,60 +407,78 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
 #pragma unroll
         for (int v = 0; v < NV; ++v) skip[j][v] = zero4();
     }
-    auto zero_acc = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-            for (int t = 0; t < NTW; ++t) acc[mt][t] = zero16();
-        }
-    };
 
     // ================================================================== contractions
     // Un-pipelined form (exact-fp32 build; in-kernel proj stage of the split build): the wave's weight slice for KSUB k-steps
     // is loaded, then the A fragments of its rows stream from LDS.
     constexpr int KSUB = DX2 <= 128 ? (SPLIT ? 4 : 8) / NTW : (NW > 8 ? 2 : 8);   // k-steps (of 8 channels) of weights in registers at a time
-#if ESMI_DEC_SPLIT
+    // the wave's B fragments of KSUB k-steps: the split form's two f16 planes per 16-channel step / the exact-fp32 form's float4 per k-step
     constexpr int KS16 = KSUB / 2;
-    u32x4 bf[NTW][KS16][2];
+    std::conditional_t<SPLIT, u32x4[NTW][KS16][2], f32x4[NTW][KSUB]> bf;
     auto load_b = [&](int wsl, int k0) __attribute__((always_inline)) {   // wsl: float offset of the wave's weight slice in the blob
+        if constexpr (SPLIT) {
 #pragma unroll
-        for (int t = 0; t < NTW; ++t) {
+            for (int t = 0; t < NTW; ++t) {
+#pragma unroll
+                for (int st = 0; st < KS16; ++st) {
+#pragma unroll
+                    for (int pl = 0; pl < 2; ++pl)
+                        bf[t][st][pl] = __builtin_bit_cast(u32x4, blob_ld(wsl + ((t * 8 + (k0 >> 1) + st) * 2 + pl) * 256, lane16));
+                }
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < NTW; ++t) {
+#pragma unroll
+                for (int kc = 0; kc < KSUB; ++kc) bf[t][kc] = blob_ld(wsl + (t * 16 + k0 + kc) * 256, lane16);
+            }
+        }
+    };
+    // fp32 rows in the tile (the split form splits them on the fly, esmi_dev.h)
+    auto mma_sub = [&](int a_col0, int k0) __attribute__((always_inline)) {
+        if constexpr (SPLIT) {
+            const float* a_base = xs + opaque_i((kDecPadRows + 32 * MT * mh + i) * LDSROW + 8 * h);
 #pragma unroll
             for (int st = 0; st < KS16; ++st) {
 #pragma unroll
-                for (int pl = 0; pl < 2; ++pl)
-                    bf[t][st][pl] = __builtin_bit_cast(u32x4, blob_ld(wsl + ((t * 8 + (k0 >> 1) + st) * 2 + pl) * 256, lane16));
-            }
-        }
-    };
-    // fp32 rows in the tile, split on the fly (esmi_dev.h)
-    auto mma_sub = [&](int a_col0, int k0) __attribute__((always_inline)) {
-        const float* a_base = xs + opaque_i((kDecPadRows + 32 * MT * mh + i) * LDSROW + 8 * h);
+                for (int mt = 0; mt < MT; ++mt) {
+                    const float* ap = a_base + 32 * mt * LDSROW + a_col0 + 8 * k0 + 16 * st;
+                    const f16x2p a2 = split_f16x2(*reinterpret_cast<const f32x4*>(ap), *reinterpret_cast<const f32x4*>(ap + 4));
 #pragma unroll
-        for (int st = 0; st < KS16; ++st) {
+                    for (int t = 0; t < NTW; ++t) acc[mt][t] = mfma32_split2_wx(bf[t][st][0], bf[t][st][1], a2, acc[mt][t]);
+                }
+            }
+        } else {
+            const float* a_base = xs + opaque_i((kDecPadRows + 32 * MT * mh + i) * LDSROW + 4 * h);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
-                const float* ap = a_base + 32 * mt * LDSROW + a_col0 + 8 * k0 + 16 * st;
-                const f16x2p a2 = split_f16x2(*reinterpret_cast<const f32x4*>(ap), *reinterpret_cast<const f32x4*>(ap + 4));
 #pragma unroll
-                for (int t = 0; t < NTW; ++t) acc[mt][t] = mfma32_split2_wx(bf[t][st][0], bf[t][st][1], a2, acc[mt][t]);
+                for (int kc = 0; kc < KSUB; ++kc) {
+                    const f32x4 av = *reinterpret_cast<const f32x4*>(a_base + 32 * mt * LDSROW + a_col0 + 8 * (k0 + kc));
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+#pragma unroll
+                        for (int t = 0; t < NTW; ++t) acc[mt][t] = mfma32(bf[t][kc][s], av[s], acc[mt][t]);
+                    }
+                }
             }
         }
     };
-    // slice pointer of chunk c of the matrix at float offset `off` (planes: 8 steps x 2 planes x 64 lanes x 16 B per tile)
-    auto wslice = [&](int off, int c) __attribute__((always_inline)) { return off + (c * (DX2 / 32) + ns * NTW) * 8 * 2 * 256; };
+    // slice offset of chunk c of the matrix at float offset `off` (a 32-column tile of a K chunk is 16 KiB in either form: 8 steps x 2 planes
+    // x 64 lanes x 16 B, or 16 k-steps x 64 lanes x 16 B)
+    auto wslice = [&](int off, int c) __attribute__((always_inline)) { return off + (c * (DX2 / 32) + ns * NTW) * 16 * 256; };
 
-    // The A operand rows already stored as the two f16 planes (row = [DX2 halves h1 | DX2 halves h2 | pad], written by the
+    // Split build only: the A operand rows already stored as the two f16 planes (row = [DX2 halves h1 | DX2 halves h2 | pad], written by the
     // depthwise phase / the last LayerNorm): per (16-channel step, row tile) two ds_read_b128 + 3*NTW MFMAs.
     // Two forms.  WD == 0 (dx2 = 128, two workgroups per CU): the weights of KSUB k-steps are loaded, then used -- the compiler
     // keeps one or two fragments in flight and the neighbour workgroup's VALU phases fill the L2 round trips (a ring that
     // pipelines the loop measured slower there: profiles/r03_probes/decoder_round3_experiments.md).  WD > 0 (dx2 = 256, ONE workgroup
     // per CU, nobody to fill the gaps): hand-pipelined -- an item = (16-channel step s, row tile mt); weight fragments of step s + WD
-    // and A fragments of item q + AD are requested while item q's MFMAs run (VGPR rings; scheduling fences keep hipcc from sinking
+    // and A fragments of item q + 1 are requested while item q's MFMAs run (VGPR rings; scheduling fences keep hipcc from sinking
     // the loads back to their first use).  small ES decoder 1774 -> 1687 us with WD = 2; WD = 4 spills (1736), 6: 1976.
-    constexpr int WD = DX2 > 128 ? kDecWeightRing256 : 0, AD = kDecARing;
+    constexpr int WD = DX2 > 128 ? kDecWeightRing256 : 0;
     constexpr int NSTEP = 8 * KCH, NITEM = NSTEP * MT;
-    static_assert(WD >= 0 && WD <= NSTEP && AD >= 1 && AD <= NITEM, "ring depths");
+    static_assert(WD >= 0 && WD <= NSTEP, "ring depth");
     u32x4 wr[WD > 0 ? WD : 1][NTW][2];
     // (`ntc`: 32-column tiles per wave of THIS contraction -- NTW for the conv layers; 1 for the mel Linear of the dx2 = 256 kernel, whose
     // n_mel <= 96 columns are packed as three one-tile slices so that three SIMDs share them instead of two)
@@ -575,7 +494,7 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
     // the first WD weight steps of the matrix at `off` (issued ahead of the barrier that precedes the K loop: the L2 round
     // trip then overlaps the barrier wait)
     auto gemm_prefetch = [&](int off, auto ntc) __attribute__((always_inline)) {
-        if constexpr (WD > 0) {
+        if constexpr (SPLIT && WD > 0) {   // (nothing in the forms without a ring)
 #pragma unroll
             for (int s = 0; s < WD; ++s) w_fetch(off, s, s, ntc);
             sched_fence();
@@ -606,57 +525,27 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
                 }
             }
         } else {
-            f16x2p ar[AD];
-            auto a_fetch = [&](int q, int slot) __attribute__((always_inline)) {
+            f16x2p ar;
+            auto a_fetch = [&](int q) __attribute__((always_inline)) {
                 const int s = q / MT, mt = q % MT;
                 const unsigned* ap = a_base + 32 * mt * LDSROW + 64 * (s >> 3) + 8 * (s & 7);
-                ar[slot].h1 = *reinterpret_cast<const u32x4*>(ap);
-                ar[slot].h2 = *reinterpret_cast<const u32x4*>(ap + DX2 / 2);
+                ar.h1 = *reinterpret_cast<const u32x4*>(ap);
+                ar.h2 = *reinterpret_cast<const u32x4*>(ap + DX2 / 2);
             };
-#pragma unroll
-            for (int q = 0; q < AD; ++q) a_fetch(q, q);
+            a_fetch(0);
             sched_fence();
 #pragma unroll
             for (int q = 0; q < NITEM; ++q) {
                 const int s = q / MT, mt = q % MT;
 #pragma unroll
                 for (int t = 0; t < NT; ++t)
-                    acc[mt][t] = mfma32_split2_wx(wr[s % (WD > 0 ? WD : 1)][t][0], wr[s % (WD > 0 ? WD : 1)][t][1], ar[q % AD], acc[mt][t]);
-                if (q + AD < NITEM) a_fetch(q + AD, q % AD);
+                    acc[mt][t] = mfma32_split2_wx(wr[s % (WD > 0 ? WD : 1)][t][0], wr[s % (WD > 0 ? WD : 1)][t][1], ar, acc[mt][t]);
+                if (q + 1 < NITEM) a_fetch(q + 1);
                 if (mt == MT - 1 && s + WD < NSTEP) w_fetch(off, s + WD, s % (WD > 0 ? WD : 1), ntc);
                 sched_fence();
             }
         }
     };
-#else
-    f32x4 bf[NTW][KSUB];
-    auto load_b = [&](int wsl, int k0) __attribute__((always_inline)) {   // wsl: float offset of the wave's weight slice in the blob
-#pragma unroll
-        for (int t = 0; t < NTW; ++t) {
-#pragma unroll
-            for (int kc = 0; kc < KSUB; ++kc) bf[t][kc] = blob_ld(wsl + (t * 16 + k0 + kc) * 256, lane16);
-        }
-    };
-    auto mma_sub = [&](int a_col0, int k0) __attribute__((always_inline)) {
-        const float* a_base = xs + opaque_i((kDecPadRows + 32 * MT * mh + i) * LDSROW + 4 * h);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-            for (int kc = 0; kc < KSUB; ++kc) {
-                const f32x4 av = *reinterpret_cast<const f32x4*>(a_base + 32 * mt * LDSROW + a_col0 + 8 * (k0 + kc));
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-#pragma unroll
-                    for (int t = 0; t < NTW; ++t) acc[mt][t] = mfma32(bf[t][kc][s], av[s], acc[mt][t]);
-                }
-            }
-        }
-    };
-    // slice pointer of chunk c of the matrix at float offset `off`
-    auto wslice = [&](int off, int c) __attribute__((always_inline)) { return off + (c * (DX2 / 32) + ns * NTW) * 16 * 256; };
-    auto gemm_prefetch = [&](int, auto) __attribute__((always_inline)) {};
-    auto gemm_planes = [&](int, auto) __attribute__((always_inline)) {};
-#endif
     // full dx2-wide contraction over fp32 rows of the tile, un-pipelined
     auto gemm_rows = [&](int off) __attribute__((always_inline)) {
 #pragma unroll
@@ -677,10 +566,12 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
     // the K loop, before the barrier that waits for the last reader of the operand planes: a wave that is through its MFMAs spends the
     // transcendental-heavy part of the epilogue while the other waves of its SIMD still feed the matrix pipe -- and `store_acc`
     // writes them to the tile after that barrier.
+    // first channel of the lane's quad 0 in column tile t (quad g: + 8 g)
+    auto acc_col = [&](int t) __attribute__((always_inline)) { return ns * WCOLS + 32 * t + 4 * h; };
     auto tanh_acc = [&](const float* bias) __attribute__((always_inline)) {
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
-            const float* bp = bias + opaque_i(ns * WCOLS + 32 * t + 4 * h);
+            const float* bp = bias + opaque_i(acc_col(t));
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x4 bc = *reinterpret_cast<const f32x4*>(bp + 8 * g) * kTanhExpScale;   // the exponent's 2 log2(e) goes into the bias and the scale of the fma
@@ -740,14 +631,14 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
             const f32x4 a = *reinterpret_cast<const f32x4*>(sp + 32 * mt * NS * 2), b = *reinterpret_cast<const f32x4*>(sp + 32 * mt * NS * 2 + 4);
             const float s1 = (a[0] + a[2]) + (b[0] + b[2]), s2 = (a[1] + a[3]) + (b[1] + b[3]);
             mean[mt] = s1 * (1.0f / DX2);
-            rstd[mt] = ESMI_DEC_RSQRT(fmaxf(fmaf(-mean[mt], mean[mt], s2 * (1.0f / DX2)), 0.0f) + 1e-5f);
+            rstd[mt] = rsqrt_fast_f32(fmaxf(fmaf(-mean[mt], mean[mt], s2 * (1.0f / DX2)), 0.0f) + 1e-5f);
         }
     };
     auto ln_acc = [&](const float* gain, const float* shift, const float (&mean)[MT], const float (&rstd)[MT]) __attribute__((always_inline)) {
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
-            const float* gp = gain + opaque_i(ns * WCOLS + 32 * t + 4 * h);
-            const float* bp = shift + opaque_i(ns * WCOLS + 32 * t + 4 * h);
+            const float* gp = gain + opaque_i(acc_col(t));
+            const float* bp = shift + opaque_i(acc_col(t));
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x4 gv = *reinterpret_cast<const f32x4*>(gp + 8 * g), bv = *reinterpret_cast<const f32x4*>(bp + 8 * g);
@@ -772,7 +663,7 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
             float* base = xs + opaque_i((kDecPadRows + 32 * MT * mh + i + shw) * LDSROW + ns * WCOLS + 32 * t + 4 * h);
-            unsigned* pbase = reinterpret_cast<unsigned*>(xs) + opaque_i((kDecPadRows + 32 * MT * mh + i) * LDSROW + (ns * WCOLS + 32 * t + 4 * h) / 2);
+            unsigned* pbase = reinterpret_cast<unsigned*>(xs) + opaque_i((kDecPadRows + 32 * MT * mh + i) * LDSROW + acc_col(t) / 2);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
 #pragma unroll
@@ -781,48 +672,13 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = inside[mt] ? acc[mt][t][4 * g + e] : 0.0f;
                     if (SPLIT && planes_) {
-                        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-                        unsigned h1a, h2a, h1b, h2b;
-                        split_f16_pair(v[0], v[1], h1a, h2a);
-                        split_f16_pair(v[2], v[3], h1b, h2b);
-                        unsigned* rowp = pbase + 32 * mt * LDSROW + 4 * g;
-                        *reinterpret_cast<u32x2*>(rowp) = u32x2{h1a, h1b};
-                        *reinterpret_cast<u32x2*>(rowp + DX2 / 2) = u32x2{h2a, h2b};
+                        dec_store_planes<DX2>(pbase, 32 * mt * LDSROW + 4 * g, v);
                     } else if (keep_row[mt]) {
                         *reinterpret_cast<f32x4*>(base + 32 * mt * LDSROW + 8 * g) = v;
                     }
                 }
             }
         }
-    };
-    // LayerNorm of one row: this thread's NV float4 of it in v[], gain / shift of the same channels in g[] / be[]
-    // (two-pass; 16 threads per row)
-    auto ln_regs = [&](f32x4 (&v)[NV], const f32x4 (&g)[NV], const f32x4 (&be)[NV]) __attribute__((always_inline)) {
-        float s = 0.0f;
-#pragma unroll
-        for (int k = 0; k < NV; ++k) s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
-        s = row_sum_n<TPR>(s);
-        const float mean = s * (1.0f / DX2);
-        float q = 0.0f;
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[k][e] -= mean;
-                q = fmaf(v[k][e], v[k][e], q);
-            }
-        }
-        q = row_sum_n<TPR>(q);
-        const float rstd = ESMI_DEC_RSQRT(q * (1.0f / DX2) + 1e-5f);
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[k][e] = fmaf(v[k][e] * rstd, g[k][e], be[k][e]);
-        }
-    };
-    auto ln_params = [&](const float* pv, f32x4 (&o)[NV]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) o[k] = *reinterpret_cast<const f32x4*>(pv + 4 * TPR * k);
     };
     // LN pass over the tile (in place): x = LN(x) [; x = LN_s(x + skip), skip = x at a block end]; rows outside [0, L) -> 0.
     // PLANES: the rows are written as the two f16 planes the pipelined K loop reads (the last LayerNorm feeds the mel Linear
@@ -833,26 +689,22 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
     // dropped: they are the rows the block lost), behind a barrier that waits for every owner to have read its rows.
     auto ln_pass = [&](const float* pb0, bool block_end_, bool planes_, int shw) __attribute__((always_inline)) {
         const float* pb = pb0 + opaque_i(4 * ln_c);           // this thread's channels of every param vector
-        float* ln_ptr = xs + opaque_i((kDecPadRows + ln_row0) * LDSROW + 4 * ln_c);
+        float* ln_ptr = owner_ptr();
         f32x4 g[NV], be[NV];
-        ln_params(pb + P_G, g);
-        ln_params(pb + P_B, be);
+        dec_owner_ld(pb + P_G, g);
+        dec_owner_ld(pb + P_B, be);
         f32x4 v[RPT][NV];
+        owner_load(v, ln_ptr);
 #pragma unroll
-        for (int j = 0; j < RPT; ++j) {
-#pragma unroll
-            for (int k = 0; k < NV; ++k) v[j][k] = *reinterpret_cast<const f32x4*>(ln_ptr + j * LDSROW + 4 * TPR * k);
-        }
-#pragma unroll
-        for (int j = 0; j < RPT; ++j) ln_regs(v[j], g, be);
+        for (int j = 0; j < RPT; ++j) dec_ln_regs<DX2>(v[j], g, be);
         if (block_end_) {  // end of a decoder block: skip = LN_s(x + skip), networks.py:299
-            ln_params(pb + P_SG, g);
-            ln_params(pb + P_SB, be);
+            dec_owner_ld(pb + P_SG, g);
+            dec_owner_ld(pb + P_SB, be);
 #pragma unroll
             for (int j = 0; j < RPT; ++j) {
 #pragma unroll
                 for (int k = 0; k < NV; ++k) v[j][k] += skip[j][k];
-                ln_regs(v[j], g, be);
+                dec_ln_regs<DX2>(v[j], g, be);
             }
         }
         if (edge_window) {   // workgroup-uniform: only the first / last windows of an utterance hold rows outside [0, L)
@@ -867,7 +719,8 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
 #pragma unroll
             for (int j = 0; j < RPT; ++j) {
 #pragma unroll
-                for (int k = 0; k < NV; ++k) {
+                for (int k = 0; k < NV; ++k) {   // (spelled out, not dec_store_planes: with the call the dx2 = 128 kernels' listing differs from
+                                                 // its predecessor's -- the same instructions in another order; whether that costs time is unmeasured)
                     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
                     unsigned h1a, h2a, h1b, h2b;
                     split_f16_pair(v[j][k][0], v[j][k][1], h1a, h2a);
@@ -911,15 +764,11 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
             const int r = e / (DX2 / 4), q = e - r * (DX2 / 4);
             const int s = src[r];
             f32x4 v = zero4();
-#if ESMI_DEC_H0_NT
             if (s >= 0) v = STREAM ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p.h0 + (long)s * DX2 + 4 * q)) : ld4(p.h0 + (long)s * DX2 + 4 * q);
-#else
-            if (s >= 0) v = ld4(p.h0 + (long)s * DX2 + 4 * q);
-#endif
             else if (s == -2) {
                 const f32x4 bb = *reinterpret_cast<const f32x4*>(pbuf + P_PWB + 4 * q);
 #pragma unroll
-                for (int c = 0; c < 4; ++c) v[c] = ESMI_DEC_TANH(bb[c]);
+                for (int c = 0; c < 4; ++c) v[c] = tanh_fast_f32(bb[c]);
             }
             *reinterpret_cast<f32x4*>(xs + (kDecPadRows + r) * LDSROW + 4 * q) = v;
         }
@@ -932,25 +781,21 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
 #endif
         {   // row owners: LayerNorm only for the padding frames' rows; skip = the stage's output
             const float* pb = pbuf + opaque_i(4 * ln_c);
-            float* ln_ptr = xs + opaque_i((kDecPadRows + ln_row0) * LDSROW + 4 * ln_c);
-#pragma unroll
-            for (int j = 0; j < RPT; ++j) {
-#pragma unroll
-                for (int k = 0; k < NV; ++k) skip[j][k] = *reinterpret_cast<const f32x4*>(ln_ptr + j * LDSROW + 4 * TPR * k);
-            }
+            float* ln_ptr = owner_ptr();
+            owner_load(skip, ln_ptr);
             unsigned pad_rows = 0;
 #pragma unroll
             for (int j = 0; j < RPT; ++j) pad_rows |= (src[ln_row0 + j] == -2 ? 1u : 0u) << j;
             if (ballot64(pad_rows != 0u) != 0ull) {   // wave-uniform: the row reductions inside are wave-level exchanges
                 f32x4 g[NV], be[NV];
-                ln_params(pb + P_G, g);
-                ln_params(pb + P_B, be);
+                dec_owner_ld(pb + P_G, g);
+                dec_owner_ld(pb + P_B, be);
 #pragma unroll
                 for (int j = 0; j < RPT; ++j) {
                     f32x4 u[NV];
 #pragma unroll
                     for (int k = 0; k < NV; ++k) u[k] = skip[j][k];
-                    ln_regs(u, g, be);
+                    dec_ln_regs<DX2>(u, g, be);
 #pragma unroll
                     for (int k = 0; k < NV; ++k) {
                         if ((pad_rows >> j) & 1u) skip[j][k] = u[k];
@@ -962,7 +807,7 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
         carry_put(0);
         __syncthreads();
     } else {
-        zero_acc();
+        dec_zero_acc(acc);
         const int nchunks = p.d4 / 128;
         for (int ch = 0; ch < nchunks; ++ch) {
             if (ch > 0) __syncthreads();  // previous chunk fully consumed
@@ -986,15 +831,15 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
         __syncthreads();
         {   // LN(tanh(proj)); skip = the stage's output
             const float* pb = pbuf + opaque_i(4 * ln_c);
-            float* ln_ptr = xs + opaque_i((kDecPadRows + ln_row0) * LDSROW + 4 * ln_c);
+            float* ln_ptr = owner_ptr();
             f32x4 g[NV], be[NV];
-            ln_params(pb + P_G, g);
-            ln_params(pb + P_B, be);
+            dec_owner_ld(pb + P_G, g);
+            dec_owner_ld(pb + P_B, be);
 #pragma unroll
             for (int j = 0; j < RPT; ++j) {
 #pragma unroll
                 for (int k = 0; k < NV; ++k) skip[j][k] = *reinterpret_cast<const f32x4*>(ln_ptr + j * LDSROW + 4 * TPR * k);
-                ln_regs(skip[j], g, be);
+                dec_ln_regs<DX2>(skip[j], g, be);
 #pragma unroll
                 for (int k = 0; k < NV; ++k) {
                     if (!row_inside(j)) skip[j][k] = zero4();
@@ -1017,10 +862,8 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
         // conv-layer carry slots (see carry_load): without the skew one per layer; with it the first layer of blocks >= 1 has none
         const int slot = skew ? ((lin == 0 && l > 0) ? -1 : l - blk) : l;
         const int slot_next = skew ? (block_end ? -1 : l + 1 - blk) : l + 1;
-        if constexpr (STREAM) {   // (as at the top of the chunk loop: keeps the layer's address arithmetic from being hoisted and spilled)
-            tid = opaque_i(tid);
-            lane = tid & 63; i = lane & 31; h = lane >> 5;
-            tid16 = (unsigned)tid * 16u; lane16 = (unsigned)lane * 16u;
+        if constexpr (STREAM) {   // (as at the top of the chunk loop)
+            lane_refresh();
             ln_c = lane & (TPR - 1); ln_row0 = 64 * (w / LNPER) + 16 * (lane / TPR) + RPT * (w % LNPER);
             dw_cg = tid % CG; dw_r0 = (tid / CG) * RS;
             if (skew && lin == 0 && l > 0) {
@@ -1052,12 +895,8 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
             }
         }
         if (!LNA && lin == 0 && l > 0) {   // a block starts: its input (the tile, complete since the barrier behind the last LayerNorm) is the skip tensor
-            const float* ln_ptr = xs + opaque_i((kDecPadRows + ln_row0) * LDSROW + 4 * ln_c);
-#pragma unroll
-            for (int j = 0; j < RPT; ++j) {
-#pragma unroll
-                for (int k = 0; k < NV; ++k) skip[j][k] = *reinterpret_cast<const f32x4*>(ln_ptr + j * LDSROW + 4 * TPR * k);
-            }
+            const float* ln_ptr = owner_ptr();
+            owner_load(skip, ln_ptr);
         }
         ESMI_STAMP();   // 0: layer start
         // 1. depthwise conv in place: window -> registers | barrier | filtered rows -> tile (as the K loop's operand planes)
@@ -1086,26 +925,19 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
                     for (int e = 0; e < 4; ++e) a[e] = fmaf(win[r + j][e], tap[j][e], a[e]);
                 }
                 if (SPLIT) {   // the K loop's A operand, already split (esmi_dev.h): 4 channels = 2 dwords per plane
-                    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-                    unsigned h1a, h2a, h1b, h2b;
-                    split_f16_pair(a[0], a[1], h1a, h2a);
-                    split_f16_pair(a[2], a[3], h1b, h2b);
-                    unsigned* rowp = prow + r * LDSROW;
-                    *reinterpret_cast<u32x2*>(rowp) = u32x2{h1a, h1b};
-                    *reinterpret_cast<u32x2*>(rowp + DX2 / 2) = u32x2{h2a, h2b};
+                    dec_store_planes<DX2>(prow, r * LDSROW, a);
                 } else {
                     *reinterpret_cast<f32x4*>(col + (r + PAD) * LDSROW) = a;
                 }
             }
         }
-        commit_B(l);
         gemm_prefetch(lbase + lay.l_pw, NtwC{});   // first weight steps: in flight across the barrier
         ESMI_STAMP();   // 3: dw written
         __syncthreads();
         ESMI_STAMP();   // 4: barrier
         // 2. pointwise conv: K = dx2
-        zero_acc();
-        if (SPLIT) gemm_planes(lbase + lay.l_pw, NtwC{});
+        dec_zero_acc(acc);
+        if constexpr (SPLIT) gemm_planes(lbase + lay.l_pw, NtwC{});
         else gemm_rows(lbase + lay.l_pw);
         ESMI_STAMP();   // 5: K loop issued
         // 3. bias + tanh on the accumulators (no tile access: ahead of the barrier), then -> tile
@@ -1116,7 +948,6 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
         __syncthreads();  // all reads of the filtered tile done
         ESMI_STAMP();   // 7: barrier
         if constexpr (!LNA) store_acc();
-        commit_A(l + 1);     // (the taps' LDS slots were last read by this layer's depthwise phase)
         ESMI_STAMP();   // 8: tanh stored
         if constexpr (!LNA) __syncthreads();
         ESMI_STAMP();   // 9: barrier
@@ -1179,9 +1010,13 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
     const float* mb = pbuf;                          // mel bias (zero padded to dx2)
     const bool vec_ok = (p.n_mel & 3) == 0;          // rows of 16-byte multiples: float4 stores
     if (mel_wave) {
-        zero_acc();
-        if (SPLIT && n_layers > 0) gemm_planes(lay.mel_w, NtmC{});
-        else gemm_rows(lay.mel_w);
+        dec_zero_acc(acc);
+        if constexpr (SPLIT) {
+            if (n_layers > 0) gemm_planes(lay.mel_w, NtmC{});
+            else gemm_rows(lay.mel_w);
+        } else {
+            gemm_rows(lay.mel_w);
+        }
     }
 #ifdef ESMI_DEC_TRACE
     ESMI_STAMP_AT(60);   // mel K loop issued
@@ -1221,11 +1056,7 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
         if (vec_ok) {
             const int n4 = (out_hi - f_lo) * (p.n_mel >> 2);
             for (int e = tid; e < n4; e += kDecThreads) {
-#if ESMI_DEC_MEL_NT
                 __builtin_nontemporal_store(*reinterpret_cast<const f32x4*>(sp + 4 * e), reinterpret_cast<f32x4*>(dp + 4 * e));
-#else
-                *reinterpret_cast<f32x4*>(dp + 4 * e) = *reinterpret_cast<const f32x4*>(sp + 4 * e);
-#endif
             }
         } else {   // rows that are not 16-byte multiples: element by element
             const int n = (out_hi - f_lo) * p.n_mel;
@@ -1266,4 +1097,24 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
     }   // chunks of the segment
 }
 
+// ---- one instantiation: the launcher and the clock probe's setter of (DX2, KD), declared in dec_layout.h.  Each tu_dec_<dx2>_<k>.hip
+// is ESMI_DEC_INSTANCE(dx2, k) and nothing else: this kernel dominates the library's compile time, so the four build side by side.
+template <int DX2, int KD>
+int set_dec_clock(long long* slots) { return store_dec_clock_pointer(slots); }
+
+template <int DX2, int KD>
+int launch_mel_decoder(const MelDecP& p, dim3 grid, hipStream_t st) {
+    constexpr int NW = 8;   // waves per window (16 for dx2 = 256 measured 30 % slower: HISTORY.md 3.1)
+    const int lds = (dec_lds_floats<DX2>(KD) + p.carry_lds_layers * (KD / 2) * DX2) * (int)sizeof(float);
+    ESMI_LAUNCH_LDS((mel_decoder_kernel<DX2, KD, NW>), grid, dim3(64 * NW), lds, st, p);
+    return launch_status();
+}
+
 }  // namespace esmi
+
+#define ESMI_DEC_INSTANCE(DX2, KD)                                                                    \
+    ESMI_TU_RANGE_SETTER(dec_##DX2##_##KD)                                                            \
+    namespace esmi {                                                                                  \
+    template int set_dec_clock<DX2, KD>(long long*);                                                  \
+    template int launch_mel_decoder<DX2, KD>(const MelDecP&, dim3, hipStream_t);                      \
+    }

@@ -1,65 +1,28 @@
-// esmi C-ABI, translation unit "tu_decoder.hip": the mel decoder: blob packer and mel_decoder_kernel launches (mel_decoder.h)
+// esmi C-ABI, translation unit "tu_decoder.hip": the mel decoder: blob packer and mel_decoder_kernel launches (dec_layout.h; the kernel
+// itself, mel_decoder.h, is compiled by the tu_dec_<dx2>_<k>.hip units)
 // One of several translation units of libesmi.so (compiled in parallel by __graft_entry__.build(); the simulator build
 // tools/wavesim/build.sh compiles the same files with the host compiler).  Internal launchers are declared in launch.h.
 #include "launch.h"
 #include <cstdlib>
 
-#include "mel_decoder.h"
+#include "dec_layout.h"
 
 using namespace esmi;
 ESMI_TU_RANGE_SETTER(decoder)
-
-namespace esmi {
-int launch_mel_decoder_128_5(const MelDecP& p, dim3 grid, hipStream_t st);
-int launch_mel_decoder_128_3(const MelDecP& p, dim3 grid, hipStream_t st);
-int launch_mel_decoder_256_5(const MelDecP& p, dim3 grid, hipStream_t st);
-int launch_mel_decoder_256_3(const MelDecP& p, dim3 grid, hipStream_t st);
-int set_dec_clock_128_5(long long* slots);
-int set_dec_clock_128_3(long long* slots);
-int set_dec_clock_256_5(long long* slots);
-int set_dec_clock_256_3(long long* slots);
-}  // namespace esmi
 
 #ifdef ESMI_DEC_TRACE
 long long* g_esmi_trace = nullptr;
 extern "C" void esmi_dev_set_trace(long long* ptr) { g_esmi_trace = ptr; }
 #endif
 
-extern "C" {
+namespace {
 
-// measurement aid (include/esmi.h): arm / disarm the clock probe of every decoder instantiation (one device global per unit)
-int esmi_mel_decoder_clock_probe(int64_t* dev_slots) {
-    long long* s = reinterpret_cast<long long*>(dev_slots);
-    int (*const setters[])(long long*) = {set_dec_clock_128_5, set_dec_clock_128_3, set_dec_clock_256_5, set_dec_clock_256_3};
-    for (auto set : setters)
-        if (int rc = set(s)) return rc;
-    return ESMI_OK;
-}
-
-static int dec_check(const esmi_decoder_shape* s) {
-    if (!s) return ESMI_ERR_ARG;
-    if (s->dx2 != 128 && s->dx2 != 256) return ESMI_ERR_UNSUPPORTED;
-    if (s->d4 <= 0 || s->d4 % 128) return ESMI_ERR_UNSUPPORTED;
-    if (s->kernel != 3 && s->kernel != 5) return ESMI_ERR_UNSUPPORTED;
-    if (s->n_mel <= 0 || s->n_mel > kMelCols) return ESMI_ERR_UNSUPPORTED;
-    if (s->n_blocks < 1 || s->block_depth < 1 || s->n_blocks * s->block_depth > ESMI_MAX_DEC_LAYERS) return ESMI_ERR_UNSUPPORTED;
-    if (2 * (s->kernel / 2) * s->n_blocks * s->block_depth >= kDecRows - 32) return ESMI_ERR_UNSUPPORTED;
-    return ESMI_OK;
-}
-
-size_t esmi_mel_decoder_blob_bytes(const esmi_decoder_shape* s) {
-    if (dec_check(s)) return 0;
-    return (size_t)dec_layout(s->d4, s->dx2, s->kernel, s->n_blocks, s->block_depth).total * sizeof(float);
-}
-
-int esmi_mel_decoder_pack_f32(const esmi_decoder_weights* w, const esmi_decoder_shape* s, float* blob,
-                              esmi_stream_t stream) {
-    int rc = dec_check(s);
-    if (rc) return rc;
-    if (!w || !blob) return ESMI_ERR_ARG;
-    const DecLayout L = dec_layout(s->d4, s->dx2, s->kernel, s->n_blocks, s->block_depth);
-    hipStream_t st = S(stream);
-    const int dx2 = s->dx2, ntw = dx2 / 128;
+// the blob of one (dx2, kernel) instantiation, written by the layout its kernel reads by (DecLay, dec_layout.h)
+template <int DX2, int KD>
+int dec_pack(const esmi_decoder_weights* w, const esmi_decoder_shape* s, float* blob, hipStream_t st) {
+    if (DecLay<DX2, KD>::floats(s->d4, s->n_blocks, s->block_depth) > kDecBlobMaxFloats) return ESMI_ERR_UNSUPPORTED;
+    const DecLay<DX2, KD> L(s->d4, s->n_blocks, s->block_depth);
+    constexpr int dx2 = DX2, ntw = DX2 / 128;
     auto bslice = [&](const float* src, long off, int N, int K, int ntw) {
 #if ESMI_DEC_SPLIT == 2
         const long n = (long)(K / 128) * 4 * ntw * 8 * 2 * 256;
@@ -75,8 +38,8 @@ int esmi_mel_decoder_pack_f32(const esmi_decoder_weights* w, const esmi_decoder_
     };
     bslice(w->proj_w, L.proj_w, dx2, s->d4, ntw);
     vec(w->proj_b, L.proj_b, dx2, dx2);
-    vec(w->proj_ln_g, L.proj_g, dx2, dx2);
-    vec(w->proj_ln_b, L.proj_beta, dx2, dx2);
+    vec(w->proj_ln_g, L.proj_b + dx2, dx2, dx2);
+    vec(w->proj_ln_b, L.proj_b + 2 * dx2, dx2, dx2);
     for (int l = 0; l < s->n_blocks * s->block_depth; ++l) {
         const long base = L.layer0 + (long)l * L.layer_stride;
         if (!w->dw_w[l] || !w->pw_w[l]) return ESMI_ERR_ARG;
@@ -102,21 +65,71 @@ int esmi_mel_decoder_pack_f32(const esmi_decoder_weights* w, const esmi_decoder_
     return launch_status();
 }
 
+// the (dx2, kernel) instantiations: launcher and clock-probe setter (defined in tu_dec_<dx2>_<k>.hip), blob size and packer
+struct DecInst {
+    int dx2, kd;
+    int (*launch)(const MelDecP&, dim3, hipStream_t);
+    int (*set_clock)(long long*);
+    long (*blob_floats)(int d4, int n_blocks, int block_depth);
+    int (*pack)(const esmi_decoder_weights*, const esmi_decoder_shape*, float*, hipStream_t);
+};
+template <int DX2, int KD>
+constexpr DecInst dec_inst_of() {
+    return {DX2, KD, launch_mel_decoder<DX2, KD>, set_dec_clock<DX2, KD>, DecLay<DX2, KD>::floats, dec_pack<DX2, KD>};
+}
+const DecInst kDecInst[] = {dec_inst_of<128, 5>(), dec_inst_of<128, 3>(), dec_inst_of<256, 5>(), dec_inst_of<256, 3>()};
+const DecInst* dec_inst(const esmi_decoder_shape* s) {   // (after dec_check: the shape is one of the table's)
+    for (const DecInst& d : kDecInst)
+        if (d.dx2 == s->dx2 && d.kd == s->kernel) return &d;
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+// measurement aid (include/esmi.h): arm / disarm the clock probe of every decoder instantiation (one device global per unit)
+int esmi_mel_decoder_clock_probe(int64_t* dev_slots) {
+    long long* s = reinterpret_cast<long long*>(dev_slots);
+    for (const DecInst& d : kDecInst)
+        if (int rc = d.set_clock(s)) return rc;
+    return ESMI_OK;
+}
+
+static int dec_check(const esmi_decoder_shape* s) {
+    if (!s) return ESMI_ERR_ARG;
+    if (s->dx2 != 128 && s->dx2 != 256) return ESMI_ERR_UNSUPPORTED;
+    if (s->d4 <= 0 || s->d4 % 128) return ESMI_ERR_UNSUPPORTED;
+    if (s->kernel != 3 && s->kernel != 5) return ESMI_ERR_UNSUPPORTED;
+    if (s->n_mel <= 0 || s->n_mel > kMelCols) return ESMI_ERR_UNSUPPORTED;
+    if (s->n_blocks < 1 || s->block_depth < 1 || s->n_blocks * s->block_depth > ESMI_MAX_DEC_LAYERS) return ESMI_ERR_UNSUPPORTED;
+    if (2 * (s->kernel / 2) * s->n_blocks * s->block_depth >= kDecRows - 32) return ESMI_ERR_UNSUPPORTED;
+    return ESMI_OK;
+}
+
+size_t esmi_mel_decoder_blob_bytes(const esmi_decoder_shape* s) {
+    if (dec_check(s)) return 0;
+    return (size_t)dec_inst(s)->blob_floats(s->d4, s->n_blocks, s->block_depth) * sizeof(float);
+}
+
+int esmi_mel_decoder_pack_f32(const esmi_decoder_weights* w, const esmi_decoder_shape* s, float* blob,
+                              esmi_stream_t stream) {
+    int rc = dec_check(s);
+    if (rc) return rc;
+    if (!w || !blob) return ESMI_ERR_ARG;
+    return dec_inst(s)->pack(w, s, blob, S(stream));
+}
+
 // segments per utterance / frames per segment of the dx2 = 256 kernel when it may carry rows between chunks: whole utterances when
 // the batch fills the chip, else as many segments per utterance as it takes to give every CU one (a segment's first chunk recomputes
 // its left halo, so fewer, longer segments are cheaper)
-// Block skew (mel_decoder.h, the chunk loop): a chunk advances by 128 - block_depth * k/2 frames instead of 128 - halo; used when the
-// model has more than one block and a block carry fits one float4 per thread.
-static bool stream_skew(const esmi_decoder_shape* s) {
-    return s->n_blocks >= 2 && (s->block_depth + 1) * (s->kernel / 2) * (s->dx2 / 4) <= kDecBlockCarry4;
-}
+// (what a chunk keeps, leads with and loses is DecWalk, dec_layout.h: the kernel derives these by the same lines; whether the walk is
+// skewed is decided here, dec_walk_skew, and handed to the kernel as p.skew)
+static bool stream_skew(const esmi_decoder_shape* s) { return dec_walk_skew(s->dx2, s->kernel, s->n_blocks, s->block_depth); }
 static void stream_geometry(const esmi_decoder_shape* s, int B, int L_out, int* n_seg_out, int* seg_len_out) {
-    const int pad = s->kernel / 2, halo = pad * s->n_blocks * s->block_depth;
-    const bool skew = stream_skew(s);
-    const int sh = pad * s->block_depth;
-    // frames a chunk keeps; frames in front of an utterance's first output frame (the last block's tile starts that much early); rows a
-    // segment that starts inside an utterance recomputes (nothing is carried into its first chunk)
-    const int keep = skew ? kDecRows - sh : kDecRows - halo, lead = skew ? halo - sh : 0, lost = skew ? 2 * halo - sh : halo;
+    const int pad = s->kernel / 2;
+    const DecWalk wk(stream_skew(s), pad, s->n_blocks, s->block_depth, pad * s->n_blocks * s->block_depth);
+    const int keep = wk.keep(), lead = wk.lead(), lost = wk.lost();
     const int chunks = (L_out + lead + keep - 1) / keep;
     // (ESMI_DEC_STREAM_WGS: test knob -- the workgroup count the segmentation aims at, default one per CU; 1 = whole-utterance walks
     // at any batch size, which is how the CPU simulator tests reach multi-chunk segments without a 256-utterance batch)
@@ -160,12 +173,8 @@ static int mel_decoder_launch(const float* blob, const esmi_decoder_shape* s, co
     if (!lmax_dev && lmax_host < 0 && (!mel_len || !cum)) return ESMI_ERR_ARG;   // L derived from mel_len
     MelDecP p;
     p.blob = blob;
-    {   // the kernel derives the blob layout itself (DecLay: compile-time offsets); it must be the one the packer wrote by
-        const DecLayout L = dec_layout(s->d4, s->dx2, s->kernel, s->n_blocks, s->block_depth);
-        const bool same = s->dx2 == 128 ? (s->kernel == 5 ? DecLay<128, 5>(s->d4, s->n_blocks, s->block_depth).matches(L) : DecLay<128, 3>(s->d4, s->n_blocks, s->block_depth).matches(L))
-                                        : (s->kernel == 5 ? DecLay<256, 5>(s->d4, s->n_blocks, s->block_depth).matches(L) : DecLay<256, 3>(s->d4, s->n_blocks, s->block_depth).matches(L));
-        if (!same || L.total > 0x1fffffffL) return ESMI_ERR_UNSUPPORTED;
-    }
+    const DecInst* inst = dec_inst(s);
+    if (inst->blob_floats(s->d4, s->n_blocks, s->block_depth) > kDecBlobMaxFloats) return ESMI_ERR_UNSUPPORTED;
     p.d4 = s->d4; p.n_blocks = s->n_blocks; p.block_depth = s->block_depth; p.n_mel = s->n_mel;
     p.x = x; p.h0 = h0; p.cum = cum; p.mel_len = mel_len; p.lmax_dev = lmax_dev; p.lmax_host = lmax_host;
     p.apply_mask = apply_mask && mel_len; p.B = B; p.T = T; p.L_out = L_out; p.mel = mel;
@@ -195,11 +204,7 @@ static int mel_decoder_launch(const float* blob, const esmi_decoder_shape* s, co
         p.n_seg = (L_out + p.seg_len - 1) / p.seg_len;
     }
     dim3 grid((unsigned)(p.n_seg * ((B + 7) / 8) * 8)), block(kDecThreads);
-    // one translation unit per instantiation (tu_dec_<dx2>_<k>.hip): the kernel is by far the slowest thing to compile
-    if (s->dx2 == 128 && s->kernel == 5) return launch_mel_decoder_128_5(p, grid, st);
-    if (s->dx2 == 128 && s->kernel == 3) return launch_mel_decoder_128_3(p, grid, st);
-    if (s->dx2 == 256 && s->kernel == 5) return launch_mel_decoder_256_5(p, grid, st);
-    return launch_mel_decoder_256_3(p, grid, st);
+    return inst->launch(p, grid, st);
 }
 
 int esmi_mel_decoder_f32(const float* blob, const esmi_decoder_shape* s, const float* x, const float* h0,

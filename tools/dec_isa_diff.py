@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""Compare the decoder's generated machine code between two source trees (profiles/dec_refactor_isa.md).
+
+    tools/dec_isa_diff.py PARENT_TREE BRANCH_TREE [--out DIR] [--reuse-parent]
+
+Compiles the five decoder translation units for each library of __graft_entry__.VARIANTS to device assembly
+(FLAGS + the variant's defines + --cuda-device-only -S), replaces __hip_cuid_<hash> (derived from the output path) and reports per unit:
+"identical", or the second form: the kernels' resource metadata and the histogram of every mnemonic that is not scalar ALU / move.
+Exit status 0 when every unit is identical or passes the second form.
+"""
+import collections
+import os
+import re
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+UNITS = ("tu_dec_128_5", "tu_dec_128_3", "tu_dec_256_5", "tu_dec_256_3", "tu_decoder")
+META = (".vgpr_count", ".sgpr_count", ".sgpr_spill_count", ".vgpr_spill_count", ".private_segment_fixed_size", ".group_segment_fixed_size",
+        ".amdhsa_next_free_vgpr", ".amdhsa_next_free_sgpr")
+GATED = re.compile(r"^(v_|ds_|buffer_|global_|flat_|scratch_|s_barrier|s_waitcnt|s_load_|s_buffer_load_)")
+
+
+def listing(tree, out, lib, defines, unit, flags, reuse):
+    dst = os.path.join(out, lib.replace(".so", ""), unit + ".s")
+    os.makedirs(os.path.dirname(dst), exist_ok=True)
+    if not (reuse and os.path.exists(dst)):
+        src = os.path.join(tree, "efficientspeech_amd", "csrc", unit + ".hip")
+        subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + flags + defines + ["--cuda-device-only", "-S", src, "-o", dst])
+    return re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_X", open(dst).read())
+
+
+def facts(text):
+    """per kernel symbol: the metadata fields; for the unit: the mnemonic histogram"""
+    meta, hist, name = collections.defaultdict(dict), collections.Counter(), None
+    for line in text.splitlines():
+        s = line.strip()
+        m = re.match(r"\.amdhsa_kernel\s+(\S+)", s)
+        if m:
+            name = m.group(1)
+        m = re.match(r"\.name:\s+(\S+)", s)
+        if m:
+            name = m.group(1)
+        for k in META:
+            if s.startswith(k + " ") or s.startswith(k + ":"):
+                meta[name][k] = s.split()[-1]
+        if line.startswith("\t") and s and s[0] not in ".;" and not s.endswith(":"):
+            hist[s.split()[0]] += 1
+    return meta, hist
+
+
+def main():
+    args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] != "--out"]
+    parent, branch = os.path.abspath(args[0]), os.path.abspath(args[1])
+    out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else tempfile.mkdtemp(prefix="dec_isa_")
+    sys.path.insert(0, branch)
+    import __graft_entry__ as ge
+    jobs = [(tree, os.path.join(out, tag), lib, d, u, ge.FLAGS, tag == "parent" and "--reuse-parent" in sys.argv)
+            for tag, tree in (("parent", parent), ("branch", branch)) for lib, d in ge.VARIANTS.items() for u in UNITS]
+    with ThreadPoolExecutor(max_workers=min(len(jobs), 16, os.cpu_count() or 4)) as ex:
+        texts = list(ex.map(lambda j: listing(*j), jobs))
+    half, bad = len(jobs) // 2, 0
+    for (_, _, lib, _, unit, _, _), a, b in zip(jobs[:half], texts[:half], texts[half:]):
+        if a == b:
+            print(f"{lib:22s} {unit:14s} identical")
+            continue
+        (ma, ha), (mb, hb) = facts(a), facts(b)
+        dm = [(k, f, ma[k].get(f), mb.get(k, {}).get(f)) for k in ma for f in ma[k] if ma[k].get(f) != mb.get(k, {}).get(f)]
+        dh = [(m, ha[m], hb[m]) for m in sorted(set(ha) | set(hb)) if ha[m] != hb[m]]
+        gated = [d for d in dh if GATED.match(d[0])]
+        ok = not dm and not gated and set(ma) == set(mb)
+        bad += not ok
+        print(f"{lib:22s} {unit:14s} {'second form' if ok else 'DIFFERS'}: metadata {dm or 'equal'}; gated mnemonics {gated or 'equal'}; "
+              f"scalar ALU / move {[d for d in dh if not GATED.match(d[0])] or 'equal'}")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
