@@ -1,7 +1,10 @@
 """Operator-level checks of the training kernels (csrc/train_ops.h, esmi_train_*) against plain PyTorch fp32 ops on the same
 device, at sizes that exercise what the small reference fixture cannot: many row chunks in the two-stage reductions, weight
 tiles that are not multiples of 32, strided / transposed / depthwise convolutions, several heads.  (PyTorch is the checker
-here, as the numerics-test rule asks; the step-level parity is pinned to the reference fixture in test_train_step.py.)"""
+here, as the numerics-test rule asks; the step-level parity is pinned to the reference fixture in test_train_step.py.)
+The largest convolution here has 3,500 rows, all at precision 32: on the device that reaches `convgemm_kernel` and, for the one k = 1
+shape above 2,048 rows, `convgemm_dma_kernel<4, 1>` -- not the kernels of a benchmark-size step (`pwgemm_kernel` from 32,768 rows,
+`convgemm_dma_kernel<4, 2>`) and no `precision = 16` instantiation; those are test_train_gemm_at_size.py's."""
 import numpy as np
 import pytest
 import torch
