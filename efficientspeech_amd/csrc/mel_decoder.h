@@ -257,7 +257,7 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
     // STREAM: the k/2 input rows of every conv layer in front of the next chunk are carried: in LDS behind the tile (`carry_lds_layers`
     // slots), else in a global scratch row set of this workgroup (written and read back by the same thread, one chunk apart: no fence)
     float* const cws = STREAM && p.carry_ws ? p.carry_ws + ((long)seg * p.B + b) * p.ws_stride : nullptr;
-    float* const stat = reinterpret_cast<float*>(src + kDecRows);     // LNA: [2 exchanges][kDecRows][NS] x (sum, sum of squares)
+    float* const stat = reinterpret_cast<float*>(src + kDecRows);     // LNA: [2 exchanges][kDecRows][NS] x (sum, M2 about the slice's own mean)
     float* const cbuf = stat + (LNA ? 2 * kDecRows * NS * 2 : 0);     // [carry_lds_layers][PAD][DX2]
     float cnext = 0.0f;                      // the carried element of the NEXT conv layer, requested one phase ahead
     // BLOCK SKEW (round 6; DecWalk, dec_layout.h, has the arithmetic and the host derives the segments by it)
@@ -600,28 +600,38 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
         }
     };
     // ---- LNA (dx2 = 256): LayerNorm without the tile round trip.  After the K loop lane (i, h) of wave (mh, ns) holds, per row tile mt, row
-    // 64 mh + 32 mt + i x 32 NTW channels of the wave's column slice.  `stats_put`: the lane's sum and sum of squares, + its partner half
-    // (lane ^ 32), written as one (sum, sumsq) pair per (row, ns) -- ahead of the barrier the epilogue needs anyway (last reader of the
+    // 64 mh + 32 mt + i x 32 NTW channels of the wave's column slice.  `stats_put`: the lane's sum and squared deviations, + its partner half
+    // (lane ^ 32), written as one (sum, M2) pair per (row, ns) -- ahead of the barrier the epilogue needs anyway (last reader of the
     // operand planes); behind it every lane adds the row's four pairs (`stats_get`: two ds_read_b128), normalises its registers
     // (`ln_acc`: gain / shift of its own channels, read like the bias in tanh_acc) and stores the finished rows once (`store_ln`).
-    // One-pass variance E[x^2] - mean^2 on |x| <= 1 (tanh) or O(1) (block end) values: parity held at 1e-5 (tests).  Against the
-    // round-5 form: one barrier, 16 ds_write_b128 + 16 ds_read_b128 per thread and the row owners' DPP reductions less per layer.
+    // The variance is as accurate as a two-pass one: a lane pair knows the mean of ITS 64 channels after one swap32_f, takes the squared
+    // deviations about that local mean in registers and writes (sum, M2_local); `stats_get` combines the four slices pairwise,
+    // M2 = sum_l M2_l + n_l sum_l (mean_l - mean)^2 (Chan et al.).  (Until round 7 the pair was (sum, sum of squares) and the variance
+    // E[x^2] - mean^2: on rows with |mean| >> std -- saturated tanh rows of a trained model -- the cancellation cost up to 1.5e-2 of mel
+    // L-inf, tests/test_weight_profiles.py.)  Against the round-5 form: one barrier, 16 ds_write_b128 + 16 ds_read_b128 per thread and
+    // the row owners' DPP reductions less per layer.
     auto stats_put = [&](int buf) __attribute__((always_inline)) {
         typedef float f32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            float s1 = 0.0f, s2 = 0.0f;
+            float s1 = 0.0f, m2 = 0.0f;
+#pragma unroll
+            for (int t = 0; t < NTW; ++t) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s1 += acc[mt][t][r];
+            }
+            s1 += swap32_f(s1);
+            const float lmean = s1 * (1.0f / WCOLS);   // mean of the row's WCOLS channels in this column slice
 #pragma unroll
             for (int t = 0; t < NTW; ++t) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    s1 += acc[mt][t][r];
-                    s2 = fmaf(acc[mt][t][r], acc[mt][t][r], s2);
+                    const float d = acc[mt][t][r] - lmean;
+                    m2 = fmaf(d, d, m2);
                 }
             }
-            s1 += swap32_f(s1);
-            s2 += swap32_f(s2);
-            if (h == 0) *reinterpret_cast<f32x2*>(stat + opaque_i(((buf * kDecRows + 32 * MT * mh + i) * NS + ns) * 2) + 32 * mt * NS * 2) = f32x2{s1, s2};
+            m2 += swap32_f(m2);
+            if (h == 0) *reinterpret_cast<f32x2*>(stat + opaque_i(((buf * kDecRows + 32 * MT * mh + i) * NS + ns) * 2) + 32 * mt * NS * 2) = f32x2{s1, m2};
         }
     };
     auto stats_get = [&](int buf, float (&mean)[MT], float (&rstd)[MT]) __attribute__((always_inline)) {
@@ -629,9 +639,13 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const f32x4 a = *reinterpret_cast<const f32x4*>(sp + 32 * mt * NS * 2), b = *reinterpret_cast<const f32x4*>(sp + 32 * mt * NS * 2 + 4);
-            const float s1 = (a[0] + a[2]) + (b[0] + b[2]), s2 = (a[1] + a[3]) + (b[1] + b[3]);
+            const float s1 = (a[0] + a[2]) + (b[0] + b[2]);
             mean[mt] = s1 * (1.0f / DX2);
-            rstd[mt] = rsqrt_fast_f32(fmaxf(fmaf(-mean[mt], mean[mt], s2 * (1.0f / DX2)), 0.0f) + 1e-5f);
+            // slice means about the row mean: sum_l n_l (mean_l - mean)^2 with n_l = WCOLS, folded into the sum of the slices' M2
+            const float d0 = fmaf(a[0], 1.0f / WCOLS, -mean[mt]), d1 = fmaf(a[2], 1.0f / WCOLS, -mean[mt]);
+            const float d2 = fmaf(b[0], 1.0f / WCOLS, -mean[mt]), d3 = fmaf(b[2], 1.0f / WCOLS, -mean[mt]);
+            const float m2 = fmaf((float)WCOLS, fmaf(d0, d0, d1 * d1) + fmaf(d2, d2, d3 * d3), (a[1] + a[3]) + (b[1] + b[3]));
+            rstd[mt] = rsqrt_fast_f32(m2 * (1.0f / DX2) + 1e-5f);
         }
     };
     auto ln_acc = [&](const float* gain, const float* shift, const float (&mean)[MT], const float (&rstd)[MT]) __attribute__((always_inline)) {

@@ -199,9 +199,10 @@ class _HgCfg(C.Structure):
                 ("rb_dilations", (C.c_int * 3) * 8)]
 
 
-def hifigan(h, w: Weights, mel):
+def hifigan(h, w: Weights, mel, f32=False):
     """HiFi-GAN Generator.forward (hifigan/models.py:84-135) on a channels-last mel (B, L, n_mel) -> wav (B, L * hop).
-    `h`: efficientspeech_amd.hifigan.HifiGanConfig; `w`: Weights over the remove_weight_norm()-form state dict."""
+    `h`: efficientspeech_amd.hifigan.HifiGanConfig; `w`: Weights over the remove_weight_norm()-form state dict.
+    `f32`: the float-accumulator build, as for the other entry points."""
     mel = _f(mel)
     B, L, nm = mel.shape
     c = _HgCfg()
@@ -214,7 +215,7 @@ def hifigan(h, w: Weights, mel):
         for m, dd in enumerate(d):
             c.rb_dilations[j][m] = dd
     wav = np.empty((B, L * int(np.prod(h.upsample_rates))), np.float32)
-    L_ = lib()
+    L_ = lib(f32)
     L_.eso_hifigan.restype = C.c_int
     _chk(L_.eso_hifigan(C.byref(c), C.byref(w.c), B, L, _p(mel), _p(wav)), "hifigan")
     return wav

@@ -376,7 +376,8 @@ def test_large_batch_uses_other_kernels(nets):
 
 def test_exact_fp32_mfma_build():
     """The alternative build (mel-decoder contractions on v_mfma_f32_32x32x2_f32 instead of split 16-bit products) is the same
-    ABI; run two golden fixtures and the smoke check through it in a fresh interpreter (ESMI_LIB selects the library)."""
+    ABI; run two golden fixtures, one saturated-row decoder case on base ES (tests/test_weight_profiles.py) and the smoke check
+    through it in a fresh interpreter (ESMI_LIB selects the library)."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -392,6 +393,8 @@ def test_exact_fp32_mfma_build():
         "    g = np.load(os.path.join(%r, 'tests', 'golden', f))\n"
         "    net, cfg, sd = H.make_net('tiny', 'cuda', golden=g)\n"
         "    H.check_against_golden(net, g, 'cuda')\n"
+        "from tests import test_weight_profiles as WP\n"      # this build shares the dx2 = 256 LayerNorm on the accumulators
+        "WP.check_decoder('cuda', 'base', 'sat+3x0.3', 1, 40)\n"
         "import __graft_entry__ as ge; ge.smoke()\n" % (root, root))
     env = dict(os.environ, ESMI_LIB=lib)
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
