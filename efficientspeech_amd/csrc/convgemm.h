@@ -76,7 +76,18 @@ struct ConvGemmP {
     // kernels', i.e. results differ in the last bits with the row count that selects it: set by the training step only -- the
     // inference plans promise results that do not depend on how a batch is split
     int pw_ok;
+    // HiFi-GAN generator with per-utterance lengths (esmi_hifigan_generator_ragged_f32; convgemm_len_kernel / conv_to1_len_kernel only):
+    // (B) mel frames on the device.  Utterance b has conv_len_limit() = min(n_out, clamp(len[b], 0, len_max) * len_mul + len_add) output
+    // positions: a wave tile that starts at or behind it leaves at once, positions from it on are neither computed nor written, and a
+    // stride-1 convolution (n_in == n_out) reads its input rows from it on as zeros -- they may never have been written.  A
+    // ConvTranspose1d reads what its kept outputs need: the caller's margins (hg_margins, esmi_abi.hip) keep that inside the rows the
+    // stage before it wrote.  NULL: no limit
+    const int* len;
+    int len_max, len_mul, len_add;
 };
+__device__ __forceinline__ int conv_len_limit(const ConvGemmP& p, int b) {
+    return utterance_positions(p.len, b, p.len_max, p.len_mul, p.len_add, p.n_out);
+}
 // (s, 1/s) for a tensor whose largest magnitude has the bit pattern *absmax
 __device__ __forceinline__ void conv_pow2_scales(const float* absmax, float* s, float* inv) {
     const int bits = __builtin_bit_cast(int, absmax[0]);
@@ -122,8 +133,10 @@ __device__ __forceinline__ f32x4 conv_act_in(f32x4 v, const ConvGemmP& p, float 
 // Fused epilogue of the implicit-GEMM kernels, in the MFMA C/D layout (row = tile_row(r), col = n0 + 32*nt + (lane&31)):
 //   out = mask( post_relu( LN( act(acc * s + bias) + residual ) ) ), optional row-dot side output on the pre-LN value.
 template <int NT>
-__device__ __forceinline__ void convgemm_epilogue(f32x16 (&acc)[NT], const ConvGemmP& p, int b, int t0, int n0, int lane, int ts = 1, int flat_rows = 0) {
+__device__ __forceinline__ void convgemm_epilogue(f32x16 (&acc)[NT], const ConvGemmP& p, int b, int t0, int n0, int lane, int ts = 1, int flat_rows = 0,
+                                                  int t_lim = 0x7fffffff) {
     const int n_out = flat_rows ? flat_rows : p.n_out;   // (flat_rows: the caller's rows are b * n_out + t with b = 0)
+    const int t_end = t_lim < n_out ? t_lim : n_out;     // rows from here on are not written, their residual / accumulator not read (t_lim: ConvGemmP::len)
     const int i = lane & 31;
     const float out_s = (ESMI_CHAIN_SPLIT ? kF16WScaleInv : 1.0f) * conv_out_scale(p);
     int col[NT];
@@ -157,7 +170,7 @@ __device__ __forceinline__ void convgemm_epilogue(f32x16 (&acc)[NT], const ConvG
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int t = t0 + tile_row(r, lane) * ts;
-            if (t >= n_out) continue;
+            if (t >= t_end) continue;
             const long row = (long)b * n_out + t;
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
@@ -233,7 +246,7 @@ __device__ __forceinline__ void convgemm_epilogue(f32x16 (&acc)[NT], const ConvG
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int t = t0 + tile_row(r, lane) * ts;
-            if (t >= n_out) continue;
+            if (t >= t_end) continue;
             const long row = (long)b * n_out + t;
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
@@ -251,7 +264,7 @@ __device__ __forceinline__ void convgemm_epilogue(f32x16 (&acc)[NT], const ConvG
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int t = t0 + tile_row(r, lane) * ts;
-        if (t >= n_out) continue;
+        if (t >= t_end) continue;
         const long row = (long)b * n_out + t;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
@@ -263,8 +276,10 @@ __device__ __forceinline__ void convgemm_epilogue(f32x16 (&acc)[NT], const ConvG
     }
 }
 
-template <int NT, bool AMP = false>     // AMP: ConvGemmP::amp as a compile-time constant (a run-time branch in the K loop broke its software pipeline: base ES +35 %)
-__global__ __launch_bounds__(256) void convgemm_kernel(const ConvGemmP p) {
+// The kernel body.  AMP: ConvGemmP::amp as a compile-time constant (a run-time branch in the K loop broke its software pipeline: base
+// ES +35 %); LEN: ConvGemmP::len likewise (convgemm_len_kernel -- the plain kernels' machine code does not carry the limit)
+template <int NT, bool AMP, bool LEN>
+__device__ __forceinline__ void convgemm_body(const ConvGemmP& p) {
     const int lane = lane_id();
     // A strided ConvTranspose1d tile holds 32 positions of ONE phase (t mod stride): only the k/stride taps of that phase are
     // visited, instead of all k with (stride-1)/stride of the rows masked out of each (HiFi-GAN ups: k = 16, stride 8).
@@ -276,6 +291,11 @@ __global__ __launch_bounds__(256) void convgemm_kernel(const ConvGemmP p) {
     const int b = wt / tiles_per_b;
     const int rem = wt - b * tiles_per_b, phase = rem / tiles_per_phase;
     const int t0 = ((rem - phase * tiles_per_phase) << 5) * ts + phase;
+    int n_lim = p.n_out;                  // LEN: the utterance's positions at this stage
+    if constexpr (LEN) {
+        n_lim = conv_len_limit(p, b);
+        if (t0 >= n_lim) return;          // every position of the tile lies behind the utterance's end (wave-uniform)
+    }
     const int n0 = (int)blockIdx.y * (NT * 32);
     const int i = lane & 31, h = lane >> 5;
     const int t_out = t0 + i * ts;
@@ -290,10 +310,10 @@ __global__ __launch_bounds__(256) void convgemm_kernel(const ConvGemmP p) {
     for (int j = j_first; j < p.k; j += ts) {
         // which input row feeds output position t_out through tap j
         int ti;
-        bool ok = t_out < p.n_out;
+        bool ok = t_out < n_lim;
         if (p.mode == MODE_CONV) {
             ti = t_out * p.stride + j * (p.dil > 0 ? p.dil : 1) - p.pad;
-            ok = ok && ti >= 0 && ti < p.n_in;
+            ok = ok && ti >= 0 && ti < (LEN ? n_lim : p.n_in);   // (LEN: stride 1, n_in == n_out -- the launcher checks)
         } else {  // ConvTranspose1d: out[n*stride + j - pad] += in[n] * W[:, :, j]
             const int q = t_out + p.pad - j;
             ti = q / p.stride;
@@ -435,17 +455,21 @@ __global__ __launch_bounds__(256) void convgemm_kernel(const ConvGemmP p) {
 #endif
     }
 
-    convgemm_epilogue<NT>(acc, p, b, t0, n0, lane, ts);
+    if constexpr (LEN) convgemm_epilogue<NT>(acc, p, b, t0, n0, lane, ts, 0, n_lim);
+    else convgemm_epilogue<NT>(acc, p, b, t0, n0, lane, ts);
 }
+
+template <int NT, bool AMP = false>
+__global__ __launch_bounds__(256) void convgemm_kernel(const ConvGemmP p) { convgemm_body<NT, AMP, false>(p); }
+// the same with ConvGemmP::len applied (the HiFi-GAN stages of at most 64 channels in a length-aware call)
+template <int NT>
+__global__ __launch_bounds__(256) void convgemm_len_kernel(const ConvGemmP p) { convgemm_body<NT, false, true>(p); }
 
 
 // ---- a convolution down to ONE output channel (HiFi-GAN conv_post, hifigan/models.py:123-125: 8..32 channels -> 1, k = 7,
 // tanh): 1/32 of an MFMA tile's columns would be used, and the op is a plain read of the input (C floats per sample).
 // One thread per output position, fp32 FMAs in tap-major / channel order; neighbouring threads share their rows in L1.
-static __global__ __launch_bounds__(256) void conv_to1_kernel(const ConvGemmP p) {
-    const long q = (long)blockIdx.x * 256 + threadIdx.x;
-    if (q >= (long)p.B * p.n_out) return;
-    const int b = (int)(q / p.n_out), t = (int)(q - (long)b * p.n_out);
+__device__ __forceinline__ float conv_to1_value(const ConvGemmP& p, int b, int t) {
     const int dil = p.dil > 0 ? p.dil : 1;
     const float in_s = conv_in_scale(p);
     float acc = 0.0f;
@@ -462,8 +486,28 @@ static __global__ __launch_bounds__(256) void conv_to1_kernel(const ConvGemmP p)
     }
     float v = apply_act(acc * conv_out_scale(p) + (p.bias ? p.bias[0] : 0.0f), p.act);
     if (p.post_relu) v = fmaxf(v, 0.0f);
+    return v;
+}
+static __global__ __launch_bounds__(256) void conv_to1_kernel(const ConvGemmP p) {
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= (long)p.B * p.n_out) return;
+    const int b = (int)(q / p.n_out), t = (int)(q - (long)b * p.n_out);
+    const float v = conv_to1_value(p, b, t);
     float* o = p.out + ((long)b * p.n_out + t) * p.ldo + p.o_coff;
     *o = p.accum ? *o + v : v;
+}
+// ... with per-utterance lengths (ConvGemmP::len; HiFi-GAN conv_post of a length-aware call): EVERY sample of the output is written --
+// the utterance's own as above, the ones from conv_len_limit() on as exact zeros without computing them -- to the float plane, to an
+// int16 PCM plane (B, n_out), or to both (either may be NULL).  PCM = trunc(clamp(v * 32768, -32768, 32767)): the reference's host side
+// does `(wav * 32768).astype("int16")` (utils/tools.py:96-103), which WRAPS +1.0f (tanh saturated) to -32768; clamping to 32767 is
+// the deliberate difference.
+static __global__ __launch_bounds__(256) void conv_to1_len_kernel(const ConvGemmP p, short* pcm) {
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= (long)p.B * p.n_out) return;
+    const int b = (int)(q / p.n_out), t = (int)(q - (long)b * p.n_out);
+    const float v = t < conv_len_limit(p, b) ? conv_to1_value(p, b, t) : 0.0f;
+    if (p.out) p.out[((long)b * p.n_out + t) * p.ldo + p.o_coff] = v;
+    if (pcm) pcm[q] = (short)(int)fminf(fmaxf(v * 32768.0f, -32768.0f), 32767.0f);
 }
 
 #if ESMI_CHAIN_SPLIT

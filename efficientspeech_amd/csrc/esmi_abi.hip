@@ -773,6 +773,37 @@ int hg_plan(const esmi_hifigan_shape* s, int B, int L, HgPlan* o) {
     return ESMI_OK;
 }
 
+// one-sided receptive field of ResBlock j of a stage: sum((k - 1) / 2 . dilation) over its convolutions
+int rb_halo(const esmi_hifigan_shape* s, int j) {
+    const int nconv = s->resblock == 1 ? 3 : 2, half = (s->rb_kernels[j] - 1) / 2;
+    int halo = 0;
+    for (int m = 0; m < nconv; ++m) halo += half * s->rb_dilations[j * 3 + m] + (s->resblock == 1 ? half : 0);
+    return halo;
+}
+// Length-aware call: how far behind an utterance's last mel frame each stage still has to be right for every KEPT sample (t < len . hop)
+// to come out as in the full run -- the one-sided receptive field from that stage to the waveform, walked backwards: conv_post reads 3
+// positions ahead; the ResBlocks of a stage the largest halo among them (one margin per stage: out (+)= block(x) then accumulates
+// over the same rows for every block); ConvTranspose1d(k, u, pad (k - u) / 2) output t reads inputs up to floor((t + pad) / u), so m
+// positions behind len . rate need ceil((m + pad) / u) behind len . rate / u; conv_pre reads 3 frames ahead.  Stage i (the output of
+// ups[i] and its ResBlocks) then covers n_eff = min(n, len . mul[i] + add[i]) positions.
+// hifigan.ragged_margins (Python; tools/bench_vocoder.py's ideal ratio) is the same walk written a second time: keep the two in step.
+// This copy is bound by tests/test_vocoder_ragged.py on the device -- too short fails the bit-for-bit test on NaN-filled workspaces, and
+// the margin test overwrites the mel from the frames the PYTHON copy claims on -- for v1 / v2 / v3; other shapes have no such test.
+struct HgMargins { int mul[ESMI_HIFIGAN_MAX_UP], add[ESMI_HIFIGAN_MAX_UP]; };
+HgMargins hg_margins(const esmi_hifigan_shape* s) {
+    HgMargins g = {};
+    int rate = 1, need = 3;
+    for (int i = 0; i < s->n_up; ++i) g.mul[i] = rate *= s->up_rates[i];
+    for (int i = s->n_up - 1; i >= 0; --i) {
+        int halo = 0;
+        for (int j = 0; j < s->n_kernels; ++j) halo = rb_halo(s, j) > halo ? rb_halo(s, j) : halo;
+        g.add[i] = need + halo;
+        const int u = s->up_rates[i], pad = (s->up_kernels[i] - u) / 2;
+        need = (g.add[i] + pad + u - 1) / u;
+    }
+    return g;
+}
+
 bool resblock_fused_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, int rb, int c, int k, int n, ResblockP* o) {
 #if !ESMI_CHAIN_SPLIT
     return false;   // the exact-fp32 build keeps the per-conv fp32-MFMA launches
@@ -780,16 +811,15 @@ bool resblock_fused_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* 
     if ((c != 8 && c != 16 && c != 32 && c != 64) || (k != 3 && k != 7 && k != 11)) return false;   // the instantiations
     const int nconv = s->resblock == 1 ? 3 : 2, j = rb % s->n_kernels;
     ResblockP p = {};
-    int halo = 0, q = 0;
+    const int halo = rb_halo(s, j);
+    int q = 0;
     for (int m = 0; m < nconv; ++m) {
         const int d = s->rb_dilations[j * 3 + m];
         if (d < 1 || !w->rb_wp1[rb * 3 + m] || !w->rb_b1[rb * 3 + m]) return false;
         p.conv[q++] = RbConv{static_cast<const unsigned*>(w->rb_wp1[rb * 3 + m]), w->rb_b1[rb * 3 + m], d, s->resblock == 1 ? 0 : 1};
-        halo += (k - 1) / 2 * d;
         if (s->resblock == 1) {
             if (!w->rb_wp2[rb * 3 + m] || !w->rb_b2[rb * 3 + m]) return false;
             p.conv[q++] = RbConv{static_cast<const unsigned*>(w->rb_wp2[rb * 3 + m]), w->rb_b2[rb * 3 + m], 1, 1};
-            halo += (k - 1) / 2;
         }
     }
     const int r_max = c == 64 ? 256 : 512;    // 8 waves = 8 (row pair, 32-channel tile) items; LDS <= 80 KB: two workgroups per CU
@@ -801,19 +831,19 @@ bool resblock_fused_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* 
     *o = p;
     return true;
 }
-}  // namespace
-
-size_t esmi_hifigan_workspace_bytes(const esmi_hifigan_shape* s, int B, int L) {
-    HgPlan o;
-    return hg_plan(s, B, L, &o) == ESMI_OK ? 4 * o.buf : 0;
-}
-
-int esmi_hifigan_generator_f32(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
-                               float* wav, void* workspace, size_t workspace_bytes, esmi_stream_t stream) {
+// The generator behind both entry points.  mel_len == nullptr: the plain call.  Otherwise (include/esmi.h) conv_pre and the stages of
+// more than 64 channels compute every frame -- their convolutions run on the kernels that tile flat rows across utterances --, and from
+// the first stage of at most 64 channels on every launch (ConvTranspose1d, the ResBlocks fused or conv by conv, conv_post) carries the
+// stage's limit from hg_margins: a limited stage reads only rows the stage before it wrote, full or limited.  What that leaves
+// unlimited, by multiply-adds (n . c^2 per stage): v2 (64 / 32 / 16 / 8 channels) conv_pre alone, a few per cent; v3 its 128-channel
+// stage, about a fifth; v1 its 256- and 128-channel stages, about two thirds -- on v1 most of the padded work is still done.
+int hifigan_generator(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
+                      const int32_t* mel_len, float* wav, int16_t* pcm, void* workspace, size_t workspace_bytes, esmi_stream_t stream) {
     HgPlan o;
     int rc = hg_plan(s, B, L, &o);
     if (rc) return rc;
-    if (!w || !mel || !wav || !workspace) return ESMI_ERR_ARG;
+    if (!w || !mel || (!wav && !pcm) || !workspace) return ESMI_ERR_ARG;
+    const HgMargins mg = hg_margins(s);
     if (workspace_bytes < 4 * o.buf) return ESMI_ERR_WORKSPACE;
     hipStream_t st = S(stream);
     float* bufs[4];
@@ -831,12 +861,15 @@ int esmi_hifigan_generator_f32(const esmi_hifigan_weights* w, const esmi_hifigan
     for (int i = 0; i < s->n_up; ++i) {
         const int u = s->up_rates[i], k = s->up_kernels[i], co = c / 2;
         const long no = n * u;
+        const bool lim = mel_len && co <= 64;   // this stage runs under the per-utterance limit (and so does every later one)
+        auto limit = [&](ConvGemmP& q) { if (lim) { q.len = mel_len; q.len_max = L; q.len_mul = mg.mul[i]; q.len_add = mg.add[i]; } };
         // x = ups[i](leaky_relu(x, 0.1)), models.py:114-115: ConvTranspose1d(c, c/2, k, u, padding (k-u)//2)
         p = conv_defaults();
         p.mode = MODE_CONVT; p.k = k; p.stride = u; p.pad = (k - u) / 2;
         p.B = B; p.n_in = (int)n; p.c_in = c; p.n_out = (int)no; p.c_out = co;
         p.A = x; p.lda = c; p.W = w->up_w[i]; p.bias = w->up_b[i]; p.out = y; p.ldo = co;
         p.act_in = 1; p.act_in_slope = slope; p.a_scale = in_scale;
+        limit(p);
         if (!p.W || !p.bias) return ESMI_ERR_ARG;
         if ((rc = launch_convgemm(p, st))) return rc;
         n = no; c = co;
@@ -846,6 +879,7 @@ int esmi_hifigan_generator_f32(const esmi_hifigan_weights* w, const esmi_hifigan
             ResblockP fp;
             if (resblock_fused_ok(w, s, rb, c, kk, (int)n, &fp)) {   // the whole block on an LDS-resident window: y -> x (+)=
                 fp.x = y; fp.out = x; fp.B = B; fp.accum = j > 0; fp.slope = slope;
+                if (lim) { fp.len = mel_len; fp.len_max = L; fp.len_mul = mg.mul[i]; fp.len_add = mg.add[i]; }
                 if ((rc = launch_resblock(fp, c, st))) return rc;
                 continue;
             }
@@ -861,6 +895,7 @@ int esmi_hifigan_generator_f32(const esmi_hifigan_weights* w, const esmi_hifigan
                     p.B = B; p.n_in = (int)n; p.c_in = c; p.n_out = (int)n; p.c_out = c; p.k = kk; p.dil = d; p.pad = (kk * d - d) / 2;
                     p.A = cur; p.lda = c; p.W = w->rb_w1[rb * 3 + m]; p.bias = w->rb_b1[rb * 3 + m]; p.out = t; p.ldo = c;
                     p.act_in = 1; p.act_in_slope = slope;
+                    limit(p);
                     if (!p.W || !p.bias) return ESMI_ERR_ARG;
                     if ((rc = launch_convgemm(p, st))) return rc;
                     p = conv_defaults();
@@ -869,6 +904,7 @@ int esmi_hifigan_generator_f32(const esmi_hifigan_weights* w, const esmi_hifigan
                     p.res = cur; p.ldr = c;
                     p.out = last ? x : r; p.ldo = c; p.accum = last && j > 0;
                     p.act_in = 1; p.act_in_slope = slope;
+                    limit(p);
                     if (!p.W || !p.bias) return ESMI_ERR_ARG;
                     if ((rc = launch_convgemm(p, st))) return rc;
                     cur = r;
@@ -879,6 +915,7 @@ int esmi_hifigan_generator_f32(const esmi_hifigan_weights* w, const esmi_hifigan
                     p.A = cur; p.lda = c; p.W = w->rb_w1[rb * 3 + m]; p.bias = w->rb_b1[rb * 3 + m];
                     p.res = cur; p.ldr = c; p.out = dst; p.ldo = c; p.accum = last && j > 0;
                     p.act_in = 1; p.act_in_slope = slope;
+                    limit(p);
                     if (!p.W || !p.bias) return ESMI_ERR_ARG;
                     if ((rc = launch_convgemm(p, st))) return rc;
                     cur = dst;
@@ -893,7 +930,28 @@ int esmi_hifigan_generator_f32(const esmi_hifigan_weights* w, const esmi_hifigan
     p.A = x; p.lda = c; p.W = w->post_w; p.bias = w->post_b; p.out = wav; p.ldo = 1; p.act = ACT_TANH;
     p.act_in = 1; p.act_in_slope = 0.01f; p.a_scale = in_scale;
     if (!p.W || !p.bias) return ESMI_ERR_ARG;
-    return launch_convgemm(p, st);
+    if (!mel_len) return launch_convgemm(p, st);
+    // every sample is written: the utterance's own, then exact zeros from len . hop on (no margin: these are the kept samples themselves)
+    p.len = mel_len; p.len_max = L; p.len_mul = (int)(n / L); p.len_add = 0;
+    return launch_conv_to1_len(p, pcm, st);
+}
+}  // namespace
+
+size_t esmi_hifigan_workspace_bytes(const esmi_hifigan_shape* s, int B, int L) {
+    HgPlan o;
+    return hg_plan(s, B, L, &o) == ESMI_OK ? 4 * o.buf : 0;
+}
+
+int esmi_hifigan_generator_f32(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
+                               float* wav, void* workspace, size_t workspace_bytes, esmi_stream_t stream) {
+    return hifigan_generator(w, s, mel, B, L, nullptr, wav, nullptr, workspace, workspace_bytes, stream);
+}
+
+int esmi_hifigan_generator_ragged_f32(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
+                                      const int32_t* mel_len, float* wav, int16_t* pcm, void* workspace, size_t workspace_bytes,
+                                      esmi_stream_t stream) {
+    if (!mel_len) return ESMI_ERR_ARG;
+    return hifigan_generator(w, s, mel, B, L, mel_len, wav, pcm, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------ whole forward behind one call

@@ -203,6 +203,16 @@ __device__ __forceinline__ void layernorm_tile_regs(f32x16 (&v)[NT], const float
 // loop-invariant VGPR (measured: ~100 address registers in the mel decoder, 80+ of them spilled at a 128-VGPR budget), and
 // instruction selection can then no longer fold the constants into the 16-bit DS offset field.
 
+// Positions of utterance b at a stage of a length-aware HiFi-GAN call: min(n, clamp(len[b], 0, len_max) * mul + add) -- its mel frames
+// times the stage's up-sampling rate plus the stage's margin (esmi_abi.hip, hg_margins).  The ONE place the limit is formed: the
+// ConvTranspose1d, the ResBlocks (one launch or conv by conv) and conv_post of a stage must agree on it to the position.
+__device__ __forceinline__ int utterance_positions(const int* len, int b, int len_max, int mul, int add, int n) {
+    int l = len[b];
+    l = l < 0 ? 0 : (l > len_max ? len_max : l);
+    const long e = (long)l * mul + add;
+    return e < n ? (int)e : n;
+}
+
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ f32x4 zero4() { f32x4 z = {0.f, 0.f, 0.f, 0.f}; return z; }
 __device__ __forceinline__ f32x16 zero16() {

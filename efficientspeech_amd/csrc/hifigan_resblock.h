@@ -24,6 +24,14 @@
 // done), is written, and a second barrier publishes it -- half the LDS of a ping-pong pair, so two workgroups share a CU and
 // one's K loop (matrix pipe) runs under the other's epilogue (VALU) and barriers.
 //
+// Per-utterance lengths (ResblockP::len, esmi_hifigan_generator_ragged_f32): utterance b ends at n_eff[b] = min(n, clamp(len[b], 0,
+// len_max) . len_mul + len_add) -- its mel frames times the stage's cumulative up-sampling rate plus the one-sided receptive field from
+// this stage's input to the waveform (host: hg_margins, esmi_abi.hip).  A workgroup whose output window starts at or behind n_eff[b]
+// returns at once (a scalar branch on blockIdx; the grid stays B . tiles_per_b and the lengths stay on the device); a surviving window
+// treats positions >= n_eff[b] exactly as positions >= n: they load as zeros and `inside` is false.  So no surviving workgroup reads a
+// row a skipped one would have written, and -- the window grid depends on n only -- every sample inside the receptive-field margin
+// goes through the same MFMA sequence as in the full run: bit-identical.  len == nullptr: n_eff = n, today's kernel.
+//
 // Work split: 8 waves; wave = (pair of 32-row tiles, 32-channel M tile).  C < 32 pads M with zero weight rows (the MFMA
 // work of the padding is wasted but the pipe is otherwise idle: these stages are the memory-bound ones).
 #pragma once
@@ -45,7 +53,13 @@ struct ResblockP {
     int B, n, k, n_conv, R, TL, halo, accum, tiles_per_b;
     float slope;
     RbConv conv[kRbMaxConv];
+    const int* len;       // (B) mel frames per utterance, device memory; nullptr: every utterance is n positions long
+    int len_max, len_mul, len_add;
 };
+// positions of utterance b that exist at this stage: rows at and behind it are zeros to every conv of the chain and are not written
+__device__ __forceinline__ int rb_n_eff(const ResblockP& p, int b) {
+    return p.len ? utterance_positions(p.len, b, p.len_max, p.len_mul, p.len_add, p.n) : p.n;
+}
 
 // per plane.  C >= 32 (32x32x16 tiles: lane = position, 32 consecutive rows per read): 16 pad bytes make the 16-byte reads
 // conflict-free; C <= 16 (16x16x32 tiles: 16 consecutive rows, the k-blocks of a lane group 16 bytes or one tap apart): unpadded
@@ -130,6 +144,8 @@ __global__ __launch_bounds__(64 * kRbWaves, kRbWps) void hifigan_resblock_kernel
     const bool active = pair * 64 < p.R;
     const int b = (int)blockIdx.x / p.tiles_per_b;
     const int t0 = ((int)blockIdx.x - b * p.tiles_per_b) * p.TL - p.halo;   // sequence position of window row 0
+    const int n_eff = rb_n_eff(p, b);
+    if (t0 + p.halo >= n_eff) return;             // the whole output window lies behind the utterance's end (workgroup-uniform)
     const int plane = p.R * RS;
     const int row0 = 64 * pair + i;
     const long wlane = (long)(mt * STEPS) * 512 + lane * 4;
@@ -182,7 +198,7 @@ __global__ __launch_bounds__(64 * kRbWaves, kRbWps) void hifigan_resblock_kernel
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
             const int row = row0 + 32 * tt, pos = t0 + row;
-            inside[tt] = pos >= 0 && pos < p.n;
+            inside[tt] = pos >= 0 && pos < n_eff;
             const float* src = p.x + ((long)b * p.n + (inside[tt] ? pos : 0)) * C + 32 * mt + 4 * h;
 #pragma unroll
             for (int g = 0; g < CG; ++g) {
@@ -274,6 +290,8 @@ __global__ __launch_bounds__(64 * kRbWaves, kRbWps) void hifigan_resblock16_kern
     const bool active = w * 64 < p.R, chan_ok = 4 * kb < C;      // C = 8: k-blocks 2, 3 hold the zero rows of the M tile
     const int b = (int)blockIdx.x / p.tiles_per_b;
     const int t0 = ((int)blockIdx.x - b * p.tiles_per_b) * p.TL - p.halo;
+    const int n_eff = rb_n_eff(p, b);
+    if (t0 + p.halo >= n_eff) return;             // the whole output window lies behind the utterance's end (workgroup-uniform)
     const int plane = p.R * RS;
     const int row0 = 64 * w + n;
 
@@ -309,7 +327,7 @@ __global__ __launch_bounds__(64 * kRbWaves, kRbWps) void hifigan_resblock16_kern
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
             const int row = row0 + 16 * nt, pos = t0 + row;
-            inside[nt] = pos >= 0 && pos < p.n;
+            inside[nt] = pos >= 0 && pos < n_eff;
             xres[nt] = (inside[nt] && chan_ok) ? ld4(p.x + ((long)b * p.n + pos) * C + 4 * kb) : zero4();
             if (chan_ok) put_planes(row, split4(xres[nt]));
         }

@@ -58,6 +58,7 @@ inline unsigned grid1d(long n, int block = 256) { return (unsigned)((n + block -
 // tu_convgemm.hip
 ConvGemmP conv_defaults();
 int launch_convgemm(ConvGemmP p, hipStream_t st);
+int launch_conv_to1_len(ConvGemmP p, int16_t* pcm, hipStream_t st);   // ConvGemmP::len set: zeros behind each utterance's end; float and / or int16 plane
 // tu_attention.hip
 int launch_attn(const AttnP& p, hipStream_t st);
 // tu_enc_merge.hip / tu_enc_block.hip / tu_enc_attn_ffn.hip / tu_enc_fuse_va.hip (rounds 1-4: the 32-row wave-chain kernels).  Every

@@ -35,9 +35,22 @@ int launch_convgemm(ConvGemmP p, hipStream_t st) {
         if (!p.table || (p.ld_table & 3) || !aligned16(p.table)) return ESMI_ERR_ARG;
     } else if (!p.A || (p.lda & 3) || (p.a_coff & 3) || !aligned16(p.A)) return ESMI_ERR_ARG;
     const bool full_row = p.ln_g || p.dot_out;
-    if (p.c_out == 1 && p.mode == MODE_CONV && p.stride == 1 && !p.ids && !full_row && !p.res && !p.rowmask && p.out) {
+    if (p.c_out == 1 && p.mode == MODE_CONV && p.stride == 1 && !p.ids && !full_row && !p.res && !p.rowmask && p.out && !p.len) {
         const long n = (long)p.B * p.n_out;
         ESMI_LAUNCH(conv_to1_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
+        return launch_status();
+    }
+    if (p.len) {
+        // per-utterance lengths (HiFi-GAN stages of a length-aware call): the streaming kernel's tiles never span utterances, so the
+        // limit is one scalar per wave; the LDS-staged kernels below tile flat rows across utterances and do not take it
+        if (full_row || p.ids || p.amp || p.rowmask || p.io_scale || p.len_mul < 1 || p.len_add < 0 ||
+            p.c_out > 64 || (p.mode == MODE_CONV && (p.stride != 1 || p.n_in != p.n_out)))   // (c_out <= 64: what the generator limits)
+            return ESMI_ERR_UNSUPPORTED;
+        const int nt = p.c_out > 32 ? 2 : 1;
+        const int tiles = p.B * convgemm_tiles_per_phase(p) * convgemm_row_stride(p);
+        const dim3 grid((tiles + 3) / 4, (p.c_out + 32 * nt - 1) / (32 * nt)), block(256);
+        if (nt == 1) { ESMI_LAUNCH((convgemm_len_kernel<1>), grid, block, 0, st, p); }
+        else { ESMI_LAUNCH((convgemm_len_kernel<2>), grid, block, 0, st, p); }
         return launch_status();
     }
     int nt;
@@ -142,6 +155,16 @@ int launch_convgemm(ConvGemmP p, hipStream_t st) {
             default: return ESMI_ERR_UNSUPPORTED;
         }
     }
+    return launch_status();
+}
+
+// conv_post of a length-aware HiFi-GAN call: a convolution down to one channel that writes every sample -- zeros behind each utterance's
+// end -- as float (p.out), int16 PCM (pcm), or both
+int launch_conv_to1_len(ConvGemmP p, int16_t* pcm, hipStream_t st) {
+    if ((p.c_in & 3) || p.c_in <= 0 || p.c_out != 1 || p.n_out <= 0 || p.B <= 0 || p.n_in != p.n_out || p.mode != MODE_CONV || p.stride != 1) return ESMI_ERR_ARG;
+    if (!p.W || !aligned16(p.W) || !p.A || (p.lda & 3) || (p.a_coff & 3) || !aligned16(p.A) || !p.len || (!p.out && !pcm) || p.accum) return ESMI_ERR_ARG;
+    const long n = (long)p.B * p.n_out;
+    ESMI_LAUNCH(conv_to1_len_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, reinterpret_cast<short*>(pcm));
     return launch_status();
 }
 

@@ -176,10 +176,19 @@ class Generator(_PackedModule):
         return self._cache.get(lambda: list(self.parameters()), build)
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x):
-        """x: mel (B, num_mels, L) as the reference takes it -> wav (B, 1, L * hop)."""
+    def forward(self, x, lengths=None, pcm16=False):
+        """x: mel (B, num_mels, L) as the reference takes it -> wav (B, 1, L * hop).
+
+        `lengths`: int tensor (B,) on the device, the mel frames of each utterance (`Phoneme2Mel`'s `mel_len` as it is: no host
+        synchronisation).  The stages of at most 64 channels (all of v2; the last two of v1 and v3) then do no work for frames no
+        kept sample can depend on, and the samples from
+        `lengths[b] * hop` on are exactly zero; the kept samples are bit for bit those of `forward(x)`.  `pcm16`: int16 PCM
+        (trunc(clamp(wav * 32768, -32768, 32767))) instead of float.  `lengths=None`, `pcm16=False`: the plain call; `pcm16=True` without
+        lengths takes every utterance as L frames long."""
         with _on_device_of(self.conv_post.weight):
-            return self._forward(x)
+            if lengths is None and not pcm16:
+                return self._forward(x)
+            return self._forward_ragged(x, lengths, pcm16)
 
     def _forward(self, x):
         lib, stream = networks._runtime(self.conv_post.weight)
@@ -194,6 +203,44 @@ class Generator(_PackedModule):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=mel.device)
         lib.esmi_hifigan_generator_f32(C.byref(w), C.byref(s), _ptr(mel), B, L, _ptr(wav), _ptr(ws), nbytes, stream)
         return wav
+
+    def _forward_ragged(self, x, lengths, pcm16):
+        lib, stream = networks._runtime(self.conv_post.weight)
+        mel = _f32(x.transpose(1, 2))
+        B, L, nm = mel.shape
+        assert nm == self.h.num_mels, f"expected {self.h.num_mels} mel channels, got {nm}"
+        if lengths is None:
+            lengths = torch.full((B,), L, dtype=torch.int32, device=mel.device)
+        assert lengths.shape == (B,) and lengths.device == mel.device and not lengths.is_floating_point(), "lengths: int tensor (B,) on the mel's device"
+        lengths = lengths.to(torch.int32).contiguous()       # (a device-side cast when mel_len is not int32 already: no sync)
+        out = torch.empty((B, 1, L * self.h.hop), dtype=torch.int16 if pcm16 else torch.float32, device=mel.device)
+        if B == 0 or L == 0:
+            return out
+        w, s, _keep = self._packed(lib, stream)
+        nbytes = lib.esmi_hifigan_workspace_bytes(C.byref(s), B, L)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=mel.device)
+        lib.esmi_hifigan_generator_ragged_f32(C.byref(w), C.byref(s), _ptr(mel), B, L, _ptr(lengths), None if pcm16 else _ptr(out),
+                                              _ptr(out) if pcm16 else None, _ptr(ws), nbytes, stream)
+        return out
+
+
+def ragged_margins(h: HifiGanConfig):
+    """The one-sided receptive field of the length-aware generator, walked backwards from the waveform exactly as the library's host
+    side does (esmi_abi.hip, hg_margins): -> (per stage i the positions behind `len * rate_i` that stage computes, mel frames behind
+    `len` that can reach a kept sample).  conv_post adds 3; a stage's ResBlocks add the largest halo among them; a
+    ConvTranspose1d(k, u, pad (k - u) / 2) maps a need of m output positions to ceil((m + pad) / u) inputs; conv_pre adds 3 frames.
+
+    A second copy of the C walk, not a binding to it: keep the two in step.  tests/test_vocoder_ragged.py pins this copy's values for
+    v1 / v2 / v3 on the host and, on the device, checks that the library reads nothing that matters behind the frames this copy claims;
+    for other generator shapes nothing ties the two together."""
+    per_conv = 2 if h.resblock == "1" else 1
+    halos = [sum((k - 1) // 2 * d + ((k - 1) // 2 if per_conv == 2 else 0) for d in dil)
+             for k, dil in zip(h.resblock_kernel_sizes, h.resblock_dilation_sizes)]
+    need, adds = 3, []
+    for u, k in reversed(list(zip(h.upsample_rates, h.upsample_kernel_sizes))):
+        adds.append(need + max(halos))
+        need = -(-(adds[-1] + (k - u) // 2) // u)
+    return adds[::-1], need + 3
 
 
 # ---------------------------------------------------------------------- checkpoints

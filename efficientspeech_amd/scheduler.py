@@ -6,6 +6,9 @@ utterances it is batched with.  `BucketedSynthesizer` sorts requests by length a
 `max_batch` utterances whose lengths fall into one bucket of `granularity` phonemes: granularity 1 never pads (only
 equal-length utterances share a batch), a larger one trades a bounded amount of padding (< granularity phonemes per
 utterance) for fuller batches.  Each batch is one `Phoneme2Mel` forward; results come back in request order.
+
+With a `vocoder` (the HIP `hifigan.Generator`) each batch also goes through the length-aware generator -- `mel_len` handed over on
+the device, no work for the frames behind an utterance's end in the stages of at most 64 channels -- and every request gets its waveform trimmed to `mel_len * hop`.
 """
 import numpy as np
 import torch
@@ -14,9 +17,10 @@ from .networks import get_mask_from_lengths
 
 
 class BucketedSynthesizer:
-    def __init__(self, net, max_batch=256, granularity=8, pad_id=0):
+    def __init__(self, net, max_batch=256, granularity=8, pad_id=0, vocoder=None):
         assert max_batch >= 1 and granularity >= 1
         self.net, self.max_batch, self.granularity, self.pad_id = net, int(max_batch), int(granularity), int(pad_id)
+        self.vocoder = vocoder
 
     def plan(self, lengths):
         """-> list of (request indices, padded length T) covering every request once, longest bucket first."""
@@ -44,7 +48,8 @@ class BucketedSynthesizer:
 
     @torch.no_grad()
     def __call__(self, sequences, extra=None):
-        """sequences: list of 1-D integer phoneme id sequences.  -> list (request order) of (mel (L_i, n_mel), duration (T_i,)).
+        """sequences: list of 1-D integer phoneme id sequences.  -> list (request order) of (mel (L_i, n_mel), duration (T_i,)), or
+        with a vocoder of (wav (L_i * hop,), mel (L_i, n_mel), duration (T_i,)).
         `extra(indices, T)` may return additional input-dict entries for a batch (e.g. forced durations)."""
         dev = self.net.decoder.mel_linear.weight.device
         lengths = [int(len(s)) for s in sequences]
@@ -59,7 +64,13 @@ class BucketedSynthesizer:
             if extra is not None:
                 x.update(extra(idx, T))
             mel, mel_len, dur = self.net(x)
+            wav = None
+            if self.vocoder is not None and mel.shape[1] > 0:      # (launched before the lengths are read back)
+                wav = self.vocoder(mel.transpose(1, 2), lengths=mel_len)[:, 0]
             ml = mel_len.cpu().numpy()
             for r, i in enumerate(idx):
                 out[i] = (mel[r, :int(ml[r])], dur[r, :lengths[i], 0])
+                if self.vocoder is not None:
+                    hop = self.vocoder.h.hop
+                    out[i] = ((wav[r, :int(ml[r]) * hop] if wav is not None else mel.new_zeros((0,))),) + out[i]
         return out

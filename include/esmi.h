@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ESMI_VERSION 501 /* 0.5.1: esmi_train_conv_ln_fwd_f32 (an addition; nothing else changed shape).  0.5.0 (round 5): esmi_mel_decoder_clock_probe;
+#define ESMI_VERSION 501 /* 0.5.1: esmi_train_conv_ln_fwd_f32, then esmi_hifigan_generator_ragged_f32 (additions; nothing else changed shape).  0.5.0 (round 5): esmi_mel_decoder_clock_probe;
                             0.4.0: esmi_decoder_head.proj_w (the decoder's first stage at phoneme rate for every model size:
                           * esmi_decoder_head_f32).  0.3.0: training entry points changed shape (esmi_conv_desc: act / packed_fwd / packed_grad; LayerNorm with
                           * residual / row mask / activation arguments; esmi_train_loss_args.grad_seed; esmi_train_pack_weights_f32,
@@ -486,6 +486,23 @@ int esmi_pack_resblock_f16(const float* src, void* dst, int c, int k, esmi_strea
 size_t esmi_hifigan_workspace_bytes(const esmi_hifigan_shape* s, int B, int L);
 int esmi_hifigan_generator_f32(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
                                float* wav, void* workspace, size_t workspace_bytes, esmi_stream_t stream);
+/* The same generator for a padded batch of utterances of different lengths: mel_len (B) int32 ON THE DEVICE holds each utterance's mel
+ * frames (esmi_phoneme2mel_forward_f32's mel_len as it is; values are clamped to [0, L]), and no work is done for frames no kept sample
+ * can depend on.  hop = prod(up_rates):
+ *   - samples t < mel_len[b] * hop are bit for bit those of esmi_hifigan_generator_f32 on the same mel (whatever the rows of `mel`
+ *     behind mel_len[b] + margin hold -- they are read by conv_pre only and reach no kept sample; the margin is the generator's
+ *     one-sided receptive field, 13 frames for v1 / v2, 11 for v3);
+ *   - samples t >= mel_len[b] * hop are exactly 0.0f (0 in the PCM plane): written, not computed.
+ * wav: float (B, L * hop) or NULL; pcm: int16 (B, L * hop) or NULL, = trunc(clamp(wav * 32768, -32768, 32767)).  The reference makes its
+ * PCM on the host with `(wav[:length] * 32768).astype("int16")` (utils/tools.py:96-103), which wraps a saturated tanh (+1.0f) around to
+ * -32768; this entry point clamps it to 32767 -- the one deliberate difference.  ESMI_ERR_ARG when mel_len is NULL or both planes are.
+ * Which launches carry the limit: conv_pre and the stages of more than 64 channels (v1's first two, v3's first) compute every frame;
+ * from the first stage of at most 64 channels on, the ConvTranspose1d, the ResBlocks (one launch or conv by conv) and conv_post
+ * work on min(n, mel_len[b] * rate + margin of that stage) positions per utterance (csrc/hifigan_resblock.h).  The workspace is
+ * esmi_hifigan_workspace_bytes(s, B, L), and its contents on entry do not matter. */
+int esmi_hifigan_generator_ragged_f32(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
+                                      const int32_t* mel_len, float* wav, int16_t* pcm, void* workspace, size_t workspace_bytes,
+                                      esmi_stream_t stream);
 
 /* x.masked_fill(mask[:, :, None], 0) on (rows, C) fp32 -- used by the module-level API when the
  * decoder is called stand-alone.                                                              */

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Development: time the HiFi-GAN generator (esmi_hifigan_generator_f32) alone.  python tools/bench_vocoder.py [--config v2] [--batch 16] [--frames 768]"""
+"""Development: time the HiFi-GAN generator (esmi_hifigan_generator_f32) alone.  python tools/bench_vocoder.py [--config v2] [--batch 16] [--frames 768]
+--ragged lo:hi[:seed]: utterance lengths uniform in [lo, hi] frames, the batch padded to hi; the full run and the length-aware run
+(esmi_hifigan_generator_ragged_f32) of that batch alternate, and the ideal ratio sum(min(len + margin, L)) / (B L) is printed."""
 import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -9,14 +11,50 @@ from efficientspeech_amd.hifigan import HIFIGAN_CONFIGS, Generator, synth_hifiga
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="v2"); ap.add_argument("--batch", type=int, default=16); ap.add_argument("--frames", type=int, default=768)
 ap.add_argument("--iters", type=int, default=5)
+ap.add_argument("--ragged", default=None, metavar="lo:hi[:seed]"); ap.add_argument("--rounds", type=int, default=5)
 a = ap.parse_args()
 h = HIFIGAN_CONFIGS[a.config]
+if a.ragged:
+    lo, hi, *seed = (int(v) for v in a.ragged.split(":"))
+    assert 0 <= lo <= hi and hi >= 1
+    a.frames = hi
 
 
 voc = Generator(h)
 voc.load_state_dict({k: torch.from_numpy(v) for k, v in synth_hifigan_state_dict(h, 1234).items()})
 voc = voc.cuda().eval()
 mel = torch.randn((a.batch, a.frames, h.num_mels), device="cuda") * 2 - 4
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(a.iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / a.iters
+
+
+if a.ragged:
+    from efficientspeech_amd.hifigan import ragged_margins
+    lens = np.random.default_rng(seed[0] if seed else 0).integers(lo, hi + 1, size=a.batch)
+    lengths = torch.from_numpy(lens.astype(np.int32)).cuda()
+    margin = ragged_margins(h)[1]
+    ideal = float(np.minimum(lens + margin, a.frames).sum()) / (a.batch * a.frames)
+    full, rag = [], []
+    with torch.no_grad():
+        for _ in range(2):
+            ref, wav = voc(mel.transpose(1, 2)), voc(mel.transpose(1, 2), lengths=lengths)
+        for _ in range(a.rounds):                       # alternating: both see the same clocks and neighbours
+            full.append(timed(lambda: voc(mel.transpose(1, 2))))
+            rag.append(timed(lambda: voc(mel.transpose(1, 2), lengths=lengths)))
+    keep = torch.arange(a.frames * h.hop, device="cuda")[None, :] < lengths[:, None] * h.hop
+    same = bool(torch.equal(wav[:, 0][keep], ref[:, 0][keep])) and not bool(wav[:, 0][~keep].any())
+    ms = lambda v: " ".join(f"{x * 1e3:.2f}" for x in v)      # noqa: E731
+    print(f"hifigan {a.config}: B={a.batch} L={a.frames} lengths U[{lo},{hi}] mean {lens.mean():.1f} margin {margin} frames")
+    print(f"  full   ms: {ms(full)}   median {np.median(full) * 1e3:.2f}")
+    print(f"  ragged ms: {ms(rag)}   median {np.median(rag) * 1e3:.2f}")
+    print(f"  ragged / full = {np.median(rag) / np.median(full):.3f}   ideal ratio = {ideal:.3f}   kept samples identical, tails zero: {same}")
+    sys.exit(0)
 with torch.no_grad():
     for _ in range(2):
         wav = voc(mel.transpose(1, 2))
