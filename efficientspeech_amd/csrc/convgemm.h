@@ -80,7 +80,7 @@ struct ConvGemmP {
     // (B) mel frames on the device.  Utterance b has conv_len_limit() = min(n_out, clamp(len[b], 0, len_max) * len_mul + len_add) output
     // positions: a wave tile that starts at or behind it leaves at once, positions from it on are neither computed nor written, and a
     // stride-1 convolution (n_in == n_out) reads its input rows from it on as zeros -- they may never have been written.  A
-    // ConvTranspose1d reads what its kept outputs need: the caller's margins (hg_margins, esmi_abi.hip) keep that inside the rows the
+    // ConvTranspose1d reads what its kept outputs need: the caller's margins (hg_margins, tu_hifigan.hip) keep that inside the rows the
     // stage before it wrote.  NULL: no limit
     const int* len;
     int len_max, len_mul, len_add;

@@ -90,13 +90,13 @@ const char* esmi_build_config(void) {
 int esmi_pack_conv_weight_f32(const float* src, float* dst, int cout, int cin, int k, esmi_stream_t stream) {
     if (!src || !dst || cout <= 0 || cin <= 0 || k <= 0) return ESMI_ERR_ARG;
     const long n = (long)cout * cin * k;
-    ESMI_LAUNCH(pack_conv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), src, dst, cout, cin, k, 0);
+    ESMI_LAUNCH(pack_conv_kernel, dim3(grid1d(n)), dim3(256), 0, S(stream), src, dst, cout, cin, k, 0);
     return launch_status();
 }
 int esmi_pack_convT_weight_f32(const float* src, float* dst, int cin, int cout, int k, esmi_stream_t stream) {
     if (!src || !dst || cout <= 0 || cin <= 0 || k <= 0) return ESMI_ERR_ARG;
     const long n = (long)cout * cin * k;
-    ESMI_LAUNCH(pack_conv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), src, dst, cout, cin, k, 1);
+    ESMI_LAUNCH(pack_conv_kernel, dim3(grid1d(n)), dim3(256), 0, S(stream), src, dst, cout, cin, k, 1);
     return launch_status();
 }
 
@@ -110,7 +110,7 @@ int esmi_pack_bfrag_f32(const float* src, float* dst, int n, int k, int taps, es
     if (k & 31) return ESMI_ERR_UNSUPPORTED;   // the split-f16 packing works on groups of 32 channels (two 16-channel MFMA steps)
 #endif
     const long tot = (long)esmi_pack_bfrag_floats(n, k, taps);
-    ESMI_LAUNCH(pack_bfrag_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, S(stream), src, dst, n, k, (n + 31) / 32, taps);
+    ESMI_LAUNCH(pack_bfrag_kernel, dim3(grid1d(tot)), dim3(256), 0, S(stream), src, dst, n, k, (n + 31) / 32, taps);
     return launch_status();
 }
 
@@ -118,13 +118,13 @@ int esmi_compose_merge_f32(const float* merge_w, const float* merge1_w, int k, i
                            esmi_stream_t stream) {
     if (!merge_w || !merge1_w || !dst || k <= 0 || cin <= 0 || cout <= 0) return ESMI_ERR_ARG;
     const long n = (long)k * cin * cout;
-    ESMI_LAUNCH(compose_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), merge_w, merge1_w, dst, k, cin, cout);
+    ESMI_LAUNCH(compose_merge_kernel, dim3(grid1d(n)), dim3(256), 0, S(stream), merge_w, merge1_w, dst, k, cin, cout);
     return launch_status();
 }
 
 int esmi_pool_mask_u8(const uint8_t* mask, int B, int T, int pool, uint8_t* out, int n_out, esmi_stream_t stream) {
     if (!mask || !out || B <= 0 || T <= 0 || pool <= 0 || n_out <= 0) return ESMI_ERR_ARG;
-    ESMI_LAUNCH(pool_mask_kernel, dim3((B * n_out + 255) / 256), dim3(256), 0, S(stream), mask, B, T, pool, out, n_out);
+    ESMI_LAUNCH(pool_mask_kernel, dim3(grid1d(B * n_out)), dim3(256), 0, S(stream), mask, B, T, pool, out, n_out);
     return launch_status();
 }
 
@@ -180,6 +180,96 @@ void fold_attention(const esmi_encoder_block_weights* w, EncAttnFfnP* f) {
     f->fold = 1; f->m.qkv_w = w->qk_wp; f->m.nq_override = 0; f->proj_w = w->vo_wp;
 }
 
+// ---- the one-kernel-per-op plan: the ops that have two callers, then the stages of a block that run when no chain kernel serves them
+// the unfolded MixFFN up to its GELU, blocks.py:23-27: mlp1, then the dense k = 3 conv + exact-erf GELU.  x -> m1 -> m2, both (rows, E)
+int launch_mixffn_front(int B, int n, int C, int E, const float* x, ConvW mlp1, const float* mlp1_b, ConvW conv, const float* conv_b,
+                        float* m1, float* m2, hipStream_t st) {
+    if (int rc = launch_convgemm(linear(B, n, C, E, x, C, mlp1, mlp1_b, m1, E), st)) return rc;
+    ConvGemmP p = conv1d(B, n, E, E, 3, 1, m1, E, conv, conv_b, m2, E);
+    p.act = ACT_GELU;
+    return launch_convgemm(p, st);
+}
+
+// One predictor (AcousticDecoder, networks.py:148-160) in two launches: conv1 + ReLU -> LN1 -> ReLU into t1 (rows, dim); conv2 + ReLU
+// with pred = Linear(dim, 1) on the PRE-norm2 tensor in the epilogue.  `features` (the duration predictor): the prediction passes a
+// ReLU and LN2 of the conv2 rows goes to features + row . ldf + f_coff, masked rows zeroed; nullptr: the rows are not stored.
+int launch_predictor(const esmi_predictor_weights* w, int dim, int B, int T, const float* x, int ldx, float* t1, float* pred, float* features,
+                     int ldf, int f_coff, const uint8_t* mask, hipStream_t st) {
+    ConvGemmP p = conv1d(B, T, dim, dim, 3, 1, x, ldx, {w->conv1_w, w->conv1_wp}, w->conv1_b, t1, dim);   // :152-155
+    p.act = ACT_RELU; p.ln_g = w->ln1_g; p.ln_b = w->ln1_b; p.post_relu = 1;
+    if (int rc = launch_convgemm(p, st)) return rc;
+    p = conv1d(B, T, dim, dim, 3, 1, t1, dim, {w->conv2_w, w->conv2_wp}, w->conv2_b, features, features ? ldf : 0);   // :157-160
+    p.act = ACT_RELU; p.dot_w = w->lin_w; p.dot_b = w->lin_b; p.dot_out = pred; p.dot_relu = features != nullptr;
+    if (features) { p.ln_g = w->ln2_g; p.ln_b = w->ln2_b; p.rowmask = mask; p.o_coff = f_coff; }
+    return launch_convgemm(p, st);
+}
+
+// the length regulator's scan: cum = the running sum of an utterance's durations, mel_len its total (lmax, optional: the batch's maximum)
+void launch_length_regulate(const int32_t* dur, int B, int T, int32_t* cum, int32_t* mel_len, int32_t* lmax, hipStream_t st) {
+    ESMI_LAUNCH(length_regulate_kernel, dim3(B), dim3(64), 0, st, dur, T, cum, mel_len, lmax);
+}
+
+// front: merge convs + the q / k / v GEMM (folded: q = x M, h*C wide, esmi.h) -> x_mid, qkv
+int per_op_front(const esmi_encoder_block_weights* w, const esmi_encoder_block_shape* s, int n, const int32_t* ids, const float* embed,
+                 const float* x_in, bool folded, float* t_merge, float* x_mid, float* qkv, hipStream_t st) {
+    const int B = s->B, C = s->c_out, nq = (folded ? 1 : 3) * s->heads * C;
+    int rc;
+    // merge conv k x k (dense, bias-free), networks.py:64-66
+    ConvGemmP p = conv_defaults();
+    p.B = B; p.n_in = s->n_in; p.c_in = s->c_in; p.n_out = n; p.c_out = s->c_in;
+    p.k = s->kernel; p.stride = s->stride; p.pad = s->kernel / 2;
+    if (ids) { p.ids = ids; p.table = embed; p.ld_table = s->c_in; p.vocab = s->vocab; }
+    else { p.A = x_in; p.lda = s->c_in; }
+    if (ESMI_CHAIN_SPLIT && w->merge_cwp && (s->c_in & 31) == 0) {   // (the exact-fp32 build's GEMMs read fp32 weights)
+        // both merge convolutions as ONE launch on the composed, pre-split weights the chain kernels use (merge_cwp: k x k conv . 1x1,
+        // esmi_compose_merge_f32 -> esmi_pack_bfrag_f32): no t_merge round trip, no weight split per wave
+        p.c_out = C; p.W = nullptr; p.Wp = w->merge_cwp; p.out = x_mid; p.ldo = C;
+        if ((rc = launch_convgemm(p, st))) return rc;
+    } else {
+        p.W = w->merge_w; p.out = t_merge; p.ldo = s->c_in;
+        if ((rc = launch_convgemm(p, st))) return rc;
+        // merge 1x1, networks.py:67
+        if ((rc = launch_convgemm(linear(B, n, s->c_in, C, t_merge, s->c_in, {w->merge1_w, nullptr}, nullptr, x_mid, C), st))) return rc;
+    }
+    // qkv Linear (bias-free), blocks.py:44
+    const ConvW qkv_w = folded ? ConvW{w->qk_w, w->qk_wp} : ConvW{w->qkv_w, w->qkv_wp};
+    return launch_convgemm(linear(B, n, C, nq, x_mid, C, qkv_w, nullptr, qkv, nq), st);
+}
+
+// softmax(q k^T scale) v -> ctx, blocks.py:49-64 (scores not masked).  qkv: the q | k | v rows; folded: q_h = x M_h, h*C wide, and
+// keys = values = x, shared by the heads
+int launch_self_attention(int B, int n, int C, int h, bool folded, float* qkv, float* x, float* ctx, hipStream_t st) {
+    AttnP a = {};
+    a.B = B; a.N = n; a.C = C; a.h = h; a.ctx = ctx; a.scale = 1.0f / sqrtf((float)(C / h));
+    if (!folded) a.qkv = qkv;
+    else { a.q = qkv; a.ldq = h * C; a.hsq = C; a.k = a.v = x; a.ldk = a.ldv = C; a.hsk = a.hsv = 0; }
+    return launch_attn(a, st);
+}
+
+// back, behind the attention: proj + LN1, MixFFN, mlp2 + LN2 -> x_out.  mask: pooled to the block's (B, n)
+int per_op_post_attention(const esmi_encoder_block_weights* w, const esmi_encoder_block_shape* s, int n, bool folded, const uint8_t* mask,
+                          const float* ctx, float* y1, float* m1, float* m2, float* x_out, hipStream_t st) {
+    const int B = s->B, C = s->c_out, h = s->heads, E = C * s->expansion;
+    int rc;
+    // proj + residual + LN1 + mask, blocks.py:65 + networks.py:73-75  (folded: ctx holds P_h x, the matrix is [O_h])
+    ConvGemmP p = linear(B, n, h * C, C, ctx, h * C, folded ? ConvW{w->vo_w, w->vo_wp} : ConvW{w->proj_w, w->proj_wp}, w->proj_b, y1, C);
+    p.res = x_out; p.ldr = C; p.ln_g = w->ln1_g; p.ln_b = w->ln1_b; p.rowmask = mask;
+    if ((rc = launch_convgemm(p, st))) return rc;
+    // MixFFN, blocks.py:22-29
+    if (ffn_folded(w)) {   // Linear folded into the k = 3 conv (esmi.h, ffn_cw): one contraction C -> E, position-dependent bias at the two ends
+        p = conv1d(B, n, C, E, 3, 1, y1, C, {w->ffn_cw, w->ffn_cwp}, w->ffn_cb, m2, E);
+        p.bias_first = w->ffn_cb_first; p.bias_last = w->ffn_cb_last; p.act = ACT_GELU;
+        rc = launch_convgemm(p, st);
+    } else {
+        rc = launch_mixffn_front(B, n, C, E, y1, {w->mlp1_w, w->mlp1_wp}, w->mlp1_b, {w->conv_w, w->conv_wp}, w->conv_b, m1, m2, st);
+    }
+    if (rc) return rc;
+    // mlp2 + residual + LN2 + mask, networks.py:80-83
+    p = linear(B, n, E, C, m2, E, {w->mlp2_w, w->mlp2_wp}, w->mlp2_b, x_out, C);
+    p.res = y1; p.ldr = C; p.ln_g = w->ln2_g; p.ln_b = w->ln2_b; p.rowmask = mask;
+    return launch_convgemm(p, st);
+}
+
 }  // namespace
 
 int esmi_encoder_block_f32(const esmi_encoder_block_weights* w, const esmi_encoder_block_shape* s, const int32_t* ids,
@@ -192,24 +282,17 @@ int esmi_encoder_block_f32(const esmi_encoder_block_weights* w, const esmi_encod
     const EncWs ws = enc_ws(s);
     if (workspace_bytes < ws.total) return ESMI_ERR_WORKSPACE;
     char* wsb = static_cast<char*>(workspace);
-    float* t_merge = reinterpret_cast<float*>(wsb + ws.t_merge);
-    float* qkv = reinterpret_cast<float*>(wsb + ws.qkv);
-    float* ctx = reinterpret_cast<float*>(wsb + ws.ctx);
-    float* y1 = reinterpret_cast<float*>(wsb + ws.y1);
-    float* m1 = reinterpret_cast<float*>(wsb + ws.m1);
-    float* m2 = reinterpret_cast<float*>(wsb + ws.m2);
-    const int B = s->B, C = s->c_out, h = s->heads, E = s->c_out * s->expansion;
+    auto F = [&](size_t off) { return reinterpret_cast<float*>(wsb + off); };
+    const int B = s->B, C = s->c_out, h = s->heads;
     const int n = conv_out_len(s->n_in, s->kernel, s->stride, s->kernel / 2);
     hipStream_t st = S(stream);
-    int rc;
     const bool packed = block_packed(w);
     // enc_attn_ffn behind the front: x (the block input after the merge convs) lives in scratch and the result goes straight to x_out
     // (tiles read their neighbours' x rows, so in place is not possible)
     const bool attn_ffn = packed && (plan & ESMI_FUSE_ATTN_FFN) && enc_attn_ffn_supported(C, n, s->expansion);
-    float* x_mid = attn_ffn ? y1 : x_out;
     // one-kernel-per-op attention with folded weights (esmi.h): the Linear behind the merge convs is x M (h*C wide) instead of qkv
     const bool folded = !attn_ffn && h >= 2 && w->qk_w && w->qk_wp && w->vo_w && w->vo_wp;   // (one head: measured no gain per op; HISTORY.md 3.3)
-    const int nq = folded ? h * C : 3 * h * C;
+    float *qkv = F(ws.qkv), *ctx = F(ws.ctx), *y1 = F(ws.y1), *x_mid = attn_ffn ? y1 : x_out;
     const EncAttnFfnP f = block_params(w, s, ids, embed, x_in, mask, x_mid, qkv, x_out);
 
     // ---- the whole block in one launch
@@ -227,55 +310,21 @@ int esmi_encoder_block_f32(const esmi_encoder_block_weights* w, const esmi_encod
                  launch_enc_merge_q256(MergeQ256P{x_in, x_mid, qkv, w->merge_cwp, w->qk_wp, B, s->n_in, n, s->kernel, h}, st))
         if (packed && (plan & ESMI_FUSE_MERGE_QKV)) {
             EncMergeP m = f.m;
-            if (folded) { m.qkv_w = w->qk_wp; m.nq_override = nq; }
+            if (folded) { m.qkv_w = w->qk_wp; m.nq_override = h * C; }
             ESMI_TRY(true, launch_enc_merge_qkv(m, s->c_in, C, st))
         }
-        // merge conv k x k (dense, bias-free), networks.py:64-66
-        ConvGemmP p = conv_defaults();
-        p.B = B; p.n_in = s->n_in; p.c_in = s->c_in; p.n_out = n; p.c_out = s->c_in;
-        p.k = s->kernel; p.stride = s->stride; p.pad = s->kernel / 2;
-        if (ids) { p.ids = ids; p.table = embed; p.ld_table = s->c_in; p.vocab = s->vocab; }
-        else { p.A = x_in; p.lda = s->c_in; }
-        if (ESMI_CHAIN_SPLIT && w->merge_cwp && (s->c_in & 31) == 0) {   // (the exact-fp32 build's GEMMs read fp32 weights)
-            // both merge convolutions as ONE launch on the composed, pre-split weights the chain kernels use (merge_cwp: k x k conv . 1x1,
-            // esmi_compose_merge_f32 -> esmi_pack_bfrag_f32): no t_merge round trip, no weight split per wave
-            p.c_out = C; p.W = nullptr; p.Wp = w->merge_cwp; p.out = x_mid; p.ldo = C;
-            if ((rc = launch_convgemm(p, st))) return rc;
-        } else {
-            p.W = w->merge_w; p.out = t_merge; p.ldo = s->c_in;
-            if ((rc = launch_convgemm(p, st))) return rc;
-            // merge 1x1, networks.py:67
-            p = conv_defaults();
-            p.B = B; p.n_in = n; p.c_in = s->c_in; p.n_out = n; p.c_out = C;
-            p.A = t_merge; p.lda = s->c_in; p.W = w->merge1_w; p.out = x_mid; p.ldo = C;
-            if ((rc = launch_convgemm(p, st))) return rc;
-        }
-        // qkv Linear (bias-free), blocks.py:44
-        p = conv_defaults();
-        p.B = B; p.n_in = n; p.c_in = C; p.n_out = n; p.c_out = nq;
-        p.A = x_mid; p.lda = C; p.W = folded ? w->qk_w : w->qkv_w; p.Wp = folded ? w->qk_wp : w->qkv_wp; p.out = qkv; p.ldo = nq;
-        return launch_convgemm(p, st);
+        return per_op_front(w, s, n, ids, embed, x_in, folded, F(ws.t_merge), x_mid, qkv, st);
     };
-    if ((rc = front())) return rc;
+    if (int rc = front()) return rc;
 
     // ---- back: attention + proj + LN1 + MixFFN + LN2 -> x_out
     if (attn_ffn) return launch_enc_attn_ffn(f, s->expansion, plan & ESMI_FUSE_SPLIT2, st);   // (the front wrote x to y1 for it)
     if (mask && s->mask_pool > 1) {   // the one-kernel-per-op plan takes a pooled (B, n) mask: blocks.py:51-57
         uint8_t* pm = reinterpret_cast<uint8_t*>(wsb + ws.pmask);
-        if ((rc = esmi_pool_mask_u8(mask, B, s->mask_len, s->mask_pool, pm, n, stream))) return rc;
+        if (int rc = esmi_pool_mask_u8(mask, B, s->mask_len, s->mask_pool, pm, n, stream)) return rc;
         mask = pm;
     }
-    // softmax(q k^T scale) v, blocks.py:49-64
-    AttnP a = {};
-    a.B = B; a.N = n; a.C = C; a.h = h; a.ctx = ctx;
-    a.scale = 1.0f / sqrtf((float)(C / h));
-    if (folded) {   // q_h = x M_h (the `qkv` buffer, h*C wide); keys = values = x, shared by the heads
-        a.q = qkv; a.ldq = h * C; a.hsq = C;
-        a.k = a.v = x_out; a.ldk = a.ldv = C; a.hsk = a.hsv = 0;
-    } else {
-        a.qkv = qkv;
-    }
-    if ((rc = launch_attn(a, st))) return rc;
+    if (int rc = launch_self_attention(B, n, C, h, folded, qkv, x_out, ctx, st)) return rc;
     // everything behind the attention in one launch; folded (enc_ffn128.h): ctx = the heads' P_h x, the projection is [Wv_h^T Wp_h^T]
     ESMI_TRY(chain16 && packed && !folded && C == 64 && h == 1 && s->expansion == 1 && n <= 256,
              launch_enc_post_attn64(PostAttn64P{ctx, x_out, x_out, w->proj_wp, w->ffn_cwp, w->mlp2_wp, w->proj_b, w->ln1_g, w->ln1_b, w->ffn_cb,
@@ -283,37 +332,7 @@ int esmi_encoder_block_f32(const esmi_encoder_block_weights* w, const esmi_encod
     ESMI_TRY(chain16 && packed && folded && C == 128 && h == 2 && s->expansion == 2 && n <= 256,
              launch_enc_post_attn128(PostAttn128P{ctx, x_out, y1, x_out, w->vo_wp, w->ffn_cwp, w->mlp2_wp, w->proj_b, w->ln1_g, w->ln1_b,
                                                   w->ffn_cb, w->ffn_cb_first, w->ffn_cb_last, w->mlp2_b, w->ln2_g, w->ln2_b, mask, B, n}, st))
-    // proj + residual + LN1 + mask, blocks.py:65 + networks.py:73-75  (folded: ctx holds P_h x, the matrix is [O_h])
-    ConvGemmP p = conv_defaults();
-    p.B = B; p.n_in = n; p.c_in = h * C; p.n_out = n; p.c_out = C;
-    p.A = ctx; p.lda = h * C; p.W = folded ? w->vo_w : w->proj_w; p.Wp = folded ? w->vo_wp : w->proj_wp; p.bias = w->proj_b;
-    p.res = x_out; p.ldr = C; p.ln_g = w->ln1_g; p.ln_b = w->ln1_b; p.rowmask = mask;
-    p.out = y1; p.ldo = C;
-    if ((rc = launch_convgemm(p, st))) return rc;
-    // MixFFN, blocks.py:22-29
-    if (ffn_folded(w)) {   // Linear folded into the k = 3 conv (esmi.h, ffn_cw): one contraction C -> E, position-dependent bias at the two ends
-        p = conv_defaults();
-        p.B = B; p.n_in = n; p.c_in = C; p.n_out = n; p.c_out = E; p.k = 3; p.pad = 1;
-        p.A = y1; p.lda = C; p.W = w->ffn_cw; p.Wp = w->ffn_cwp; p.bias = w->ffn_cb; p.bias_first = w->ffn_cb_first; p.bias_last = w->ffn_cb_last;
-        p.act = ACT_GELU; p.out = m2; p.ldo = E;
-        if ((rc = launch_convgemm(p, st))) return rc;
-    } else {
-        p = conv_defaults();
-        p.B = B; p.n_in = n; p.c_in = C; p.n_out = n; p.c_out = E;
-        p.A = y1; p.lda = C; p.W = w->mlp1_w; p.Wp = w->mlp1_wp; p.bias = w->mlp1_b; p.out = m1; p.ldo = E;
-        if ((rc = launch_convgemm(p, st))) return rc;
-        p = conv_defaults();
-        p.B = B; p.n_in = n; p.c_in = E; p.n_out = n; p.c_out = E; p.k = 3; p.pad = 1;
-        p.A = m1; p.lda = E; p.W = w->conv_w; p.Wp = w->conv_wp; p.bias = w->conv_b; p.act = ACT_GELU; p.out = m2; p.ldo = E;
-        if ((rc = launch_convgemm(p, st))) return rc;
-    }
-    // mlp2 + residual + LN2 + mask, networks.py:80-83
-    p = conv_defaults();
-    p.B = B; p.n_in = n; p.c_in = E; p.n_out = n; p.c_out = C;
-    p.A = m2; p.lda = E; p.W = w->mlp2_w; p.Wp = w->mlp2_wp; p.bias = w->mlp2_b;
-    p.res = y1; p.ldr = C; p.ln_g = w->ln2_g; p.ln_b = w->ln2_b; p.rowmask = mask;
-    p.out = x_out; p.ldo = C;
-    return launch_convgemm(p, st);
+    return per_op_post_attention(w, s, n, folded, mask, ctx, y1, F(ws.m1), F(ws.m2), x_out, st);
 }
 
 size_t esmi_fuse_workspace_bytes(int B, int T, int dim, int depth) {
@@ -331,29 +350,20 @@ int esmi_fuse_f32(const esmi_fuse_weights* w, int depth, int dim, int kernel, in
     int rc;
     for (int i = 0; i < depth; ++i) {
         const int ci = dim << i, s = 1 << i;
-        ConvGemmP p = conv_defaults();  // Linear(dim*2^i, dim), networks.py:197
-        p.B = B; p.n_in = n_i[i]; p.c_in = ci; p.n_out = n_i[i]; p.c_out = dim;
-        p.A = feats[i]; p.lda = ci; p.W = w->mlp_w[i]; p.Wp = w->mlp_wp[i]; p.bias = w->mlp_b[i];
-        if (i == 0) {
-            if (n_i[0] != T) return ESMI_ERR_ARG;
-            p.out = cat; p.ldo = dim * depth; p.o_coff = 0;
-            if ((rc = launch_convgemm(p, st))) return rc;
-        } else {
-            p.out = tmp; p.ldo = dim;
-            if ((rc = launch_convgemm(p, st))) return rc;
-            if ((n_i[i] - 1) * s + kernel < T) return ESMI_ERR_UNSUPPORTED;  // torch.cat would raise in the reference
-            p = conv_defaults();  // ConvTranspose1d(dim, dim, k, stride 2^i) cropped to T, networks.py:199-206
-            p.mode = MODE_CONVT; p.k = kernel; p.stride = s;
-            p.B = B; p.n_in = n_i[i]; p.c_in = dim; p.n_out = T; p.c_out = dim;
-            p.A = tmp; p.lda = dim; p.W = w->up_w[i]; p.Wp = w->up_wp[i]; p.bias = w->up_b[i];   // (the streaming kernel reads the pre-split blob: round 5)
-            p.out = cat; p.ldo = dim * depth; p.o_coff = i * dim;
-            if ((rc = launch_convgemm(p, st))) return rc;
-        }
+        if (i == 0 && n_i[0] != T) return ESMI_ERR_ARG;
+        // Linear(dim*2^i, dim), networks.py:197: level 0 straight into its columns of the concatenation
+        ConvGemmP p = linear(B, n_i[i], ci, dim, feats[i], ci, {w->mlp_w[i], w->mlp_wp[i]}, w->mlp_b[i], i == 0 ? cat : tmp, i == 0 ? dim * depth : dim);
+        if ((rc = launch_convgemm(p, st))) return rc;
+        if (i == 0) continue;
+        if ((n_i[i] - 1) * s + kernel < T) return ESMI_ERR_UNSUPPORTED;  // torch.cat would raise in the reference
+        // ConvTranspose1d(dim, dim, k, stride 2^i) cropped to T, networks.py:199-206  (the streaming kernel reads the pre-split blob: round 5)
+        p = conv_transpose1d(B, n_i[i], T, dim, dim, kernel, s, 0, tmp, dim, {w->up_w[i], w->up_wp[i]}, w->up_b[i], cat, dim * depth);
+        p.o_coff = i * dim;
+        if ((rc = launch_convgemm(p, st))) return rc;
     }
-    ConvGemmP p = conv_defaults();  // Linear(depth*dim, dim) + masked_fill, networks.py:215-217
-    p.B = B; p.n_in = T; p.c_in = dim * depth; p.n_out = T; p.c_out = dim;
-    p.A = cat; p.lda = dim * depth; p.W = w->fuse_w; p.Wp = w->fuse_wp; p.bias = w->fuse_b; p.rowmask = mask;
-    p.out = out; p.ldo = ld_out;
+    // Linear(depth*dim, dim) + masked_fill, networks.py:215-217
+    ConvGemmP p = linear(B, T, dim * depth, dim, cat, dim * depth, {w->fuse_w, w->fuse_wp}, w->fuse_b, out, ld_out);
+    p.rowmask = mask;
     return launch_convgemm(p, st);
 }
 
@@ -370,27 +380,11 @@ int esmi_variance_adaptor_f32(const esmi_predictor_weights* pitch, const esmi_pr
     if (workspace_bytes < esmi_variance_adaptor_workspace_bytes(B, T, dim)) return ESMI_ERR_WORKSPACE;
     float* t1 = static_cast<float*>(workspace);
     hipStream_t st = S(stream);
-    const esmi_predictor_weights* pw[3] = {pitch, energy, duration};
-    float* preds[3] = {pitch_pred, energy_pred, duration_pred};
+    // the fused features are columns [0, dim) of feat's 4 dim; the duration predictor's features go to [3 dim, 4 dim), masked (:366-368)
     int rc;
-    for (int q = 0; q < 3; ++q) {
-        // conv1 + ReLU -> LN1 -> ReLU, networks.py:152-155
-        ConvGemmP p = conv_defaults();
-        p.B = B; p.n_in = T; p.c_in = dim; p.n_out = T; p.c_out = dim; p.k = 3; p.pad = 1;
-        p.A = feat; p.lda = 4 * dim; p.a_coff = 0; p.W = pw[q]->conv1_w; p.Wp = pw[q]->conv1_wp; p.bias = pw[q]->conv1_b; p.act = ACT_RELU;
-        p.ln_g = pw[q]->ln1_g; p.ln_b = pw[q]->ln1_b; p.post_relu = 1; p.out = t1; p.ldo = dim;
-        if ((rc = launch_convgemm(p, st))) return rc;
-        // conv2 + ReLU; pred = Linear(dim,1) on the PRE-norm2 tensor (:157-160); duration: ReLU + features = LN2
-        p = conv_defaults();
-        p.B = B; p.n_in = T; p.c_in = dim; p.n_out = T; p.c_out = dim; p.k = 3; p.pad = 1;
-        p.A = t1; p.lda = dim; p.W = pw[q]->conv2_w; p.Wp = pw[q]->conv2_wp; p.bias = pw[q]->conv2_b; p.act = ACT_RELU;
-        p.dot_w = pw[q]->lin_w; p.dot_b = pw[q]->lin_b; p.dot_out = preds[q]; p.dot_relu = q == 2;
-        if (q == 2) {
-            p.ln_g = pw[q]->ln2_g; p.ln_b = pw[q]->ln2_b; p.rowmask = mask;   // :366-368
-            p.out = feat; p.ldo = 4 * dim; p.o_coff = 3 * dim;
-        }
-        if ((rc = launch_convgemm(p, st))) return rc;
-    }
+    if ((rc = launch_predictor(pitch, dim, B, T, feat, 4 * dim, t1, pitch_pred, nullptr, 0, 0, nullptr, st))) return rc;
+    if ((rc = launch_predictor(energy, dim, B, T, feat, 4 * dim, t1, energy_pred, nullptr, 0, 0, nullptr, st))) return rc;
+    if ((rc = launch_predictor(duration, dim, B, T, feat, 4 * dim, t1, duration_pred, feat, 4 * dim, 3 * dim, mask, st))) return rc;
     VaTailP v;
     v.rows = B * T; v.T = T; v.dim = dim; v.mask = mask;
     v.pitch_pred = pitch_pred; v.energy_pred = energy_pred; v.dur_pred = duration_pred;
@@ -400,7 +394,7 @@ int esmi_variance_adaptor_f32(const esmi_predictor_weights* pitch, const esmi_pr
     if (!v.pbins || !v.ebins || !v.pemb || !v.eemb) return ESMI_ERR_ARG;
     if (dim & 3) return ESMI_ERR_UNSUPPORTED;                  // (dim = embed_dim // reduction: 32 / 64 / 128 for the published sizes)
     const long n = (long)B * T * (dim >> 2);                   // one thread per four channels
-    ESMI_LAUNCH(va_tail_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, v);
+    ESMI_LAUNCH(va_tail_kernel, dim3(grid1d(n)), dim3(256), 0, st, v);
     return launch_status();
 }
 
@@ -546,7 +540,7 @@ int fuse_variance_adaptor(const VaArgs& a) {
             return launch_enc_fuse_va(p, a.dim, a.kernel, nw, head_in_chain, st);
         };
         if ((rc = chain())) return rc;
-        if (a.cum && !scan_done) ESMI_LAUNCH(length_regulate_kernel, dim3(a.B), dim3(64), 0, st, a.dur, a.T, a.cum, a.mel_len, (int*)nullptr);
+        if (a.cum && !scan_done) launch_length_regulate(a.dur, a.B, a.T, a.cum, a.mel_len, nullptr, st);
     } else {                // ---- Fuse, then the three predictors + the variance adaptor's tail + the length regulator's scan
         if (!a.workspace || a.workspace_bytes < esmi_fuse_variance_adaptor_workspace_bytes(a.B, a.T, a.dim, a.depth)) return ESMI_ERR_WORKSPACE;
         const size_t fws = esmi_fuse_workspace_bytes(a.B, a.T, a.dim, a.depth);
@@ -567,7 +561,7 @@ int fuse_variance_adaptor(const VaArgs& a) {
                                                     a.preds[0], a.preds[1], a.preds[2], a.pitch_idx, a.energy_idx, a.dur,
                                                     static_cast<char*>(a.workspace) + fws, a.workspace_bytes - fws, a.stream);
             if (r) return r;
-            if (a.cum) ESMI_LAUNCH(length_regulate_kernel, dim3(a.B), dim3(64), 0, st, a.dur, a.T, a.cum, a.mel_len, (int*)nullptr);
+            if (a.cum) launch_length_regulate(a.dur, a.B, a.T, a.cum, a.mel_len, nullptr, st);
             return ESMI_OK;
         };
         if ((rc = fuse()) || (rc = predictors())) return rc;
@@ -594,11 +588,9 @@ int esmi_fuse_variance_adaptor_f32(const esmi_fuse_weights* fw, int depth, int d
 // MelDecoder's first stage at phoneme rate as one launch: GEMM (k = 1) + bias + tanh + LayerNorm in the epilogue (networks.py:291-293)
 int esmi_decoder_head_f32(const esmi_decoder_head* head, long rows, const float* feat, float* h0, esmi_stream_t stream) {
     if (!head_gemm_ok(head) || !feat || !h0 || rows <= 0 || rows > 0x7fffffffL) return head_gemm_ok(head) ? ESMI_ERR_ARG : ESMI_ERR_UNSUPPORTED;
-    ConvGemmP p = conv_defaults();
-    p.B = 1; p.n_in = p.n_out = (int)rows; p.c_in = head->d4; p.c_out = head->dx2;
-    p.A = feat; p.lda = head->d4; p.W = head->proj_w; p.bias = head->proj_b; p.act = ACT_TANH;
-    p.ln_g = head->ln_g; p.ln_b = head->ln_b; p.out = h0; p.ldo = head->dx2;
-    p.Wp = head->proj_wp;            // (optional) pre-split fragments: the LDS-staged kernel then brings the weight tiles in by LDS-DMA
+    // (proj_wp, optional: pre-split fragments -- the LDS-staged kernel then brings the weight tiles in by LDS-DMA)
+    ConvGemmP p = linear(1, (int)rows, head->d4, head->dx2, feat, head->d4, {head->proj_w, head->proj_wp}, head->proj_b, h0, head->dx2);
+    p.act = ACT_TANH; p.ln_g = head->ln_g; p.ln_b = head->ln_b;
     return launch_convgemm(p, S(stream));
 }
 
@@ -634,18 +626,10 @@ int esmi_self_attention_f32(const float* qkv_w, const float* proj_w, const float
     float* ctx = reinterpret_cast<float*>(static_cast<char*>(workspace) + align256((size_t)B * N * 3 * heads * C * 4));
     hipStream_t st = S(stream);
     int rc;
-    ConvGemmP p = conv_defaults();   // qkv Linear (bias-free), blocks.py:44
-    p.B = B; p.n_in = N; p.c_in = C; p.n_out = N; p.c_out = 3 * heads * C;
-    p.A = x; p.lda = C; p.W = qkv_w; p.out = qkv; p.ldo = 3 * heads * C;
-    if ((rc = launch_convgemm(p, st))) return rc;
-    AttnP a = {};                     // softmax(q k^T scale) v, blocks.py:49-64 (scores not masked)
-    a.qkv = qkv; a.B = B; a.N = N; a.C = C; a.h = heads; a.ctx = ctx;
-    a.scale = 1.0f / sqrtf((float)(C / heads));
-    if ((rc = launch_attn(a, st))) return rc;
-    p = conv_defaults();              // proj, blocks.py:65
-    p.B = B; p.n_in = N; p.c_in = heads * C; p.n_out = N; p.c_out = C;
-    p.A = ctx; p.lda = heads * C; p.W = proj_w; p.bias = proj_b; p.out = out; p.ldo = C;
-    return launch_convgemm(p, st);
+    // qkv Linear (bias-free), blocks.py:44
+    if ((rc = launch_convgemm(linear(B, N, C, 3 * heads * C, x, C, {qkv_w, nullptr}, nullptr, qkv, 3 * heads * C), st))) return rc;
+    if ((rc = launch_self_attention(B, N, C, heads, false, qkv, nullptr, ctx, st))) return rc;
+    return launch_convgemm(linear(B, N, heads * C, C, ctx, heads * C, {proj_w, nullptr}, proj_b, out, C), st);   // proj, blocks.py:65
 }
 
 size_t esmi_mixffn_workspace_bytes(int B, int N, int C, int expansion) {
@@ -663,19 +647,8 @@ int esmi_mixffn_f32(const float* mlp1_w, const float* mlp1_b, const float* conv_
     float* m1 = static_cast<float*>(workspace);
     float* m2 = reinterpret_cast<float*>(static_cast<char*>(workspace) + align256((size_t)B * N * E * 4));
     hipStream_t st = S(stream);
-    int rc;
-    ConvGemmP p = conv_defaults();   // mlp1, blocks.py:23
-    p.B = B; p.n_in = N; p.c_in = C; p.n_out = N; p.c_out = E;
-    p.A = x; p.lda = C; p.W = mlp1_w; p.bias = mlp1_b; p.out = m1; p.ldo = E;
-    if ((rc = launch_convgemm(p, st))) return rc;
-    p = conv_defaults();              // dense k=3 conv + exact-erf GELU, blocks.py:24-27
-    p.B = B; p.n_in = N; p.c_in = E; p.n_out = N; p.c_out = E; p.k = 3; p.pad = 1;
-    p.A = m1; p.lda = E; p.W = conv_w; p.bias = conv_b; p.act = ACT_GELU; p.out = m2; p.ldo = E;
-    if ((rc = launch_convgemm(p, st))) return rc;
-    p = conv_defaults();              // mlp2, blocks.py:28
-    p.B = B; p.n_in = N; p.c_in = E; p.n_out = N; p.c_out = C;
-    p.A = m2; p.lda = E; p.W = mlp2_w; p.bias = mlp2_b; p.out = out; p.ldo = C;
-    return launch_convgemm(p, st);
+    if (int rc = launch_mixffn_front(B, N, C, E, x, {mlp1_w, nullptr}, mlp1_b, {conv_w, nullptr}, conv_b, m1, m2, st)) return rc;
+    return launch_convgemm(linear(B, N, E, C, m2, E, {mlp2_w, nullptr}, mlp2_b, out, C), st);   // mlp2, blocks.py:28
 }
 
 int esmi_acoustic_decoder_f32(const esmi_predictor_weights* w, int dim, int B, int T, int duration, const float* x, int ldx,
@@ -683,27 +656,14 @@ int esmi_acoustic_decoder_f32(const esmi_predictor_weights* w, int dim, int B, i
     if (!w || !x || !pred || !workspace || dim <= 0 || B <= 0 || T <= 0 || ldx < dim) return ESMI_ERR_ARG;
     if (duration && !features) return ESMI_ERR_ARG;
     if (workspace_bytes < esmi_variance_adaptor_workspace_bytes(B, T, dim)) return ESMI_ERR_WORKSPACE;
-    float* t1 = static_cast<float*>(workspace);
-    hipStream_t st = S(stream);
-    ConvGemmP p = conv_defaults();   // conv1 + ReLU -> LN1 -> ReLU, networks.py:152-155
-    p.B = B; p.n_in = T; p.c_in = dim; p.n_out = T; p.c_out = dim; p.k = 3; p.pad = 1;
-    p.A = x; p.lda = ldx; p.W = w->conv1_w; p.Wp = w->conv1_wp; p.bias = w->conv1_b; p.act = ACT_RELU;
-    p.ln_g = w->ln1_g; p.ln_b = w->ln1_b; p.post_relu = 1; p.out = t1; p.ldo = dim;
-    int rc = launch_convgemm(p, st);
-    if (rc) return rc;
-    p = conv_defaults();              // conv2 + ReLU; y = Linear(dim,1) on the PRE-norm2 tensor (:157-160); duration: ReLU + features = LN2
-    p.B = B; p.n_in = T; p.c_in = dim; p.n_out = T; p.c_out = dim; p.k = 3; p.pad = 1;
-    p.A = t1; p.lda = dim; p.W = w->conv2_w; p.Wp = w->conv2_wp; p.bias = w->conv2_b; p.act = ACT_RELU;
-    p.dot_w = w->lin_w; p.dot_b = w->lin_b; p.dot_out = pred; p.dot_relu = duration != 0;
-    if (duration) { p.ln_g = w->ln2_g; p.ln_b = w->ln2_b; p.out = features; p.ldo = dim; }
-    return launch_convgemm(p, st);
+    return launch_predictor(w, dim, B, T, x, ldx, static_cast<float*>(workspace), pred, duration ? features : nullptr, dim, 0, nullptr, S(stream));
 }
 
 int esmi_bucket_embedding_f32(const float* v, const float* bins, const float* emb, int64_t rows, int dim, float* out,
                               int32_t* idx, esmi_stream_t stream) {
     if (!v || !bins || !emb || !out || rows <= 0 || dim <= 1) return ESMI_ERR_ARG;
     const long n = (long)rows * dim;
-    ESMI_LAUNCH(bucket_embed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), v, bins, emb, (long)rows, dim, out, idx);
+    ESMI_LAUNCH(bucket_embed_kernel, dim3(grid1d(n)), dim3(256), 0, S(stream), v, bins, emb, (long)rows, dim, out, idx);
     return launch_status();
 }
 
@@ -718,14 +678,14 @@ int esmi_length_regulate_i32(const int32_t* dur, int B, int T, int32_t* cum, int
     if (!dur || !cum || !mel_len || !lmax || B <= 0 || T <= 0) return ESMI_ERR_ARG;
     hipError_t e = hipMemsetAsync(lmax, 0, sizeof(int32_t), S(stream));
     if (e != hipSuccess) return (int)e;
-    ESMI_LAUNCH(length_regulate_kernel, dim3(B), dim3(64), 0, S(stream), dur, T, cum, mel_len, lmax);
+    launch_length_regulate(dur, B, T, cum, mel_len, lmax, S(stream));
     return launch_status();
 }
 
 int esmi_length_regulator_indices_i32(const int32_t* cum, int B, int T, int L, int32_t* idx, esmi_stream_t stream) {
     if (!cum || !idx || B <= 0 || T <= 0 || L <= 0) return ESMI_ERR_ARG;
     const long n = (long)B * L;
-    ESMI_LAUNCH(lr_indices_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), cum, B, T, L, idx);
+    ESMI_LAUNCH(lr_indices_kernel, dim3(grid1d(n)), dim3(256), 0, S(stream), cum, B, T, L, idx);
     return launch_status();
 }
 
@@ -733,7 +693,7 @@ int esmi_upsample_f32(const float* feat, const uint8_t* fmask, const int32_t* cu
                       float* features, uint8_t* masks, esmi_stream_t stream) {
     if (!feat || !cum || !features || B <= 0 || T <= 0 || L <= 0 || (C & 3)) return ESMI_ERR_ARG;
     const long n = (long)B * L * (C / 4);
-    ESMI_LAUNCH(upsample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), feat, fmask, cum, B, T, C, L,
+    ESMI_LAUNCH(upsample_kernel, dim3(grid1d(n)), dim3(256), 0, S(stream), feat, fmask, cum, B, T, C, L,
                 features, masks);
     return launch_status();
 }
@@ -741,217 +701,8 @@ int esmi_upsample_f32(const float* feat, const uint8_t* fmask, const int32_t* cu
 int esmi_mask_rows_f32(float* x, const uint8_t* mask, int64_t rows, int C, esmi_stream_t stream) {
     if (!x || !mask || rows <= 0 || C <= 0) return ESMI_ERR_ARG;
     const long n = (long)rows * C;
-    ESMI_LAUNCH(mask_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), x, mask, (long)rows, C);
+    ESMI_LAUNCH(mask_rows_kernel, dim3(grid1d(n)), dim3(256), 0, S(stream), x, mask, (long)rows, C);
     return launch_status();
-}
-
-// ------------------------------------------------------------------ mel decoder
-// ------------------------------------------------------------------ HiFi-GAN generator
-namespace {
-struct HgPlan {
-    size_t buf;      // bytes of one activation buffer (the largest B * N * C of the chain)
-    long n_last;     // samples per utterance
-};
-int hg_plan(const esmi_hifigan_shape* s, int B, int L, HgPlan* o) {
-    if (!s || B <= 0 || L <= 0 || s->n_up < 1 || s->n_up > ESMI_HIFIGAN_MAX_UP || s->n_kernels < 1 ||
-        s->n_kernels > ESMI_HIFIGAN_MAX_KERNELS || (s->resblock != 1 && s->resblock != 2) || s->n_mel <= 0 || (s->n_mel & 7))
-        return ESMI_ERR_ARG;
-    if (s->n_up * s->n_kernels * 3 > ESMI_HIFIGAN_MAX_RBCONV) return ESMI_ERR_UNSUPPORTED;
-    long n = L;
-    int c = s->initial_channel;
-    size_t mx = (size_t)B * n * c;
-    for (int i = 0; i < s->n_up; ++i) {
-        if (s->up_rates[i] < 1 || s->up_kernels[i] < s->up_rates[i] || ((s->up_kernels[i] - s->up_rates[i]) & 1) || (c & 15)) return ESMI_ERR_UNSUPPORTED;
-        n *= s->up_rates[i];
-        c /= 2;
-        const size_t e = (size_t)B * n * c;
-        mx = e > mx ? e : mx;
-    }
-    if (c & 7) return ESMI_ERR_UNSUPPORTED;   // implicit-GEMM k-steps are 8 channels
-    o->buf = align256(mx * 4);
-    o->n_last = n;
-    return ESMI_OK;
-}
-
-// one-sided receptive field of ResBlock j of a stage: sum((k - 1) / 2 . dilation) over its convolutions
-int rb_halo(const esmi_hifigan_shape* s, int j) {
-    const int nconv = s->resblock == 1 ? 3 : 2, half = (s->rb_kernels[j] - 1) / 2;
-    int halo = 0;
-    for (int m = 0; m < nconv; ++m) halo += half * s->rb_dilations[j * 3 + m] + (s->resblock == 1 ? half : 0);
-    return halo;
-}
-// Length-aware call: how far behind an utterance's last mel frame each stage still has to be right for every KEPT sample (t < len . hop)
-// to come out as in the full run -- the one-sided receptive field from that stage to the waveform, walked backwards: conv_post reads 3
-// positions ahead; the ResBlocks of a stage the largest halo among them (one margin per stage: out (+)= block(x) then accumulates
-// over the same rows for every block); ConvTranspose1d(k, u, pad (k - u) / 2) output t reads inputs up to floor((t + pad) / u), so m
-// positions behind len . rate need ceil((m + pad) / u) behind len . rate / u; conv_pre reads 3 frames ahead.  Stage i (the output of
-// ups[i] and its ResBlocks) then covers n_eff = min(n, len . mul[i] + add[i]) positions.
-// hifigan.ragged_margins (Python; tools/bench_vocoder.py's ideal ratio) is the same walk written a second time: keep the two in step.
-// This copy is bound by tests/test_vocoder_ragged.py on the device -- too short fails the bit-for-bit test on NaN-filled workspaces, and
-// the margin test overwrites the mel from the frames the PYTHON copy claims on -- for v1 / v2 / v3; other shapes have no such test.
-struct HgMargins { int mul[ESMI_HIFIGAN_MAX_UP], add[ESMI_HIFIGAN_MAX_UP]; };
-HgMargins hg_margins(const esmi_hifigan_shape* s) {
-    HgMargins g = {};
-    int rate = 1, need = 3;
-    for (int i = 0; i < s->n_up; ++i) g.mul[i] = rate *= s->up_rates[i];
-    for (int i = s->n_up - 1; i >= 0; --i) {
-        int halo = 0;
-        for (int j = 0; j < s->n_kernels; ++j) halo = rb_halo(s, j) > halo ? rb_halo(s, j) : halo;
-        g.add[i] = need + halo;
-        const int u = s->up_rates[i], pad = (s->up_kernels[i] - u) / 2;
-        need = (g.add[i] + pad + u - 1) / u;
-    }
-    return g;
-}
-
-bool resblock_fused_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, int rb, int c, int k, int n, ResblockP* o) {
-#if !ESMI_CHAIN_SPLIT
-    return false;   // the exact-fp32 build keeps the per-conv fp32-MFMA launches
-#endif
-    if ((c != 8 && c != 16 && c != 32 && c != 64) || (k != 3 && k != 7 && k != 11)) return false;   // the instantiations
-    const int nconv = s->resblock == 1 ? 3 : 2, j = rb % s->n_kernels;
-    ResblockP p = {};
-    const int halo = rb_halo(s, j);
-    int q = 0;
-    for (int m = 0; m < nconv; ++m) {
-        const int d = s->rb_dilations[j * 3 + m];
-        if (d < 1 || !w->rb_wp1[rb * 3 + m] || !w->rb_b1[rb * 3 + m]) return false;
-        p.conv[q++] = RbConv{static_cast<const unsigned*>(w->rb_wp1[rb * 3 + m]), w->rb_b1[rb * 3 + m], d, s->resblock == 1 ? 0 : 1};
-        if (s->resblock == 1) {
-            if (!w->rb_wp2[rb * 3 + m] || !w->rb_b2[rb * 3 + m]) return false;
-            p.conv[q++] = RbConv{static_cast<const unsigned*>(w->rb_wp2[rb * 3 + m]), w->rb_b2[rb * 3 + m], 1, 1};
-        }
-    }
-    const int r_max = c == 64 ? 256 : 512;    // 8 waves = 8 (row pair, 32-channel tile) items; LDS <= 80 KB: two workgroups per CU
-    int R = ((n + 2 * halo + 63) / 64) * 64;
-    R = R < r_max ? R : r_max;
-    if (R - 2 * halo < 32 && R - 2 * halo < n) return false;
-    p.n_conv = q; p.k = k; p.halo = halo; p.R = R; p.TL = R - 2 * halo; p.n = n;
-    p.tiles_per_b = (n + p.TL - 1) / p.TL;
-    *o = p;
-    return true;
-}
-// The generator behind both entry points.  mel_len == nullptr: the plain call.  Otherwise (include/esmi.h) conv_pre and the stages of
-// more than 64 channels compute every frame -- their convolutions run on the kernels that tile flat rows across utterances --, and from
-// the first stage of at most 64 channels on every launch (ConvTranspose1d, the ResBlocks fused or conv by conv, conv_post) carries the
-// stage's limit from hg_margins: a limited stage reads only rows the stage before it wrote, full or limited.  What that leaves
-// unlimited, by multiply-adds (n . c^2 per stage): v2 (64 / 32 / 16 / 8 channels) conv_pre alone, a few per cent; v3 its 128-channel
-// stage, about a fifth; v1 its 256- and 128-channel stages, about two thirds -- on v1 most of the padded work is still done.
-int hifigan_generator(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
-                      const int32_t* mel_len, float* wav, int16_t* pcm, void* workspace, size_t workspace_bytes, esmi_stream_t stream) {
-    HgPlan o;
-    int rc = hg_plan(s, B, L, &o);
-    if (rc) return rc;
-    if (!w || !mel || (!wav && !pcm) || !workspace) return ESMI_ERR_ARG;
-    const HgMargins mg = hg_margins(s);
-    if (workspace_bytes < 4 * o.buf) return ESMI_ERR_WORKSPACE;
-    hipStream_t st = S(stream);
-    float* bufs[4];
-    for (int q = 0; q < 4; ++q) bufs[q] = reinterpret_cast<float*>(static_cast<char*>(workspace) + q * o.buf);
-    float *x = bufs[0], *y = bufs[1], *r = bufs[2], *t = bufs[3];   // x: stage input / sum over the ResBlocks; y: upsampled; r, t: ResBlock state
-    const float slope = 0.1f;                                       // LRELU_SLOPE, hifigan/models.py:17
-    long n = L;
-    int c = s->initial_channel;
-    ConvGemmP p = conv_defaults();   // conv_pre, models.py:112: Conv1d(n_mel, C0, 7, padding 3)
-    p.B = B; p.n_in = L; p.c_in = s->n_mel; p.n_out = L; p.c_out = c; p.k = 7; p.pad = 3;
-    p.A = mel; p.lda = s->n_mel; p.W = w->pre_w; p.bias = w->pre_b; p.out = x; p.ldo = c;
-    if (!p.W || !p.bias) return ESMI_ERR_ARG;
-    if ((rc = launch_convgemm(p, st))) return rc;
-    float in_scale = 1.0f;           // the mean over the ResBlocks of the previous stage, folded into the next input activation
-    for (int i = 0; i < s->n_up; ++i) {
-        const int u = s->up_rates[i], k = s->up_kernels[i], co = c / 2;
-        const long no = n * u;
-        const bool lim = mel_len && co <= 64;   // this stage runs under the per-utterance limit (and so does every later one)
-        auto limit = [&](ConvGemmP& q) { if (lim) { q.len = mel_len; q.len_max = L; q.len_mul = mg.mul[i]; q.len_add = mg.add[i]; } };
-        // x = ups[i](leaky_relu(x, 0.1)), models.py:114-115: ConvTranspose1d(c, c/2, k, u, padding (k-u)//2)
-        p = conv_defaults();
-        p.mode = MODE_CONVT; p.k = k; p.stride = u; p.pad = (k - u) / 2;
-        p.B = B; p.n_in = (int)n; p.c_in = c; p.n_out = (int)no; p.c_out = co;
-        p.A = x; p.lda = c; p.W = w->up_w[i]; p.bias = w->up_b[i]; p.out = y; p.ldo = co;
-        p.act_in = 1; p.act_in_slope = slope; p.a_scale = in_scale;
-        limit(p);
-        if (!p.W || !p.bias) return ESMI_ERR_ARG;
-        if ((rc = launch_convgemm(p, st))) return rc;
-        n = no; c = co;
-        for (int j = 0; j < s->n_kernels; ++j) {   // xs += resblocks[i*num_kernels + j](x), models.py:116-121
-            const int rb = i * s->n_kernels + j, kk = s->rb_kernels[j];
-            const int nconv = s->resblock == 1 ? 3 : 2;
-            ResblockP fp;
-            if (resblock_fused_ok(w, s, rb, c, kk, (int)n, &fp)) {   // the whole block on an LDS-resident window: y -> x (+)=
-                fp.x = y; fp.out = x; fp.B = B; fp.accum = j > 0; fp.slope = slope;
-                if (lim) { fp.len = mel_len; fp.len_max = L; fp.len_mul = mg.mul[i]; fp.len_add = mg.add[i]; }
-                if ((rc = launch_resblock(fp, c, st))) return rc;
-                continue;
-            }
-            const float* cur = y;                   // the ResBlock's running x (first iteration: the stage input itself)
-            for (int m = 0; m < nconv; ++m) {
-                const int d = s->rb_dilations[j * 3 + m];
-                const bool last = m + 1 == nconv;
-                float* dst = last ? x : (cur == r ? t : r);   // last iteration: straight into the stage sum (accumulated for j > 0)
-                if (s->resblock == 1) {
-                    // xt = c1(leaky_relu(x)); xt = c2(leaky_relu(xt)); x = xt + x   (models.py:49-54)
-                    // buffers: cur in {y, r}; c1 writes t; c2 reads t, adds cur, writes dst in {r (in place when cur == r), x}
-                    p = conv_defaults();
-                    p.B = B; p.n_in = (int)n; p.c_in = c; p.n_out = (int)n; p.c_out = c; p.k = kk; p.dil = d; p.pad = (kk * d - d) / 2;
-                    p.A = cur; p.lda = c; p.W = w->rb_w1[rb * 3 + m]; p.bias = w->rb_b1[rb * 3 + m]; p.out = t; p.ldo = c;
-                    p.act_in = 1; p.act_in_slope = slope;
-                    limit(p);
-                    if (!p.W || !p.bias) return ESMI_ERR_ARG;
-                    if ((rc = launch_convgemm(p, st))) return rc;
-                    p = conv_defaults();
-                    p.B = B; p.n_in = (int)n; p.c_in = c; p.n_out = (int)n; p.c_out = c; p.k = kk; p.dil = 1; p.pad = (kk - 1) / 2;
-                    p.A = t; p.lda = c; p.W = w->rb_w2[rb * 3 + m]; p.bias = w->rb_b2[rb * 3 + m];
-                    p.res = cur; p.ldr = c;
-                    p.out = last ? x : r; p.ldo = c; p.accum = last && j > 0;
-                    p.act_in = 1; p.act_in_slope = slope;
-                    limit(p);
-                    if (!p.W || !p.bias) return ESMI_ERR_ARG;
-                    if ((rc = launch_convgemm(p, st))) return rc;
-                    cur = r;
-                } else {
-                    // xt = c(leaky_relu(x)); x = xt + x   (models.py:75-79): the conv reads neighbours of x, so not in place
-                    p = conv_defaults();
-                    p.B = B; p.n_in = (int)n; p.c_in = c; p.n_out = (int)n; p.c_out = c; p.k = kk; p.dil = d; p.pad = (kk * d - d) / 2;
-                    p.A = cur; p.lda = c; p.W = w->rb_w1[rb * 3 + m]; p.bias = w->rb_b1[rb * 3 + m];
-                    p.res = cur; p.ldr = c; p.out = dst; p.ldo = c; p.accum = last && j > 0;
-                    p.act_in = 1; p.act_in_slope = slope;
-                    limit(p);
-                    if (!p.W || !p.bias) return ESMI_ERR_ARG;
-                    if ((rc = launch_convgemm(p, st))) return rc;
-                    cur = dst;
-                }
-            }
-        }
-        in_scale = 1.0f / (float)s->n_kernels;   // x = xs / num_kernels (models.py:122), applied where x is read next
-    }
-    // x = tanh(conv_post(leaky_relu(x))), models.py:123-125 (F.leaky_relu default slope 0.01)
-    p = conv_defaults();
-    p.B = B; p.n_in = (int)n; p.c_in = c; p.n_out = (int)n; p.c_out = 1; p.k = 7; p.pad = 3;
-    p.A = x; p.lda = c; p.W = w->post_w; p.bias = w->post_b; p.out = wav; p.ldo = 1; p.act = ACT_TANH;
-    p.act_in = 1; p.act_in_slope = 0.01f; p.a_scale = in_scale;
-    if (!p.W || !p.bias) return ESMI_ERR_ARG;
-    if (!mel_len) return launch_convgemm(p, st);
-    // every sample is written: the utterance's own, then exact zeros from len . hop on (no margin: these are the kept samples themselves)
-    p.len = mel_len; p.len_max = L; p.len_mul = (int)(n / L); p.len_add = 0;
-    return launch_conv_to1_len(p, pcm, st);
-}
-}  // namespace
-
-size_t esmi_hifigan_workspace_bytes(const esmi_hifigan_shape* s, int B, int L) {
-    HgPlan o;
-    return hg_plan(s, B, L, &o) == ESMI_OK ? 4 * o.buf : 0;
-}
-
-int esmi_hifigan_generator_f32(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
-                               float* wav, void* workspace, size_t workspace_bytes, esmi_stream_t stream) {
-    return hifigan_generator(w, s, mel, B, L, nullptr, wav, nullptr, workspace, workspace_bytes, stream);
-}
-
-int esmi_hifigan_generator_ragged_f32(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
-                                      const int32_t* mel_len, float* wav, int16_t* pcm, void* workspace, size_t workspace_bytes,
-                                      esmi_stream_t stream) {
-    if (!mel_len) return ESMI_ERR_ARG;
-    return hifigan_generator(w, s, mel, B, L, mel_len, wav, pcm, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------ whole forward behind one call

@@ -204,7 +204,7 @@ __device__ __forceinline__ void layernorm_tile_regs(f32x16 (&v)[NT], const float
 // instruction selection can then no longer fold the constants into the 16-bit DS offset field.
 
 // Positions of utterance b at a stage of a length-aware HiFi-GAN call: min(n, clamp(len[b], 0, len_max) * mul + add) -- its mel frames
-// times the stage's up-sampling rate plus the stage's margin (esmi_abi.hip, hg_margins).  The ONE place the limit is formed: the
+// times the stage's up-sampling rate plus the stage's margin (tu_hifigan.hip, hg_margins).  The ONE place the limit is formed: the
 // ConvTranspose1d, the ResBlocks (one launch or conv by conv) and conv_post of a stage must agree on it to the position.
 __device__ __forceinline__ int utterance_positions(const int* len, int b, int len_max, int mul, int add, int n) {
     int l = len[b];

@@ -26,7 +26,7 @@
 //
 // Per-utterance lengths (ResblockP::len, esmi_hifigan_generator_ragged_f32): utterance b ends at n_eff[b] = min(n, clamp(len[b], 0,
 // len_max) . len_mul + len_add) -- its mel frames times the stage's cumulative up-sampling rate plus the one-sided receptive field from
-// this stage's input to the waveform (host: hg_margins, esmi_abi.hip).  A workgroup whose output window starts at or behind n_eff[b]
+// this stage's input to the waveform (host: hg_margins, tu_hifigan.hip).  A workgroup whose output window starts at or behind n_eff[b]
 // returns at once (a scalar branch on blockIdx; the grid stays B . tiles_per_b and the lengths stay on the device); a surviving window
 // treats positions >= n_eff[b] exactly as positions >= n: they load as zeros and `inside` is false.  So no surviving workgroup reads a
 // row a skipped one would have written, and -- the window grid depends on n only -- every sample inside the receptive-field margin

@@ -59,6 +59,28 @@ inline unsigned grid1d(long n, int block = 256) { return (unsigned)((n + block -
 ConvGemmP conv_defaults();
 int launch_convgemm(ConvGemmP p, hipStream_t st);
 int launch_conv_to1_len(ConvGemmP p, int16_t* pcm, hipStream_t st);   // ConvGemmP::len set: zeros behind each utterance's end; float and / or int16 plane
+// The ops of the one-kernel-per-op plan as ConvGemmP descriptors: the shape and operand fields, filled in one place.  What tells one op
+// from the next (activation, residual, LayerNorm, masks, row-dot, accumulation, column offsets, ...) stays an assignment at the call site.
+struct ConvW { const float *w, *wp; };   // the fp32 tensor (k, c_out, c_in) and its pre-split blob (esmi_pack_bfrag_f32); either may be NULL
+inline ConvGemmP linear(int B, int n, int c_in, int c_out, const float* A, int lda, ConvW w, const float* bias, float* out, int ldo) {
+    ConvGemmP p = conv_defaults();
+    p.B = B; p.n_in = p.n_out = n; p.c_in = c_in; p.c_out = c_out;
+    p.A = A; p.lda = lda; p.W = w.w; p.Wp = w.wp; p.bias = bias; p.out = out; p.ldo = ldo;
+    return p;
+}
+// Conv1d(c_in, c_out, k, dilation = dil, padding = "same"), stride 1.  (dil = 1 is stored as 1; the kernels read 0, conv_defaults', as 1 too)
+inline ConvGemmP conv1d(int B, int n, int c_in, int c_out, int k, int dil, const float* A, int lda, ConvW w, const float* bias, float* out, int ldo) {
+    ConvGemmP p = linear(B, n, c_in, c_out, A, lda, w, bias, out, ldo);
+    p.k = k; p.dil = dil; p.pad = (k * dil - dil) / 2;
+    return p;
+}
+// ConvTranspose1d(c_in, c_out, k, stride, padding = pad): n_in -> n_out positions (n_out below the full length crops)
+inline ConvGemmP conv_transpose1d(int B, int n_in, int n_out, int c_in, int c_out, int k, int stride, int pad, const float* A, int lda,
+                                  ConvW w, const float* bias, float* out, int ldo) {
+    ConvGemmP p = linear(B, n_in, c_in, c_out, A, lda, w, bias, out, ldo);
+    p.n_out = n_out; p.mode = MODE_CONVT; p.k = k; p.stride = stride; p.pad = pad;
+    return p;
+}
 // tu_attention.hip
 int launch_attn(const AttnP& p, hipStream_t st);
 // tu_enc_merge.hip / tu_enc_block.hip / tu_enc_attn_ffn.hip / tu_enc_fuse_va.hip (rounds 1-4: the 32-row wave-chain kernels).  Every
@@ -81,7 +103,7 @@ int launch_enc_pred128(const Pred128P& p, int dim, hipStream_t st);   // enc_pre
 int launch_enc_fuse128(const FuseVaP& p, int dim, int kernel, hipStream_t st);   // enc_fuse128.h: the Fuse stage of the same models
 int launch_enc_post_attn128(const PostAttn128P& p, hipStream_t st);   // enc_ffn128.h: proj + LN1 + MixFFN + LN2, C = 128, two heads, expansion 2, N <= 256
 int launch_enc_merge_q256(const MergeQ256P& p, hipStream_t st);   // enc_merge256.h: merge conv k = 3 stride 2, 128 -> 256, + the folded query GEMM, N <= 128
-// tu_hifigan.hip
+// tu_hifigan.hip (which also holds the generator's host side: esmi_hifigan_*)
 int launch_resblock(const ResblockP& p, int c, hipStream_t st);
 
 // Does enc_attn_ffn serve this block (the shapes it is instantiated for)?  Not beyond 128 positions: there the chain kernel runs one
@@ -94,7 +116,8 @@ inline bool enc_attn_ffn_supported(int C, int N, int expansion) {
 }
 
 // ---- activation-range check (esmi_dev.h, the ESMI_RANGE_CHECK build): every translation unit owns a copy of the device-side flag
-// pointer and defines its setter with ESMI_TU_RANGE_SETTER(<unit>); `set_range_flag_all` (esmi_abi.hip) calls them all.
+// pointer and defines its setter with ESMI_TU_RANGE_SETTER(<unit>); the validation mode of esmi_phoneme2mel_forward_f32 (esmi_abi.hip)
+// calls them all.
 int set_range_flag_abi(int* flag);
 int set_range_flag_convgemm(int* flag);
 int set_range_flag_attention(int* flag);

@@ -6,10 +6,6 @@
 using namespace esmi;
 ESMI_TU_RANGE_SETTER(convgemm)
 
-
-// rows (B * n_out) from which the per-op plan's GEMMs take the LDS-staged kernel: kGemmLdsMinRowsDefault (wavesim_shim.h: 2048 on the
-// GPU, 1 in the simulator)
-
 #ifdef ESMI_GEMM_TRACE
 namespace esmi { __device__ long long* g_gemm_trace_dev = nullptr; }
 extern "C" void esmi_dev_set_gemm_trace(long long* ptr) { hipMemcpyToSymbol(HIP_SYMBOL(esmi::g_gemm_trace_dev), &ptr, sizeof(ptr)); }
@@ -98,7 +94,8 @@ int launch_convgemm(ConvGemmP p, hipStream_t st) {
     // large plain convolutions / Linears: operands staged through LDS by convgemm_dma_kernel (convgemm.h) -- needs input rows ==
     // output rows (flat-row addressing) and 32-bit lane offsets: the kernel forms (row + tile rows + halo) * lda BEFORE it clamps, so
     // the bound covers the last workgroup's padded rows and the taps' reach, not just the tensor (the pre-clamp product
-    // must not overflow); anything else streams from L2 below
+    // must not overflow); anything else streams from L2 below.  The rows (B * n_out) from which a GEMM takes this kernel:
+    // kGemmLdsMinRowsDefault (wavesim_shim.h: 2048 on the GPU, 1 in the simulator)
     if (p.mode == MODE_CONV && p.stride == 1 && !p.ids && (p.c_in & 31) == 0 && p.c_out > 64 && (long)p.B * p.n_out >= kGemmLdsMinRowsDefault &&
         p.n_in == p.n_out &&
         (((long)p.B * p.n_in + 64L * kGemmLdsWaves + 2L * kGemmHaloMax + 8) * p.lda + p.a_coff + p.c_in) < (1L << 31)) {

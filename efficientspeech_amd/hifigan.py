@@ -226,7 +226,7 @@ class Generator(_PackedModule):
 
 def ragged_margins(h: HifiGanConfig):
     """The one-sided receptive field of the length-aware generator, walked backwards from the waveform exactly as the library's host
-    side does (esmi_abi.hip, hg_margins): -> (per stage i the positions behind `len * rate_i` that stage computes, mel frames behind
+    side does (tu_hifigan.hip, hg_margins): -> (per stage i the positions behind `len * rate_i` that stage computes, mel frames behind
     `len` that can reach a kept sample).  conv_post adds 3; a stage's ResBlocks add the largest halo among them; a
     ConvTranspose1d(k, u, pad (k - u) / 2) maps a need of m output positions to ceil((m + pad) / u) inputs; conv_pre adds 3 frames.
 

@@ -50,16 +50,30 @@ def use_sim():
 
 
 @contextlib.contextmanager
-def launched_kernels():
-    """The kernels the simulator launches inside the block, in order: the list is filled when the block exits.  Names are the
-    launch sites' spelling without the outer parentheses and blanks, e.g. `enc_va64_kernel<2>`."""
+def launch_records():
+    """The launches the simulator makes inside the block, in order, as `(name, "gx,gy,gz|bx,by,bz|lds")`: the list is filled when the
+    block exits.  Names are the launch sites' spelling without the outer parentheses and blanks, e.g. `enc_va64_kernel<2>`; the
+    second field is the grid, the block and the dynamic LDS bytes of that launch."""
     lib = sim_lib()
     lib.wavesim_launch_log_clear()
-    names = []
+    records = []
     try:
-        yield names
+        yield records
     finally:
         for rec in lib.wavesim_launch_log().decode().splitlines():
-            name = rec.rsplit(" ", 7)[0].replace(" ", "")      # (grid, block and LDS bytes follow the name)
-            names.append(name[1:-1] if name.startswith("(") else name)
+            name, *num = rec.rsplit(" ", 7)                    # (grid, block and LDS bytes follow the name)
+            name = name.replace(" ", "")
+            records.append((name[1:-1] if name.startswith("(") else name,
+                            f"{','.join(num[0:3])}|{','.join(num[3:6])}|{num[6]}"))
         lib.wavesim_launch_log_clear()
+
+
+@contextlib.contextmanager
+def launched_kernels():
+    """launch_records() without the numbers: the kernels' names alone."""
+    names, records = [], []
+    try:
+        with launch_records() as records:
+            yield names
+    finally:
+        names.extend(name for name, _ in records)

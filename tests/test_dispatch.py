@@ -17,7 +17,7 @@ from efficientspeech_amd import CONFIGS, _lib, build_phoneme2mel, load_numpy_sta
 from efficientspeech_amd.synth import synth_phonemes, synth_state_dict
 from oracle import oracle
 from tests import helpers as H
-from tests.simlib import launched_kernels, use_sim
+from tests.simlib import launch_records, use_sim
 
 _CONFIGS = {"tiny": CONFIGS["tiny"], "small": CONFIGS["small"], "base": CONFIGS["base"],
             "tiny_e2": dataclasses.replace(CONFIGS["tiny"], name="tiny_e2", expansion=2),      # MixFFN expansion 2 on dim 32
@@ -229,8 +229,9 @@ def _without_ln2(predictors):
     return get
 
 
-def run_entry(name, B, T, lens, plan, entry):
-    """the kernels `entry` launches on the simulator (weight preparation left out), and its outputs"""
+def run_entry(name, B, T, lens, plan, entry, full_records=False):
+    """the kernels `entry` launches on the simulator (weight preparation left out), and its outputs.  full_records: each kernel as
+    `name[gx,gy,gz|bx,by,bz|lds]`, with its grid, block and dynamic LDS bytes."""
     net, _ = _net(name)
     ids, mask = synth_phonemes(B, T, 5, lens)
     x = {"phoneme": torch.from_numpy(ids)}
@@ -242,7 +243,7 @@ def run_entry(name, B, T, lens, plan, entry):
             os.environ["ESMI_FOLD_FFN"] = "0"
             enc._cache.invalidate()
         try:
-            with launched_kernels() as names:
+            with launch_records() as records:
                 if entry == "forward":
                     out = net(x)
                 elif entry == "encode":
@@ -259,7 +260,7 @@ def run_entry(name, B, T, lens, plan, entry):
             if entry == "block":
                 os.environ.pop("ESMI_FOLD_FFN", None)
                 enc._cache.invalidate()
-    return " ".join(n for n in names if not n.startswith(_PREP)), out
+    return " ".join(f"{n}[{dims}]" if full_records else n for n, dims in records if not n.startswith(_PREP)), out
 
 
 @pytest.mark.parametrize("name,B,T,lens,plan,entry,expected", ROWS, ids=[f"{r[0]}-B{r[1]}-T{r[2]}-plan{r[4]}-{r[5]}" for r in ROWS])
@@ -272,3 +273,34 @@ def test_dispatch_launches(name, B, T, lens, plan, entry, expected):
         o = oracle.phoneme2mel(_CONFIGS[name], oracle.Weights(sd), ids, mask)
         for key in ("pitch", "energy", "duration"):
             np.testing.assert_allclose(out[key].numpy(), getattr(o, key), atol=H.PRED_TOL, rtol=0, err_msg=key)
+
+
+# The names above do not tell a convolution from another of the same kernel.  One row of the one-kernel-per-op plan with the complete
+# records -- grid, block, dynamic LDS bytes per launch -- so that a descriptor with a wrong c_out, n_out or ldo, which changes a grid, is
+# seen: tiny ES, B = 2, T = 40, plan 0, the one-call forward (both blocks, Fuse, the predictors, the decoder head's GEMM).
+PER_OP_RECORDS = (
+    "convgemm_kernel<1,false>[1,1,1|256,1,1|0] convgemm_dma_kernel<4,1,NWV,false,true>[8,1,1|256,1,1|49152] "
+    "attn_kernel<2>[1,1,1|256,1,1|0] convgemm_kernel<1,false>[1,1,1|256,1,1|0] convgemm_kernel<1,false>[1,1,1|256,1,1|0] "
+    "convgemm_kernel<1,false>[1,1,1|256,1,1|0] convgemm_kernel<1,false>[1,2,1|256,1,1|0] "
+    "convgemm_dma_kernel<4,1,NWV,false,true>[8,1,1|256,1,1|49152] pool_mask_kernel[1,1,1|256,1,1|0] "
+    "attn_kernel<1>[1,1,1|256,1,1|0] convgemm_kernel<2,false>[1,1,1|256,1,1|0] convgemm_kernel<1,false>[1,2,1|256,1,1|0] "
+    "convgemm_kernel<2,false>[1,1,1|256,1,1|0] convgemm_kernel<1,false>[1,1,1|256,1,1|0] "
+    "convgemm_kernel<1,false>[1,1,1|256,1,1|0] convgemm_kernel<1,false>[1,1,1|256,1,1|0] "
+    "convgemm_kernel<1,false>[1,1,1|256,1,1|0] convgemm_kernel<1,false>[1,1,1|256,1,1|0] "
+    "convgemm_kernel<1,false>[1,1,1|256,1,1|0] convgemm_kernel<1,false>[1,1,1|256,1,1|0] "
+    "convgemm_kernel<1,false>[1,1,1|256,1,1|0] convgemm_kernel<1,false>[1,1,1|256,1,1|0] "
+    "convgemm_kernel<1,false>[1,1,1|256,1,1|0] va_tail_kernel[3,1,1|256,1,1|0] length_regulate_kernel[2,1,1|64,1,1|0] "
+    "convgemm_dma_kernel<4,1,NWV,false,true>[8,1,1|256,1,1|49152] max_i32_kernel[1,1,1|64,1,1|0] "
+    "mel_decoder_kernel<DX2,KD,NW>[16,1,1|512,1,1|75840] "
+)
+
+
+def test_per_op_plan_launch_records():
+    got, _ = run_entry("tiny", 2, 40, L40, 0, "forward", full_records=True)
+    assert got.split() == PER_OP_RECORDS.split()
+
+
+if __name__ == "__main__":   # prints PER_OP_RECORDS, to re-record after an intended change of the launches
+    import textwrap
+    for ln in textwrap.wrap(run_entry("tiny", 2, 40, L40, 0, "forward", full_records=True)[0], 116, break_long_words=False, break_on_hyphens=False):
+        print(f'    "{ln} "')
