@@ -101,6 +101,11 @@ class TrainLossArgs(C.Structure):
                [(n, fp) for n in ("out", "d_mel", "d_pitch", "d_energy", "d_dur", "scratch", "grad_seed")]
 
 
+class ProsodyControl(C.Structure):
+    """esmi_prosody_control (include/esmi.h): per-utterance (B) fp32 device arrays, NULL = 1."""
+    _fields_ = [("pitch_scale", fp), ("energy_scale", fp), ("duration_scale", fp)]
+
+
 class ForwardArgs(C.Structure):
     """esmi_forward_args (include/esmi.h): the whole inference forward behind one call."""
     _fields_ = [(n, C.c_int) for n in ("B", "T", "depth", "dim", "fuse_kernel", "plan")] + \
@@ -148,6 +153,7 @@ EXPORTS = (
     "esmi_acoustic_decoder_f32", "esmi_bucket_embedding_f32", "esmi_split_weight_limit", "esmi_absmax_f32",
     "esmi_forward_arena_bytes", "esmi_phoneme2mel_forward_f32", "esmi_hifigan_workspace_bytes", "esmi_hifigan_generator_f32",
     "esmi_hifigan_generator_ragged_f32",
+    "esmi_variance_adaptor_ctl_f32", "esmi_fuse_variance_adaptor_ctl_f32", "esmi_phoneme2mel_forward_ctl_f32",
     "esmi_pack_resblock_bytes", "esmi_pack_resblock_f16",
     "esmi_train_conv_fwd_f32", "esmi_train_conv_ln_fwd_f32", "esmi_train_conv_dgrad_f32", "esmi_train_conv_wgrad_f32", "esmi_train_layernorm_fwd_f32",
     "esmi_train_conv_wgrad_workspace_bytes", "esmi_train_layernorm_bwd_workspace_bytes", "esmi_train_conv_workspace_bytes",
@@ -186,10 +192,12 @@ def bind(lib):
     lib.esmi_variance_adaptor_workspace_bytes.argtypes = [i, i, i]
     lib.esmi_variance_adaptor_workspace_bytes.restype = sz
     lib.esmi_variance_adaptor_f32.argtypes = [P(PredictorWeights)] * 3 + [i, i, i] + [fp] * 11 + [fp, sz, fp]
+    lib.esmi_variance_adaptor_ctl_f32.argtypes = lib.esmi_variance_adaptor_f32.argtypes + [P(ProsodyControl)]
     lib.esmi_fuse_variance_adaptor_workspace_bytes.argtypes = [i, i, i, i]
     lib.esmi_fuse_variance_adaptor_workspace_bytes.restype = sz
     lib.esmi_fuse_variance_adaptor_f32.argtypes = [P(FuseWeights), i, i, i, i, i, P(fp), P(i)] + [P(PredictorWeights)] * 3 + \
         [fp] * 13 + [P(DecoderHead), fp, i] + [fp, sz, fp]
+    lib.esmi_fuse_variance_adaptor_ctl_f32.argtypes = lib.esmi_fuse_variance_adaptor_f32.argtypes + [P(ProsodyControl)]
     lib.esmi_decoder_head_f32.argtypes = [P(DecoderHead), C.c_long, fp, fp, fp]
     lib.esmi_max_i32.argtypes = [fp, i, fp, fp]
     lib.esmi_length_regulate_i32.argtypes = [fp, i, i, fp, fp, fp, fp]
@@ -217,6 +225,7 @@ def bind(lib):
     lib.esmi_forward_arena_bytes.argtypes = [P(ForwardArgs)]
     lib.esmi_forward_arena_bytes.restype = sz
     lib.esmi_phoneme2mel_forward_f32.argtypes = [P(ForwardArgs), i, fp]
+    lib.esmi_phoneme2mel_forward_ctl_f32.argtypes = [P(ForwardArgs), P(ProsodyControl), i, fp]
     i64, f, dbl = C.c_int64, C.c_float, C.c_double
     lib.esmi_train_conv_fwd_f32.argtypes = [P(ConvDesc), fp, fp, fp, fp, fp, sz, fp]
     lib.esmi_train_conv_ln_fwd_f32.argtypes = [P(ConvDesc), fp, fp, fp, fp, fp, fp, fp, i, fp, fp, fp, fp, fp, sz, fp]

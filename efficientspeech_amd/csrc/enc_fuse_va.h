@@ -106,6 +106,72 @@ __device__ __forceinline__ void layernorm_tile_regs_batched(f32x16 (&v)[NT], con
 }
 #endif
 
+// The 32-lane row sums of this kernel, four rows at a time, with the DPP stage, the ds_swizzle round trips and the next batch ordered BY DATA
+// FLOW: every row's value passes through one opaque asm statement in front of the batch, one between the two stages and one behind the
+// adds (volatile: the three keep their order, within a batch and from batch to batch).  So no ds_swizzle is issued before every DPP chain
+// of its batch is done, and no DPP chain of the next batch before this batch's swizzle results are consumed -- whatever the code around the
+// reductions looks like.  With the plain row-by-row row_sum32 that was up to the compiler's schedulers: an unrelated edit of the kernel's
+// tail brought the wrong-rows mode of profiles/r05_probes/fuse_va_wrong_rows.md back (positions 25..29 of the T = 31 fixture).  A
+// sched_fence() alone (wave_chain.h's rule) is not enough here: DPP and swizzle are side-effect-free operations that instruction selection
+// places on either side of it (seen in the ISA).  Batches of four are that note's STAGED=4 form.
+__device__ __forceinline__ void order_rows4(float (&s)[4]) {
+#ifndef ESMI_WAVESIM
+    asm volatile("" : "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3]));
+#endif
+    sched_fence();
+}
+__device__ __forceinline__ void row_sum32_rows(float (&s)[4]) {
+    float t[4];
+    order_rows4(s);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        s[r] += dpp_f<0xB1>(s[r]);
+        s[r] += dpp_f<0x4E>(s[r]);
+        s[r] += dpp_f<0x141>(s[r]);
+        s[r] += dpp_f<0x140>(s[r]);
+    }
+    order_rows4(s);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) t[r] = swz_xor16_f(s[r]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) s[r] += t[r];
+    order_rows4(s);
+}
+// layernorm_tile_regs (esmi_dev.h: same arithmetic, row by row) on row_sum32_rows
+template <int NT>
+__device__ __forceinline__ void layernorm_tile_regs_fenced(f32x16 (&v)[NT], const float (&gg)[NT], const float (&bb)[NT], float eps = 1e-5f) {
+    constexpr int RB = 4;
+    const float inv_c = 1.0f / (float)(32 * NT);
+#pragma unroll
+    for (int r0 = 0; r0 < 16; r0 += RB) {
+        float s[RB], q[RB];
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+            s[r] = 0.0f;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) s[r] += v[nt][r0 + r];
+        }
+        row_sum32_rows(s);
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+            s[r] *= inv_c;
+            q[r] = 0.0f;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const float d = v[nt][r0 + r] - s[r];
+                q[r] = fmaf(d, d, q[r]);
+            }
+        }
+        row_sum32_rows(q);
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+            const float rstd = rsqrt_fast_f32(q[r] * inv_c + eps);
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) v[nt][r0 + r] = fmaf((v[nt][r0 + r] - s[r]) * rstd, gg[nt], bb[nt]);
+        }
+    }
+}
+
 __device__ __forceinline__ int floor_div(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
 template <int ND, int KU>   // dim = 32*ND, ConvTranspose1d kernel KU
@@ -260,6 +326,7 @@ __device__ __forceinline__ void enc_fuse_va_body(const FuseVaP& p) {
         }
         lb[q] = w_.lin_b[0];
     }
+    const float sc[3] = {ctl_scale(p.pitch_s, b), ctl_scale(p.energy_s, b), ctl_scale(p.dur_s, b)};   // prosody controls (scalars)
 #pragma unroll
     for (int nt = 0; nt < ND; ++nt) {
         g2[nt] = p.pred[2].ln2_g[32 * nt + i];
@@ -374,7 +441,7 @@ __device__ __forceinline__ void enc_fuse_va_body(const FuseVaP& p) {
 #ifdef ESMI_E3_STAGED   // development only (profiles/r05_probes/fuse_va_wrong_rows.md): the round-4 experiment that gave wrong rows on the GPU
         layernorm_tile_regs_batched<ND, ESMI_E3_STAGED>(c[q], g1[q], be1[q]);
 #else
-        layernorm_tile_regs<ND>(c[q], g1[q], be1[q]);
+        layernorm_tile_regs_fenced<ND>(c[q], g1[q], be1[q]);
 #endif
 #pragma unroll
         for (int nt = 0; nt < ND; ++nt) {
@@ -401,16 +468,27 @@ __device__ __forceinline__ void enc_fuse_va_body(const FuseVaP& p) {
             for (int r = 0; r < 16; ++r) c[q][nt][r] = fmaxf(c[q][nt][r] + b2[q][nt], 0.0f);
         }
         const bool has_t = q == 0 ? p.pitch_t != nullptr : p.energy_t != nullptr;
+        float dot[16];
+#pragma unroll
+        for (int r0 = 0; r0 < 16; r0 += 4) {
+            float s4[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                s4[r] = 0.0f;
+#pragma unroll
+                for (int nt = 0; nt < ND; ++nt) s4[r] = fmaf(c[q][nt][r0 + r], lw[q][nt], s4[r]);
+            }
+            row_sum32_rows(s4);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dot[r0 + r] = s4[r];
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            float s = 0.0f;
-#pragma unroll
-            for (int nt = 0; nt < ND; ++nt) s = fmaf(c[q][nt][r], lw[q][nt], s);
-            s = row_sum32(s) + lb[q];
+            float s = dot[r] + lb[q];
             if (q == 2) s = fmaxf(s, 0.0f);
             pr[q][r] = s;
             if (q < 2) {   // compile-time branch; the ballots are executed by all lanes
-                const float v = (has_t && !rout[r]) ? tv[q][r] : s;
+                const float v = (has_t && !rout[r]) ? tv[q][r] : s * sc[q];   // (a teacher value is never scaled)
                 int bi = 0;
 #pragma unroll
                 for (int e = 0; e < ND; ++e) {
@@ -431,7 +509,7 @@ __device__ __forceinline__ void enc_fuse_va_body(const FuseVaP& p) {
             for (int nt = 0; nt < ND; ++nt) emb[q][r][nt] = p.pred[q].emb[bidx[q][r] * DIM + 32 * nt + i];
         }
     }
-    layernorm_tile_regs<ND>(c[2], g2, be2);   // duration features (networks.py:161-163)
+    layernorm_tile_regs_fenced<ND>(c[2], g2, be2);   // duration features (networks.py:161-163)
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
         const BufRsrc r_pred = make_rsrc(p.preds[q] + (long)b * p.T, (long)p.T * 4);
@@ -445,7 +523,7 @@ __device__ __forceinline__ void enc_fuse_va_body(const FuseVaP& p) {
             if (q == 2) {
 #pragma unroll
                 for (int nt = 0; nt < ND; ++nt) buf_st(r_feat, frow + 128u * nt, rz[r] ? 0.0f : c[2][nt][r]);
-                float d = p.dur_t ? (float)__builtin_bit_cast(int, tv[2][r]) : rintf(pr[2][r]);   // torch.round: half to even
+                float d = p.dur_t ? (float)__builtin_bit_cast(int, tv[2][r]) : rintf(pr[2][r] * sc[2]);   // torch.round: half to even
                 if (p.mask) {                                                                        // networks.py:381-382
                     if (rz[r]) d = 0.0f;
                     d = fmaxf(d, 0.0f);
@@ -493,7 +571,7 @@ __device__ __forceinline__ void enc_fuse_va_body(const FuseVaP& p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) hh[nt][r] = tanh_fast_f32(hh[nt][r] + hb[nt]);
         }
-        layernorm_tile_regs<4>(hh, hg, hbe);
+        layernorm_tile_regs_fenced<4>(hh, hg, hbe);
         const BufRsrc r_h0 = make_rsrc(p.h0 + (long)b * p.T * D4, (long)p.T * D4 * 4);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {

@@ -23,6 +23,7 @@ struct Pred128P {
     int* cum;                       // (B, T) or NULL
     int* mel_len;                   // (B)
     int B, T;
+    const float *pitch_s, *energy_s, *dur_s;   // prosody controls: (B) scale of the prediction that is bucketized / rounded, or NULL = 1
 };
 // enc_ffn64.h (everything behind the attention of a C = 64, one-head block: one workgroup per utterance)
 struct PostAttn64P {
@@ -81,6 +82,9 @@ struct FuseVaP {
     int wgs_per_b;          // workgroups per utterance
     int useful;             // positions stored per workgroup: 32*nw - 2*halo
     int halo;               // 0: one workgroup covers the sequence, 2: two recomputed rows per side
+    // prosody controls (inference): (B) fp32 each or NULL = 1.  The value that is bucketized is pred * pitch_s[b] / pred * energy_s[b], the
+    // duration is rintf(pred * dur_s[b]); one fp32 multiply each.  Teacher / forced values are never scaled, preds[] stay the raw predictions.
+    const float *pitch_s, *energy_s, *dur_s;
 };
 
 }  // namespace esmi

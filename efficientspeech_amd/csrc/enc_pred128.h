@@ -63,6 +63,7 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_pred128_kernel(const Pred128P p
         if (w == 3 % nw) lds_dma16((v2 ? d.ln2_b : d.ln2_b) + c4, par + PP_LN2B, lane);     // (the upper half lands in the edge slots: overwritten below)
     }
     const float lin_b = d.lin_b[0];
+    const float sc = ctl_scale(q == 0 ? p.pitch_s : (q == 1 ? p.energy_s : p.dur_s), b);   // this predictor's prosody control (a scalar)
     const BufRsrc r_mask = make_rsrc(p.mask ? p.mask + (long)b * p.T : nullptr, p.T);
     const BufRsrc r_feat = make_rsrc(p.feat + (long)b * p.T * 4 * DIM, (long)p.T * 4 * DIM * 4);
     int pos[2];
@@ -138,7 +139,7 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_pred128_kernel(const Pred128P p
         buf_st(r_pred, srow, pr);
         if (q < 2) {   // torch.bucketize(v, edges, right=False) = number of edges strictly below v; the embedding row -> feat
             const float* tv = q == 0 ? p.pitch_t : p.energy_t;
-            const float v = (tv && !rout[t]) ? tv[(long)b * p.T + pos[t]] : pr;
+            const float v = (tv && !rout[t]) ? tv[(long)b * p.T + pos[t]] : pr * sc;   // (a teacher value is never scaled)
             float cnt = 0.0f;
 #pragma unroll
             for (int k4 = 0; k4 < 8; ++k4) {
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_pred128_kernel(const Pred128P p
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
                 buf_st4(r_feat, frow == kBufOOB ? kBufOOB : frow + (unsigned)((3 * DIM + 16 * nt + 4 * g) * 4), rz[t] ? z4 : c[t][nt]);
-            float dval = (p.dur_t && !rout[t]) ? (float)p.dur_t[(long)b * p.T + pos[t]] : rintf(pr);   // torch.round: half to even
+            float dval = (p.dur_t && !rout[t]) ? (float)p.dur_t[(long)b * p.T + pos[t]] : rintf(pr * sc);   // torch.round: half to even
             if (p.mask) {                                                                                 // networks.py:381-382
                 if (rz[t]) dval = 0.0f;
                 dval = fmaxf(dval, 0.0f);

@@ -92,6 +92,7 @@ __device__ __forceinline__ void enc_va16_body(const FuseVaP& p) {
     const unsigned trow = rout ? kBufOOB : (unsigned)(pos * 4);
     const float tv_p = buf_ld(r_pt, trow), tv_e = buf_ld(r_et, trow), tv_d = buf_ld(r_dt, trow);   // teacher values (0 when absent)
     const float lb0 = p.pred[0].lin_b[0], lb1 = p.pred[1].lin_b[0], lb2 = p.pred[2].lin_b[0];
+    const float sc_p = ctl_scale(p.pitch_s, b), sc_e = ctl_scale(p.energy_s, b), sc_d = ctl_scale(p.dur_s, b);   // prosody controls (scalars)
     const int e_i = (lane & 31) < DIM - 1 ? (lane & 31) : DIM - 2;
     const float edge_p = p.pred[0].bins[e_i], edge_e = p.pred[1].bins[e_i];      // bucket edges (dim - 1 of them), to LDS behind the entry barrier
     // Fuse, level 0 and level 1 operands straight from global memory
@@ -318,7 +319,7 @@ __device__ __forceinline__ void enc_va16_body(const FuseVaP& p) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const bool has_t = q == 0 ? p.pitch_t != nullptr : p.energy_t != nullptr;
-        const float v = (has_t && !rout) ? (q == 0 ? tv_p : tv_e) : pr[q];
+        const float v = (has_t && !rout) ? (q == 0 ? tv_p : tv_e) : pr[q] * (q == 0 ? sc_p : sc_e);   // (a teacher value is never scaled)
         const f32x4 e0 = ld4_lds(par + PV_EDGE + 32 * q + 8 * g), e1 = ld4_lds(par + PV_EDGE + 32 * q + 8 * g + 4);
         float cnt = 0.0f;
 #pragma unroll
@@ -346,7 +347,7 @@ __device__ __forceinline__ void enc_va16_body(const FuseVaP& p) {
         layernorm<2>(df, gg, bb);
         if (rz) { df[0] = z4; df[1] = z4; }
     }
-    float dval = p.dur_t ? (float)__builtin_bit_cast(int, tv_d) : rintf(pr[2]);   // torch.round: half to even
+    float dval = p.dur_t ? (float)__builtin_bit_cast(int, tv_d) : rintf(pr[2] * sc_d);   // torch.round: half to even
     if (p.mask) {                                                                  // networks.py:381-382
         if (rz) dval = 0.0f;
         dval = fmaxf(dval, 0.0f);

@@ -111,6 +111,7 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
         if (w == 2 % nw) lds_dma16(p.head_beta + 4 * lane, par + VP_HEADBE, lane);
     }
     const float lb0 = p.pred[0].lin_b[0], lb1 = p.pred[1].lin_b[0], lb2 = p.pred[2].lin_b[0];
+    const float sc_p = ctl_scale(p.pitch_s, b), sc_e = ctl_scale(p.energy_s, b), sc_d = ctl_scale(p.dur_s, b);   // prosody controls (scalars)
     const BufRsrc r_mask = make_rsrc(p.mask ? p.mask + (long)b * p.T : nullptr, p.T);
     const BufRsrc r_feat = make_rsrc(p.feat ? p.feat + (long)b * p.T * 4 * DIM : nullptr, (long)p.T * 4 * DIM * 4);
     const BufRsrc r_pt = make_rsrc(p.pitch_t ? p.pitch_t + (long)b * p.T : nullptr, (long)p.T * 4);
@@ -319,7 +320,7 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const bool has_t = q == 0 ? p.pitch_t != nullptr : p.energy_t != nullptr;
-            const float v = (has_t && !rout[t]) ? (q == 0 ? tv_p[t] : tv_e[t]) : pr[q][t];
+            const float v = (has_t && !rout[t]) ? (q == 0 ? tv_p[t] : tv_e[t]) : pr[q][t] * (q == 0 ? sc_p : sc_e);   // (a teacher value is never scaled)
             float cnt = 0.0f;
 #pragma unroll
             for (int k4 = 0; k4 < 4; ++k4) {
@@ -352,7 +353,7 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
             }
             if (p.h0) to_bop(df, DF[t], lower);
         }
-        float dval = p.dur_t ? (float)__builtin_bit_cast(int, tv_d[t]) : rintf(pr[2][t]);   // torch.round: half to even
+        float dval = p.dur_t ? (float)__builtin_bit_cast(int, tv_d[t]) : rintf(pr[2][t] * sc_d);   // torch.round: half to even
         if (p.mask) {                                                                        // networks.py:381-382
             if (rz[t]) dval = 0.0f;
             dval = fmaxf(dval, 0.0f);

@@ -104,6 +104,7 @@ struct VaTailP {
     const float *pbins, *ebins, *pemb, *eemb;
     float* feat;  // (rows, 4*dim): channels [dim,2dim) pitch emb, [2dim,3dim) energy emb
     int *pitch_idx, *energy_idx, *dur;
+    const float *pitch_s, *energy_s, *dur_s;            // prosody controls: (B) scale of the prediction (never of a teacher value) or NULL = 1
 };
 
 // networks.py:349-384 minus the convolutions: one thread per (row, channel)
@@ -113,8 +114,10 @@ static __global__ void va_tail_kernel(const VaTailP p) {   // one thread = (row,
     if (e >= (long)p.rows * q4) return;
     const int row = (int)(e / q4), c = 4 * (int)(e - (long)row * q4);
     const bool pad = p.mask && p.mask[row];
-    const int pi = bucketize_left(p.pitch_t ? p.pitch_t[row] : p.pitch_pred[row], p.pbins, p.dim - 1);
-    const int ei = bucketize_left(p.energy_t ? p.energy_t[row] : p.energy_pred[row], p.ebins, p.dim - 1);
+    const int b = row / p.T;   // (a wave's rows may belong to two utterances here: the scales are per-lane loads of one or two addresses)
+    const float sc_p = p.pitch_s ? p.pitch_s[b] : 1.0f, sc_e = p.energy_s ? p.energy_s[b] : 1.0f;
+    const int pi = bucketize_left(p.pitch_t ? p.pitch_t[row] : p.pitch_pred[row] * sc_p, p.pbins, p.dim - 1);
+    const int ei = bucketize_left(p.energy_t ? p.energy_t[row] : p.energy_pred[row] * sc_e, p.ebins, p.dim - 1);
     float* fr = p.feat + (long)row * 4 * p.dim;
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
     *reinterpret_cast<f32x4*>(fr + p.dim + c) = pad ? z : *reinterpret_cast<const f32x4*>(p.pemb + (long)pi * p.dim + c);
@@ -122,7 +125,7 @@ static __global__ void va_tail_kernel(const VaTailP p) {   // one thread = (row,
     if (c == 0) {
         if (p.pitch_idx) p.pitch_idx[row] = pi;
         if (p.energy_idx) p.energy_idx[row] = ei;
-        float d = p.dur_t ? (float)p.dur_t[row] : rintf(p.dur_pred[row]);  // torch.round: half to even
+        float d = p.dur_t ? (float)p.dur_t[row] : rintf(p.dur_pred[row] * (p.dur_s ? p.dur_s[b] : 1.0f));  // torch.round: half to even
         if (p.mask) {                                                      // networks.py:381-382
             if (pad) d = 0.0f;
             d = fmaxf(d, 0.0f);

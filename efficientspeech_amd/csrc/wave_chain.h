@@ -9,7 +9,8 @@
 //
 // Rule (profiles/r05_probes/fuse_va_wrong_rows.md): a loop of ds_swizzle round trips that follows a loop of DPP reductions gets a
 // sched_fence() between the two -- with ROCm 7.2 the machine scheduler's interleaving of the two stages over batches of >= 8 rows gave
-// wrong statistics on the GPU (right on the simulator); the row-by-row forms in esmi_dev.h are what the fallback kernels use.
+// wrong statistics on the GPU (right on the simulator); the row-by-row forms in esmi_dev.h are what the fallback kernels use
+// (enc_fuse_va.h: row_sum32_rows, which orders the two stages by data flow -- there the row-by-row form went wrong too after an edit elsewhere).
 #pragma once
 #include "esmi_dev.h"
 

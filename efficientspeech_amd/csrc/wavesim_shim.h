@@ -385,6 +385,18 @@ __device__ __forceinline__ int uniform_i(int v) {
     return __builtin_amdgcn_readfirstlane(v);
 #endif
 }
+// a per-utterance prosody control (enc_params.h): scale[b], 1 when the array is absent.  b is wave-uniform (a blockIdx expression) and the
+// array is read-only for the kernel's life, so the read goes through the constant address space: ONE scalar load (s_load_dword) into an
+// SGPR per wave -- no VGPR, no per-row load, and nothing added to the vector-memory queue that the LDS-DMA stages count by hand (a plain
+// `scale[b]` is a global_load_dword of a uniform address into a VGPR: hipcc cannot prove the array invariant)
+__device__ __forceinline__ float ctl_scale(const float* scale, int b) {
+#ifdef ESMI_WAVESIM
+    return scale ? scale[b] : 1.0f;
+#else
+    typedef const __attribute__((address_space(4))) float* const_f32_ptr;
+    return scale ? *(const_f32_ptr)(scale + uniform_i(b)) : 1.0f;
+#endif
+}
 // LDS-DMA (global_load_lds_dwordx4): 16 bytes per lane from this lane's global address straight into LDS at `lds_wave_base` + 16 lane
 // (the LDS address is wave-uniform + the lane's slot: that is how the instruction addresses), no staging registers
 __device__ __forceinline__ void lds_dma16(const void* gsrc_lane, void* lds_wave_base, int lane) {

@@ -89,6 +89,48 @@ def _mask_u8(mask):
     return mask.detach().to(torch.bool).contiguous().view(torch.uint8)
 
 
+CONTROL_KEYS = ("pitch_control", "energy_control", "duration_control")
+
+
+def _prosody_controls(x, B, dev, train=False):
+    """The per-utterance prosody controls of an input dict (extension keys `pitch_control`, `energy_control`, `duration_control`;
+    the reference declares `control=1.` and never wires it, layers/networks.py:128-149) -> (`_lib.ProsodyControl` or None when no
+    key is present, the (B,) fp32 device tensors it points into -- keep them alive until the launch is enqueued).
+
+    A value is a Python number (broadcast over the batch) or a tensor of shape (B,) or ().  The prediction that is bucketized
+    (pitch, energy) or rounded (duration) is multiplied by it inside the kernels; the returned predictions stay the raw ones.
+    Numbers are validated here (finite; `duration_control >= 0`).  Tensors are NOT: reading a device tensor would cost a host
+    synchronisation per forward, so a non-finite or negative entry is the caller's responsibility (a negative duration scale
+    yields zero frames for that utterance).  ValueError: a control while training, `duration_control` together with
+    `duration_forced` (a forced duration is final; pitch / energy controls combine with it), a wrong shape."""
+    import math
+    import numbers
+    given = [k for k in CONTROL_KEYS if x.get(k) is not None]
+    if not given:
+        return None, ()
+    if train:
+        raise ValueError(f"{given[0]}: the prosody controls are an inference extension (train=True takes teacher values)")
+    if "duration_control" in given and x.get("duration_forced") is not None:
+        raise ValueError("duration_control together with duration_forced: a forced duration is final and is never scaled")
+    ctl, keep = _lib.ProsodyControl(), []
+    for k in given:
+        v = x[k]
+        if isinstance(v, numbers.Real):
+            v = float(v)
+            if not math.isfinite(v) or (k == "duration_control" and v < 0.0):
+                raise ValueError(f"{k} = {v}: must be finite" + (" and >= 0" if k == "duration_control" else ""))
+            t = torch.full((B,), v, dtype=torch.float32, device=dev)
+        elif torch.is_tensor(v):
+            if tuple(v.shape) not in ((B,), ()):
+                raise ValueError(f"{k}: shape {tuple(v.shape)}, expected ({B},) (one scale per utterance) or ()")
+            t = v.detach().to(device=dev, dtype=torch.float32).expand(B).contiguous()
+        else:
+            raise ValueError(f"{k}: a number or a tensor of shape ({B},) or (), not {type(v).__name__}")
+        keep.append(t)
+        setattr(ctl, k.replace("control", "scale"), _ptr(t))
+    return ctl, tuple(keep)
+
+
 def get_mask_from_lengths(lengths, max_len=None):
     """utils/tools.py:43-51: mask[b, t] = t >= lengths[b] (True marks padding)."""
     if max_len is None:
@@ -670,9 +712,12 @@ class PhonemeEncoder(_PackedModule):
                                         for p in d.parameters()], build)
 
     def _encode(self, x, train=False, need_lmax=True, head=None):
-        """Everything up to (and including) the duration scan; nothing frame-rate is materialised."""
+        """Everything up to (and including) the duration scan; nothing frame-rate is materialised.
+        Inference extension keys: `duration_forced`, and the per-utterance prosody controls `pitch_control`, `energy_control`,
+        `duration_control` (numbers are validated on the host, device tensors are not synchronised for it: `_prosody_controls`)."""
         phoneme = x["phoneme"]
         B = phoneme.shape[0]
+        ctl, _ctl_keep = _prosody_controls(x, B, self.encoder.embed.weight.device, train)   # (_ctl_keep: alive until the launches are enqueued)
         phoneme_mask = x["phoneme_mask"] if B > 1 else None           # KeyError for B>1, as the reference (:338)
         dev = self.encoder.embed.weight.device
         lib, stream = _runtime(self.encoder.embed.weight)
@@ -709,13 +754,19 @@ class PhonemeEncoder(_PackedModule):
                 _ptr(pitch_t), _ptr(energy_t), _ptr(dur_t), _ptr(feat), _ptr(preds[0]), _ptr(preds[1]), _ptr(preds[2]),
                 _ptr(idxs[0]), _ptr(idxs[1]), _ptr(dur), _ptr(cum), _ptr(mel_len))
         plan = _lib.current_plan()
+
+        def stage(head_p, h0_p):              # (with controls: the _ctl entry point, same arguments + the scales)
+            if ctl is None:
+                lib.esmi_fuse_variance_adaptor_f32(*args, head_p, h0_p, plan, _ptr(ws), ws_bytes, stream)
+            else:
+                lib.esmi_fuse_variance_adaptor_ctl_f32(*args, head_p, h0_p, plan, _ptr(ws), ws_bytes, stream, C.byref(ctl))
         if h0 is not None:
             try:
-                lib.esmi_fuse_variance_adaptor_f32(*args, C.byref(head[0]), _ptr(h0), plan, _ptr(ws), ws_bytes, stream)
+                stage(C.byref(head[0]), _ptr(h0))
             except _lib.Unsupported:           # long sequences / other widths: the decoder runs its first stage itself
                 h0 = None
         if h0 is None:
-            lib.esmi_fuse_variance_adaptor_f32(*args, None, None, plan, _ptr(ws), ws_bytes, stream)
+            stage(None, None)
         enc = dict(feat=feat, mask_u8=m8, pitch=preds[0], energy=preds[1], duration=preds[2], pitch_idx=idxs[0],
                    energy_idx=idxs[1], dur=dur, cum=cum, mel_len=mel_len, lmax=None, feats=feats, h0=h0)
         if need_lmax:
@@ -852,10 +903,15 @@ class Phoneme2Mel(nn.Module):
             self._fwd_args, self._fwd_keep, self._fwd_ident = a, (blocks, embed, fw, preds, blob, head), ident
         return self._fwd_args
 
-    def _launch(self, x, stage=0, state=None):
+    def _launch(self, x, stage=0, state=None, taps=False):
         """Enqueue the inference forward (stage 0), its encoder side only (1), or the decoder (2) on the `state` a stage-1
         call returned (a multi-GPU caller MAX-reduces `state.lmax` in between).  -> namespace with mel, mel_len,
-        duration (B,T,1), lmax (device scalar or None)."""
+        duration (B,T,1), lmax (device scalar or None).
+        Inference extension keys of x: `duration_forced`, `max_mel_len` (`max_mel_len_exact`), and the per-utterance prosody controls
+        `pitch_control`, `energy_control`, `duration_control` (a number or a (B,) / () tensor each; numbers are validated on the host,
+        device tensors are not synchronised for it: `_prosody_controls`).
+        taps (tests): also return what `PhonemeEncoder._encode` exposes -- `state.taps` = pitch, energy (B,T) raw predictions,
+        pitch_idx, energy_idx, dur, cum (B,T) int32."""
         from types import SimpleNamespace
         w = self.decoder.mel_linear.weight
         lib, stream = _runtime(w)
@@ -872,7 +928,13 @@ class Phoneme2Mel(nn.Module):
             dur_t = None
             if "duration_forced" in x:                                # extension: inject durations at inference
                 dur_t = x["duration_forced"].detach().reshape(B, T).to(device=dev, dtype=torch.int32).contiguous()
+            ctl, ctl_keep = _prosody_controls(x, B, dev)
+            tap = None
+            if taps:
+                tap = {k: torch.empty((B, T), dtype=torch.float32 if k in ("pitch", "energy") else torch.int32, device=dev)
+                       for k in ("pitch", "energy", "pitch_idx", "energy_idx", "dur", "cum")}
             st = SimpleNamespace(ids=ids, m8=_mask_u8(phoneme_mask), dur_t=dur_t, B=B, T=T, lmax=None, mel=None, L_out=None,
+                                 ctl=ctl, ctl_keep=ctl_keep, taps=tap,
                                  lmax_host=None, plan=_lib.current_plan(),
                                  mel_len=torch.empty((B,), dtype=torch.int32, device=dev),
                                  duration=torch.empty((B, T, 1), dtype=torch.float32, device=dev))
@@ -885,7 +947,9 @@ class Phoneme2Mel(nn.Module):
         a.B, a.T, a.plan = st.B, st.T, st.plan
         a.ids, a.mask, a.dur_forced = _ptr(st.ids), _ptr(st.m8), _ptr(st.dur_t)
         a.duration_pred, a.mel_len, a.lmax_dev = _ptr(st.duration), _ptr(st.mel_len), _ptr(st.lmax)
-        a.pitch_pred = a.energy_pred = a.pitch_idx = a.energy_idx = a.dur = a.cum = None
+        tp = st.taps or {}
+        a.pitch_pred, a.energy_pred, a.pitch_idx, a.energy_idx = (_ptr(tp.get(k)) for k in ("pitch", "energy", "pitch_idx", "energy_idx"))
+        a.dur, a.cum = _ptr(tp.get("dur")), _ptr(tp.get("cum"))
         if stage != 2:
             a.L_out = st.L_out or 0                                   # known output length: the arena's scratch also fits the decoder's carried rows
             nbytes = lib.esmi_forward_arena_bytes(C.byref(a))
@@ -894,13 +958,19 @@ class Phoneme2Mel(nn.Module):
         rf = getattr(self, "_range_flag", None)                       # validation mode only (check_activation_range)
         a.range_flag = _ptr(rf)
         dec = self.decoder
+
+        def forward(stage_):                   # (with controls: the _ctl entry point; stage 2 ignores them)
+            if st.ctl is None:
+                lib.esmi_phoneme2mel_forward_f32(C.byref(a), stage_, stream)
+            else:
+                lib.esmi_phoneme2mel_forward_ctl_f32(C.byref(a), C.byref(st.ctl), stage_, stream)
         timed = False
         if stage != 1 and dec.timing is not None:                     # bench.py: HIP events around the decoder launch only
             dec._launches += 1
             timed = dec._launches % dec.timing_every == 0
         if stage != 2 and (stage == 1 or st.L_out is None or timed):  # encoder side as its own call
             a.L_out, a.lmax_host, a.mel = 0, 0, None
-            lib.esmi_phoneme2mel_forward_f32(C.byref(a), 1, stream)
+            forward(1)
             if stage == 1:
                 return st
             stage = 2
@@ -911,9 +981,9 @@ class Phoneme2Mel(nn.Module):
         if timed and st.L_out > 0:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
-            lib.esmi_phoneme2mel_forward_f32(C.byref(a), stage, stream)
+            forward(stage)
             ev[1].record()
             dec.timing.append(ev)
         else:
-            lib.esmi_phoneme2mel_forward_f32(C.byref(a), stage, stream)
+            forward(stage)
         return st

@@ -13,7 +13,7 @@ the device, no work for the frames behind an utterance's end in the stages of at
 import numpy as np
 import torch
 
-from .networks import get_mask_from_lengths
+from .networks import CONTROL_KEYS, get_mask_from_lengths
 
 
 class BucketedSynthesizer:
@@ -47,12 +47,21 @@ class BucketedSynthesizer:
         return 1.0 - float(lengths.sum()) / max(slots, 1)
 
     @torch.no_grad()
-    def __call__(self, sequences, extra=None):
+    def __call__(self, sequences, extra=None, controls=None):
         """sequences: list of 1-D integer phoneme id sequences.  -> list (request order) of (mel (L_i, n_mel), duration (T_i,)), or
         with a vocoder of (wav (L_i * hop,), mel (L_i, n_mel), duration (T_i,)).
-        `extra(indices, T)` may return additional input-dict entries for a batch (e.g. forced durations)."""
+        `extra(indices, T)` may return additional input-dict entries for a batch (e.g. forced durations).
+        `controls`: per-REQUEST prosody scales, a dict with any of `pitch_control`, `energy_control`, `duration_control`, each an array
+        of len(sequences) numbers; every batch gets its requests' entries (unrelated requests share a batch, each keeps its own scale)."""
         dev = self.net.decoder.mel_linear.weight.device
         lengths = [int(len(s)) for s in sequences]
+        controls = dict(controls or {})
+        for k, v in controls.items():
+            if k not in CONTROL_KEYS:
+                raise ValueError(f"controls: unknown key {k!r} (one of {', '.join(CONTROL_KEYS)})")
+            controls[k] = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=np.float32)
+            if controls[k].shape != (len(sequences),):
+                raise ValueError(f"controls[{k!r}]: shape {controls[k].shape}, expected one scale per request ({len(sequences)},)")
         out = [None] * len(sequences)
         for idx, T in self.plan(lengths):
             ids = np.full((len(idx), T), self.pad_id, np.int32)
@@ -63,6 +72,8 @@ class BucketedSynthesizer:
                 x["phoneme_mask"] = get_mask_from_lengths(torch.tensor([lengths[i] for i in idx], device=dev), T)
             if extra is not None:
                 x.update(extra(idx, T))
+            for k, v in controls.items():                      # this batch's requests, in the batch's order
+                x[k] = torch.from_numpy(v[idx]).to(dev)
             mel, mel_len, dur = self.net(x)
             wav = None
             if self.vocoder is not None and mel.shape[1] > 0:      # (launched before the lengths are read back)

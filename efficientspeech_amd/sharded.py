@@ -39,7 +39,9 @@ def shard_batch(x, rank, world):
     B) is padded, not refused: every rank gets ceil(B / world) utterances (equal shards are what all_gather_into_tensor needs),
     the missing ones being copies of the shard's last utterance -- or of the batch's last one for a rank that owns none.  The
     copies only cost their compute: they are duplicates of real utterances, so they cannot change the batch's padded length, and
-    `unpad_gathered` drops their rows (they sit behind the B real ones in the gathered tensors)."""
+    `unpad_gathered` drops their rows (they sit behind the B real ones in the gathered tensors).
+    The per-utterance prosody controls (`networks.CONTROL_KEYS`) given as (B,) tensors are batch-leading tensors like any other: each
+    rank gets its utterances' scales; a number or a () tensor holds for the whole batch and travels unchanged."""
     B = x["phoneme"].shape[0]
     lo, hi, per = shard_rows(B, rank, world)
     out = {}
@@ -104,6 +106,16 @@ def sharded_forward(net, x_full, group=None):
     return tuple(outs)
 
 
+def _refuse_controls_in_graph(x):
+    """The graph-replay path captures the encoder side once, with whatever scales that call had: a control key would be baked in (a
+    number) or silently dropped (a key the captured step did not have).  Not built: refuse, never drop."""
+    from .networks import CONTROL_KEYS
+    given = [k for k in CONTROL_KEYS if x.get(k) is not None]
+    if given:
+        raise NotImplementedError(f"{given[0]}: the prosody controls are not captured by the graph-replay path (use_graph / "
+                                  "GraphedForward); run this step without use_graph")
+
+
 class GraphedForward:
     """The inference forward of one fixed shape as two hipGraphs (encoder side, mel decoder) so that a step costs
     two graph launches instead of ~10 kernel launches + the Python between them.  Needs the `max_mel_len` bound
@@ -113,6 +125,7 @@ class GraphedForward:
 
     def __init__(self, net, x, nbuf=3, warmup=3):
         assert "max_mel_len" in x, "graph replay needs a static output length (x['max_mel_len'])"
+        _refuse_controls_in_graph(x)
         self.net = net
         self.L = int(x["max_mel_len"])
         self.x = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in x.items()}
@@ -140,6 +153,7 @@ class GraphedForward:
         self.i = 0
 
     def load(self, x):
+        _refuse_controls_in_graph(x)
         for k, v in x.items():
             if torch.is_tensor(v) and v.data_ptr() != self.x[k].data_ptr():
                 self.x[k].copy_(v, non_blocking=True)

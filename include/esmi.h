@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define ESMI_VERSION 501 /* 0.5.1: esmi_train_conv_ln_fwd_f32, then esmi_hifigan_generator_ragged_f32 (additions; nothing else changed shape).  0.5.0 (round 5): esmi_mel_decoder_clock_probe;
+#define ESMI_VERSION 501 /* 0.5.1: esmi_train_conv_ln_fwd_f32, then esmi_hifigan_generator_ragged_f32, then esmi_prosody_control and the three
+                            *_ctl_f32 entry points (additions; nothing else changed shape).  0.5.0 (round 5): esmi_mel_decoder_clock_probe;
                             0.4.0: esmi_decoder_head.proj_w (the decoder's first stage at phoneme rate for every model size:
                           * esmi_decoder_head_f32).  0.3.0: training entry points changed shape (esmi_conv_desc: act / packed_fwd / packed_grad; LayerNorm with
                           * residual / row mask / activation arguments; esmi_train_loss_args.grad_seed; esmi_train_pack_weights_f32,
@@ -243,6 +244,29 @@ int esmi_variance_adaptor_f32(const esmi_predictor_weights* pitch, const esmi_pr
                               int32_t* dur,                 /* (B,T) integer repeat counts              */
                               void* workspace, size_t workspace_bytes, esmi_stream_t stream);
 
+/* Per-utterance prosody controls at inference (extension): how high, how loud and how fast each utterance of the batch is spoken.
+ * The reference declares the hook and never wires it: AcousticDecoder.get_pitch_embedding / get_energy_embedding take `control=1.`
+ * and carry a commented-out `pred = pred * control` (layers/networks.py:128-149).  Here, per utterance b:
+ *   pitch / energy: the value that is bucketized is pred * scale[b] -- one fp32 multiply of the fp32 prediction, in the prediction branch
+ *                   only (networks.py:131-133, :139-141); a teacher value (:129-130, :137-138) is never scaled;
+ *   duration:       d = rintf(duration_pred * scale[b]) in place of torch.round(duration_pred) (networks.py:379-380), then the same
+ *                   masked_fill(mask, 0).clamp(min=0) (:381-382); the scan, cum and mel_len follow from d.  A forced duration is final.
+ * The predictions that are RETURNED (pitch_pred, energy_pred, duration_pred) stay the raw ones, as the reference's local
+ * `pred * control` would leave them.  A NULL array, and an array of 1.0f, give results bit-identical to the call without controls.
+ * A scale together with the matching teacher / forced pointer is a caller error: ESMI_ERR_ARG, nothing launched.  The scales are read on
+ * the device; they are not validated (a negative duration scale gives zero durations through the clamp, or through the scan's max(d, 0)
+ * on the B == 1 path). */
+typedef struct esmi_prosody_control {      /* each: (B) device fp32, or NULL = 1 */
+    const float* pitch_scale; const float* energy_scale; const float* duration_scale;
+} esmi_prosody_control;
+/* esmi_variance_adaptor_f32 with the controls (ctl == NULL: exactly that call) */
+int esmi_variance_adaptor_ctl_f32(const esmi_predictor_weights* pitch, const esmi_predictor_weights* energy,
+                                  const esmi_predictor_weights* duration, int dim, int B, int T, const uint8_t* mask,
+                                  const float* pitch_target, const float* energy_target, const int32_t* duration_target,
+                                  float* feat, float* pitch_pred, float* energy_pred, float* duration_pred,
+                                  int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur,
+                                  void* workspace, size_t workspace_bytes, esmi_stream_t stream, const esmi_prosody_control* ctl);
+
 /* Fuse + variance adaptor in ONE call (what PhonemeEncoder.forward does between the encoder and the length
  * regulator, networks.py:347-384); uses a single fused kernel when the shape allows (dim 32 or 64), else the two
  * calls above.  `feat` (B,T,4*dim) is fully written.  Arguments as in esmi_fuse_f32 / esmi_variance_adaptor_f32.
@@ -280,6 +304,17 @@ int esmi_fuse_variance_adaptor_f32(const esmi_fuse_weights* fuse, int depth, int
                                       nothing launched: call again without h0)                                     */
                                    int plan,                                 /* ESMI_FUSE_* bits of this call     */
                                    void* workspace, size_t workspace_bytes, esmi_stream_t stream);
+/* ... with the prosody controls (esmi_prosody_control above; layers/networks.py:128-149, :379-382): whichever kernel serves the shape
+ * applies them.  ctl == NULL: exactly esmi_fuse_variance_adaptor_f32. */
+int esmi_fuse_variance_adaptor_ctl_f32(const esmi_fuse_weights* fuse, int depth, int dim, int kernel, int B, int T,
+                                       const float* const* feats, const int* n_i, const esmi_predictor_weights* pitch,
+                                       const esmi_predictor_weights* energy, const esmi_predictor_weights* duration,
+                                       const uint8_t* mask, const float* pitch_target, const float* energy_target,
+                                       const int32_t* duration_target, float* feat, float* pitch_pred, float* energy_pred,
+                                       float* duration_pred, int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur,
+                                       int32_t* cum, int32_t* mel_len, const esmi_decoder_head* head, float* h0, int plan,
+                                       void* workspace, size_t workspace_bytes, esmi_stream_t stream,
+                                       const esmi_prosody_control* ctl);
 
 /* ------------------------------------------------------------------ module-level forwards
  * The reference's sub-modules called on their own (one kernel per reference op, fp32 MFMA):
@@ -442,6 +477,10 @@ size_t esmi_forward_arena_bytes(const esmi_forward_args* a);
 /* stage = 0: everything; 1: encoder side only (up to cum / mel_len / lmax_dev / h0, kept in the arena); 2: mel decoder only,
  * on the arena a stage-1 call filled (same args) -- lets a multi-GPU caller put its MAX all-reduce of lmax_dev in between. */
 int esmi_phoneme2mel_forward_f32(const esmi_forward_args* a, int stage, esmi_stream_t stream);
+/* ... with per-utterance prosody controls (esmi_prosody_control; the reference's unwired `control`, layers/networks.py:128-149, and the
+ * rounding of :379-382): applied inside the encoder-side kernels, the one-launch form included.  ctl == NULL: exactly the call above.
+ * duration_scale together with a->dur_forced is ESMI_ERR_ARG (nothing launched).  Stage 2 (the decoder alone) ignores ctl. */
+int esmi_phoneme2mel_forward_ctl_f32(const esmi_forward_args* a, const esmi_prosody_control* ctl, int stage, esmi_stream_t stream);
 
 /* ------------------------------------------------------------------ HiFi-GAN generator (the vocoder behind model.py:161-162)
  * hifigan/models.py:84-135 Generator.forward with ResBlock1 (:20-58) or ResBlock2 (:61-82), weights as after
