@@ -529,7 +529,7 @@ __device__ __forceinline__ void enc_fuse_va_body(const FuseVaP& p) {
                     d = fmaxf(d, 0.0f);
                 }
                 buf_st_i(r_dur, srow, (int)d);
-                if (p.cum && i == 0) sdur[r0 + tile_row(r, lane)] = rout[r] ? 0 : max((int)d, 0);
+                if (p.cum && i == 0) sdur[r0 + tile_row(r, lane)] = va_scan_term(d, rout[r]);
             } else {
 #pragma unroll
                 for (int nt = 0; nt < ND; ++nt) buf_st(r_feat, frow + 128u * nt, rz[r] ? 0.0f : emb[q][r][nt]);

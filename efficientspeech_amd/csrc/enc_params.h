@@ -83,7 +83,7 @@ struct FuseVaP {
     int useful;             // positions stored per workgroup: 32*nw - 2*halo
     int halo;               // 0: one workgroup covers the sequence, 2: two recomputed rows per side
     // prosody controls (inference): (B) fp32 each or NULL = 1.  The value that is bucketized is pred * pitch_s[b] / pred * energy_s[b], the
-    // duration is rintf(pred * dur_s[b]); one fp32 multiply each.  Teacher / forced values are never scaled, preds[] stay the raw predictions.
+    // duration rounds pred * dur_s[b]; one fp32 multiply each (va_decide.h).  Teacher / forced values are never scaled, preds[] stay the raw predictions.
     const float *pitch_s, *energy_s, *dur_s;
 };
 

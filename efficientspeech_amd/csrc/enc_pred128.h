@@ -18,6 +18,7 @@
 #pragma once
 #include "enc_params.h"
 #include "reg_tile.h"
+#include "va_decide.h"
 
 namespace esmi {
 
@@ -139,15 +140,9 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_pred128_kernel(const Pred128P p
         buf_st(r_pred, srow, pr);
         if (q < 2) {   // torch.bucketize(v, edges, right=False) = number of edges strictly below v; the embedding row -> feat
             const float* tv = q == 0 ? p.pitch_t : p.energy_t;
-            const float v = (tv && !rout[t]) ? tv[(long)b * p.T + pos[t]] : pr * sc;   // (a teacher value is never scaled)
-            float cnt = 0.0f;
-#pragma unroll
-            for (int k4 = 0; k4 < 8; ++k4) {
-                const f32x4 e0 = ld4_lds(par + PP_EDGE + 32 * g + 4 * k4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) cnt += e0[e] < v ? 1.0f : 0.0f;
-            }
-            const int bidx = (int)row_sum4(cnt);
+            // (the rules of va_decide.h, called per side so that only a teacher row loads its teacher value)
+            const float v = (tv && !rout[t]) ? va_bucket_input(true, tv[(long)b * p.T + pos[t]], 0.0f, 1.0f) : va_bucket_input(false, 0.0f, pr, sc);
+            const int bidx = (int)row_sum4(bucket_count_lds<8>(par + PP_EDGE + 32 * g, v));
             int* idx = q == 0 ? p.pitch_idx : p.energy_idx;
             if (idx) {
                 const BufRsrc r_i = make_rsrc(idx + (long)b * p.T, (long)p.T * 4);
@@ -168,12 +163,9 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_pred128_kernel(const Pred128P p
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
                 buf_st4(r_feat, frow == kBufOOB ? kBufOOB : frow + (unsigned)((3 * DIM + 16 * nt + 4 * g) * 4), rz[t] ? z4 : c[t][nt]);
-            float dval = (p.dur_t && !rout[t]) ? (float)p.dur_t[(long)b * p.T + pos[t]] : rintf(pr * sc);   // torch.round: half to even
-            if (p.mask) {                                                                                 // networks.py:381-382
-                if (rz[t]) dval = 0.0f;
-                dval = fmaxf(dval, 0.0f);
-            }
-            if (g == 0) sdur[pos[t]] = rout[t] ? 0 : max((int)dval, 0);
+            const float dval = (p.dur_t && !rout[t]) ? va_duration(true, (float)p.dur_t[(long)b * p.T + pos[t]], 0.0f, 1.0f, p.mask != nullptr, rz[t])
+                                                     : va_duration(false, 0.0f, pr, sc, p.mask != nullptr, rz[t]);
+            if (g == 0) sdur[pos[t]] = va_scan_term(dval, rout[t]);
             const BufRsrc r_dur = make_rsrc(p.dur + (long)b * p.T, (long)p.T * 4);
             buf_st_i(r_dur, srow, (int)dval);
         }

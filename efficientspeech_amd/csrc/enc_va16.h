@@ -17,6 +17,7 @@
 #pragma once
 #include "chain16.h"
 #include "enc_fuse_va.h"
+#include "va_decide.h"
 
 namespace esmi {
 
@@ -319,12 +320,8 @@ __device__ __forceinline__ void enc_va16_body(const FuseVaP& p) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const bool has_t = q == 0 ? p.pitch_t != nullptr : p.energy_t != nullptr;
-        const float v = (has_t && !rout) ? (q == 0 ? tv_p : tv_e) : pr[q] * (q == 0 ? sc_p : sc_e);   // (a teacher value is never scaled)
-        const f32x4 e0 = ld4_lds(par + PV_EDGE + 32 * q + 8 * g), e1 = ld4_lds(par + PV_EDGE + 32 * q + 8 * g + 4);
-        float cnt = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) cnt += (e0[e] < v ? 1.0f : 0.0f) + (e1[e] < v ? 1.0f : 0.0f);
-        bidx[q] = (int)row_sum4(cnt);
+        const float v = va_bucket_input(has_t && !rout, q == 0 ? tv_p : tv_e, pr[q], q == 0 ? sc_p : sc_e);
+        bidx[q] = (int)row_sum4(bucket_count_lds<2>(par + PV_EDGE + 32 * q + 8 * g, v));
     }
     // embedding rows from the LDS copies of the tables, in the head's B-operand order (k-step 1 = pitch, 2 = energy: the lane's eight
     // channels c0 .. c0 + 3, c0 + 8 .. c0 + 11) -- stored to feat from the same registers
@@ -347,12 +344,8 @@ __device__ __forceinline__ void enc_va16_body(const FuseVaP& p) {
         layernorm<2>(df, gg, bb);
         if (rz) { df[0] = z4; df[1] = z4; }
     }
-    float dval = p.dur_t ? (float)__builtin_bit_cast(int, tv_d) : rintf(pr[2] * sc_d);   // torch.round: half to even
-    if (p.mask) {                                                                  // networks.py:381-382
-        if (rz) dval = 0.0f;
-        dval = fmaxf(dval, 0.0f);
-    }
-    if (p.cum && g == 0) sdur[pos] = rout ? 0 : max((int)dval, 0);
+    const float dval = va_duration(p.dur_t != nullptr, (float)__builtin_bit_cast(int, tv_d), pr[2], sc_d, p.mask != nullptr, rz);
+    if (p.cum && g == 0) sdur[pos] = va_scan_term(dval, rout);
     ESMI_CT();   // 6: predictions done
     // ---------------- outputs behind the last barrier that waits for the vector-memory queue (no barrier waits for a store)
     auto store_outputs = [&]() __attribute__((always_inline)) {
@@ -443,25 +436,7 @@ __device__ __forceinline__ void enc_va16_body(const FuseVaP& p) {
     ESMI_CT();   // 9: outputs issued
     if (p.cum) {   // FeatureUpsampler's scan (networks.py:233-244) while the durations are still on the CU; T <= 128 here
         wg_sync_lds();
-        if (w == 0) {
-            const int per = (p.T + 63) / 64, q0 = lane * per;
-            int local = 0;
-            for (int q = 0; q < per; ++q) local += (q0 + q < p.T) ? sdur[q0 + q] : 0;
-            int incl = local;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int v = shfl_up_i(incl, d);
-                if (lane >= d) incl += v;
-            }
-            const BufRsrc r_cum = make_rsrc(p.cum + (long)b * p.T, (long)p.T * 4);
-            int run = incl - local;
-            for (int q = 0; q < per; ++q) {
-                run += (q0 + q < p.T) ? sdur[q0 + q] : 0;
-                buf_st_i(r_cum, (unsigned)((q0 + q) * 4), run);      // positions >= T fall off the buffer end
-            }
-            const int total = shfl_i(incl, 63);
-            if (lane == 0) p.mel_len[b] = total;
-        }
+        if (w == 0) wg_scan_durations(sdur, p.T, p.cum + (long)b * p.T, p.mel_len + b, lane);
     }
 }
 

@@ -26,6 +26,7 @@
 #pragma once
 #include "enc_params.h"
 #include "reg_tile.h"
+#include "va_decide.h"
 
 namespace esmi {
 
@@ -320,15 +321,8 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const bool has_t = q == 0 ? p.pitch_t != nullptr : p.energy_t != nullptr;
-            const float v = (has_t && !rout[t]) ? (q == 0 ? tv_p[t] : tv_e[t]) : pr[q][t] * (q == 0 ? sc_p : sc_e);   // (a teacher value is never scaled)
-            float cnt = 0.0f;
-#pragma unroll
-            for (int k4 = 0; k4 < 4; ++k4) {
-                const f32x4 e0 = ld4_lds(par + VP_EDGE + 64 * q + 16 * g + 4 * k4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) cnt += e0[e] < v ? 1.0f : 0.0f;
-            }
-            bidx[q] = (int)row_sum4(cnt);
+            const float v = va_bucket_input(has_t && !rout[t], q == 0 ? tv_p[t] : tv_e[t], pr[q][t], q == 0 ? sc_p : sc_e);
+            bidx[q] = (int)row_sum4(bucket_count_lds<4>(par + VP_EDGE + 64 * q + 16 * g, v));
             hidx[t][q] = bidx[q];
             if (p.feat) {           // the embedding row: lane group g copies floats [16 g, 16 g + 16) of it
                 const float* row = (q == 0 ? p.pred[0].emb : p.pred[1].emb) + bidx[q] * DIM + 16 * g;
@@ -353,12 +347,8 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
             }
             if (p.h0) to_bop(df, DF[t], lower);
         }
-        float dval = p.dur_t ? (float)__builtin_bit_cast(int, tv_d[t]) : rintf(pr[2][t] * sc_d);   // torch.round: half to even
-        if (p.mask) {                                                                        // networks.py:381-382
-            if (rz[t]) dval = 0.0f;
-            dval = fmaxf(dval, 0.0f);
-        }
-        if (p.cum && g == 0) sdur[pos[t]] = rout[t] ? 0 : max((int)dval, 0);
+        const float dval = va_duration(p.dur_t != nullptr, (float)__builtin_bit_cast(int, tv_d[t]), pr[2][t], sc_d, p.mask != nullptr, rz[t]);
+        if (p.cum && g == 0) sdur[pos[t]] = va_scan_term(dval, rout[t]);
         const unsigned srow = (!rout[t] && g == 0) ? (unsigned)(pos[t] * 4) : kBufOOB;   // one lane per row
 #pragma unroll
         for (int q = 0; q < 3; ++q) {

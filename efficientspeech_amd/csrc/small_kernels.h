@@ -3,6 +3,7 @@
 // optional materialisation of the upsampled features.
 #pragma once
 #include "esmi_dev.h"
+#include "va_decide.h"
 
 namespace esmi {
 
@@ -116,8 +117,11 @@ static __global__ void va_tail_kernel(const VaTailP p) {   // one thread = (row,
     const bool pad = p.mask && p.mask[row];
     const int b = row / p.T;   // (a wave's rows may belong to two utterances here: the scales are per-lane loads of one or two addresses)
     const float sc_p = p.pitch_s ? p.pitch_s[b] : 1.0f, sc_e = p.energy_s ? p.energy_s[b] : 1.0f;
-    const int pi = bucketize_left(p.pitch_t ? p.pitch_t[row] : p.pitch_pred[row] * sc_p, p.pbins, p.dim - 1);
-    const int ei = bucketize_left(p.energy_t ? p.energy_t[row] : p.energy_pred[row] * sc_e, p.ebins, p.dim - 1);
+    // (the rules of va_decide.h, called per side so that only the side's own value is loaded)
+    const int pi = bucketize_left(p.pitch_t ? va_bucket_input(true, p.pitch_t[row], 0.0f, 1.0f) : va_bucket_input(false, 0.0f, p.pitch_pred[row], sc_p),
+                                  p.pbins, p.dim - 1);
+    const int ei = bucketize_left(p.energy_t ? va_bucket_input(true, p.energy_t[row], 0.0f, 1.0f) : va_bucket_input(false, 0.0f, p.energy_pred[row], sc_e),
+                                  p.ebins, p.dim - 1);
     float* fr = p.feat + (long)row * 4 * p.dim;
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
     *reinterpret_cast<f32x4*>(fr + p.dim + c) = pad ? z : *reinterpret_cast<const f32x4*>(p.pemb + (long)pi * p.dim + c);
@@ -125,11 +129,8 @@ static __global__ void va_tail_kernel(const VaTailP p) {   // one thread = (row,
     if (c == 0) {
         if (p.pitch_idx) p.pitch_idx[row] = pi;
         if (p.energy_idx) p.energy_idx[row] = ei;
-        float d = p.dur_t ? (float)p.dur_t[row] : rintf(p.dur_pred[row] * (p.dur_s ? p.dur_s[b] : 1.0f));  // torch.round: half to even
-        if (p.mask) {                                                      // networks.py:381-382
-            if (pad) d = 0.0f;
-            d = fmaxf(d, 0.0f);
-        }
+        const float d = p.dur_t ? va_duration(true, (float)p.dur_t[row], 0.0f, 1.0f, p.mask, pad)
+                                : va_duration(false, 0.0f, p.dur_pred[row], p.dur_s ? p.dur_s[b] : 1.0f, p.mask, pad);
         p.dur[row] = (int)d;  // FeatureUpsampler `.int()`, networks.py:234
     }
 }

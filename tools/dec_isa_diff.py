@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Compare the decoder's generated machine code between two source trees (profiles/dec_refactor_isa.md).
 
-    tools/dec_isa_diff.py PARENT_TREE BRANCH_TREE [--out DIR] [--reuse-parent]
+    tools/dec_isa_diff.py PARENT_TREE BRANCH_TREE [--out DIR] [--reuse-parent] [--units a,b,c]
 
-Compiles the five decoder translation units for each library of __graft_entry__.VARIANTS to device assembly
+Compiles the five decoder translation units (or those named by --units, e.g. profiles/va_decide_refactor.md) for each library of __graft_entry__.VARIANTS to device assembly
 (FLAGS + the variant's defines + --cuda-device-only -S), replaces __hip_cuid_<hash> (derived from the output path) and reports per unit:
 "identical", or the second form: the kernels' resource metadata and the histogram of every mnemonic that is not scalar ALU / move.
 Exit status 0 when every unit is identical or passes the second form.
@@ -51,13 +51,14 @@ def facts(text):
 
 
 def main():
-    args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] != "--out"]
+    args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] not in ("--out", "--units")]
     parent, branch = os.path.abspath(args[0]), os.path.abspath(args[1])
     out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else tempfile.mkdtemp(prefix="dec_isa_")
+    units = tuple(sys.argv[sys.argv.index("--units") + 1].split(",")) if "--units" in sys.argv else UNITS
     sys.path.insert(0, branch)
     import __graft_entry__ as ge
     jobs = [(tree, os.path.join(out, tag), lib, d, u, ge.FLAGS, tag == "parent" and "--reuse-parent" in sys.argv)
-            for tag, tree in (("parent", parent), ("branch", branch)) for lib, d in ge.VARIANTS.items() for u in UNITS]
+            for tag, tree in (("parent", parent), ("branch", branch)) for lib, d in ge.VARIANTS.items() for u in units]
     with ThreadPoolExecutor(max_workers=min(len(jobs), 16, os.cpu_count() or 4)) as ex:
         texts = list(ex.map(lambda j: listing(*j), jobs))
     half, bad = len(jobs) // 2, 0
