@@ -152,7 +152,7 @@ EXPORTS = (
     "esmi_self_attention_workspace_bytes", "esmi_self_attention_f32", "esmi_mixffn_workspace_bytes", "esmi_mixffn_f32",
     "esmi_acoustic_decoder_f32", "esmi_bucket_embedding_f32", "esmi_split_weight_limit", "esmi_absmax_f32",
     "esmi_forward_arena_bytes", "esmi_phoneme2mel_forward_f32", "esmi_hifigan_workspace_bytes", "esmi_hifigan_generator_f32",
-    "esmi_hifigan_generator_ragged_f32",
+    "esmi_hifigan_generator_ragged_f32", "esmi_hifigan_generator_prec_f32",
     "esmi_variance_adaptor_ctl_f32", "esmi_fuse_variance_adaptor_ctl_f32", "esmi_phoneme2mel_forward_ctl_f32",
     "esmi_pack_resblock_bytes", "esmi_pack_resblock_f16",
     "esmi_train_conv_fwd_f32", "esmi_train_conv_ln_fwd_f32", "esmi_train_conv_dgrad_f32", "esmi_train_conv_wgrad_f32", "esmi_train_layernorm_fwd_f32",
@@ -268,6 +268,7 @@ def bind(lib):
     lib.esmi_hifigan_workspace_bytes.restype = sz
     lib.esmi_hifigan_generator_f32.argtypes = [P(HifiGanWeights), P(HifiGanShape), fp, i, i, fp, fp, sz, fp]
     lib.esmi_hifigan_generator_ragged_f32.argtypes = [P(HifiGanWeights), P(HifiGanShape), fp, i, i, fp, fp, fp, fp, sz, fp]
+    lib.esmi_hifigan_generator_prec_f32.argtypes = [P(HifiGanWeights), P(HifiGanShape), fp, i, i, fp, fp, fp, i, fp, sz, fp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name != "esmi_version":

@@ -464,6 +464,9 @@ __global__ __launch_bounds__(256) void convgemm_kernel(const ConvGemmP p) { conv
 // the same with ConvGemmP::len applied (the HiFi-GAN stages of at most 64 channels in a length-aware call)
 template <int NT>
 __global__ __launch_bounds__(256) void convgemm_len_kernel(const ConvGemmP p) { convgemm_body<NT, false, true>(p); }
+// ... and with ConvGemmP::amp (the generator at precision 16)
+template <int NT>
+__global__ __launch_bounds__(256) void convgemm_len_amp_kernel(const ConvGemmP p) { convgemm_body<NT, true, true>(p); }
 
 
 // ---- a convolution down to ONE output channel (HiFi-GAN conv_post, hifigan/models.py:123-125: 8..32 channels -> 1, k = 7,

@@ -396,4 +396,252 @@ __global__ __launch_bounds__(64 * kRbWaves, kRbWps) void hifigan_resblock16_kern
     }
 }
 
+// ---- precision 16 (include/esmi.h, "HiFi-GAN generator at precision 16"): the same two kernels with ONE binary16 product per
+// contraction.  The activation is rounded to nearest even once where it is produced -- leaky_relu(x) as ONE plane [row][C] in LDS, one
+// ds_read_b128 per B fragment --, the weight operand is the FIRST plane of the esmi_pack_resblock_f16 blob (the nearest binary16 of
+// 2^8 W: no second pack format), there is one MFMA per (k-step, row tile), and the accumulator, the residual stream, the biases and the
+// epilogue are the fp32 ones of the kernels above.  Window protocol, `len` handling and zeroing outside [0, n_eff) are unchanged.
+//
+// Window (rb_amp_rmax, the host's resblock_fused_ok): a wave's item stays (pair of 32-row tiles, 32-channel M tile), so R is bounded by
+// the number of waves, not by LDS alone.  C = 64 runs 16 waves (1024 threads, 4 waves per SIMD, <= 128 VGPRs -- the one-product loop
+// holds half the fragments and fits without scratch) on R <= 512 rows = 72 KB: of a k = 11 ResBlock1 window (halo 60 a side) 392 of 512
+// rows are output instead of 136 of 256.  C <= 32 keeps 8 waves and R <= 512 (40 KB at C = 32): already 77 % output rows at k = 11, and
+// the C = 8 / 16 stages are bound by their global accesses, which the window does not change.
+template <int C> struct RbAmp {
+    static constexpr int kWaves = C == 64 ? 16 : kRbWaves;
+    static constexpr int kWps = C == 64 ? 4 : kRbWps;
+};
+__host__ __device__ constexpr int rb_amp_waves(int c) { return c == 64 ? 16 : kRbWaves; }
+__host__ __device__ constexpr int rb_amp_rmax(int c) { return c == 64 ? 64 * (rb_amp_waves(c) / 2) : 64 * rb_amp_waves(c); }
+__host__ __device__ inline size_t rb_amp_lds_bytes(int c, int R) { return (size_t)R * rb_row_bytes(c); }
+
+typedef unsigned rb_u32x2 __attribute__((ext_vector_type(2)));
+// leaky_relu, then 4 channels rounded to binary16 (nearest even; at or beyond the binary16 range: +-inf)
+__device__ __forceinline__ rb_u32x2 lrelu_round4(const f32x4& v, float slope) {
+    const f32x4 a = lrelu4(v, slope);
+    const u32x4 r = round_f16x8(a, a);
+    return rb_u32x2{r[0], r[1]};
+}
+
+template <int C, int K>
+__global__ __launch_bounds__(64 * RbAmp<C>::kWaves, RbAmp<C>::kWps) void hifigan_resblock_amp_kernel(const ResblockP p) {
+    constexpr int RS = rb_row_bytes(C), MT = rb_mtiles(C), CG = (C < 32 ? C : 32) / 8;
+    constexpr int STEPS = rb_ksteps(C, K), HALF = (K - 1) / 2, PD = kRbPd < STEPS ? kRbPd : STEPS;
+    static_assert(STEPS >= PD, "prefetch distance reaches at most into the next conv");
+    ESMI_DYN_LDS(lds_f);
+    char* lds = reinterpret_cast<char*>(lds_f);   // ONE plane [R][RS], updated in place between two barriers
+    const int lane = lane_id(), w = wave_id(), i = lane & 31, h = lane >> 5;
+    const int pair = w / MT, mt = w - pair * MT;
+    const bool active = pair * 64 < p.R;
+    const int b = (int)blockIdx.x / p.tiles_per_b;
+    const int t0 = ((int)blockIdx.x - b * p.tiles_per_b) * p.TL - p.halo;   // sequence position of window row 0
+    const int n_eff = rb_n_eff(p, b);
+    if (t0 + p.halo >= n_eff) return;             // the whole output window lies behind the utterance's end (workgroup-uniform)
+    const int row0 = 64 * pair + i;
+    const long wlane = (long)(mt * STEPS) * 512 + lane * 4;
+
+    f32x4 xres[2][CG];
+    bool inside[2];
+    auto put_plane = [&](int row, int ch, const rb_u32x2& v) __attribute__((always_inline)) {
+        *reinterpret_cast<rb_u32x2*>(lds + row * RS + ch * 2) = v;
+    };
+    // weight fragment (the blob's first plane) of flattened step index s (s >= STEPS: the next conv's first steps; past the last conv: nothing)
+    auto wfetch = [&](int ci, int s, u32x4& hi) __attribute__((always_inline)) {
+        if (s >= STEPS) { ++ci; s -= STEPS; }
+        if (ci < p.n_conv && (C >= 32 || i < C))     // rows past C are the zero padding of the M tile: those lanes keep their zeros
+            hi = *reinterpret_cast<const u32x4*>(p.conv[ci].wp + wlane + (long)s * 512);
+    };
+    auto xfetch = [&](int s, int dil, u32x4 (&x)[2]) __attribute__((always_inline)) {
+        const int kidx = 16 * s + 8 * h;
+        int tap = kidx / C;
+        const int ch = kidx - tap * C;
+        tap = tap < K ? tap : K - 1;               // zero weight columns past the last tap: any finite row will do
+        const int shift = (tap - HALF) * dil;
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            int r = row0 + 32 * tt + shift;
+            r = r < 0 ? 0 : (r >= p.R ? p.R - 1 : r);
+            x[tt] = *reinterpret_cast<const u32x4*>(lds + opaque_i(r * RS + ch * 2));
+        }
+    };
+
+    u32x4 wq[PD];
+#pragma unroll
+    for (int q = 0; q < PD; ++q) wq[q] = u32x4{0, 0, 0, 0};
+    if (active) {
+#pragma unroll
+        for (int q = 0; q < PD; ++q) wfetch(0, q, wq[q]);
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            const int row = row0 + 32 * tt, pos = t0 + row;
+            inside[tt] = pos >= 0 && pos < n_eff;
+            const float* src = p.x + ((long)b * p.n + (inside[tt] ? pos : 0)) * C + 32 * mt + 4 * h;
+#pragma unroll
+            for (int g = 0; g < CG; ++g) {
+                xres[tt][g] = inside[tt] ? ld4(src + 8 * g) : zero4();
+                put_plane(row, 32 * mt + 8 * g + 4 * h, lrelu_round4(xres[tt][g], p.slope));
+            }
+        }
+    }
+    __syncthreads();
+
+    for (int ci = 0; ci < p.n_conv; ++ci) {
+        const bool last = ci + 1 == p.n_conv;
+        rb_u32x2 pl[2][CG];   // the conv's result as plane words, held across the barrier that ends everybody's reads
+        if (active) {
+            const int dil = p.conv[ci].dil;
+            f32x16 acc[2] = {zero16(), zero16()};
+            constexpr int XB = C == 64 ? 1 : 2;   // C <= 32: the next step's fragments are in flight under this step's MFMAs (C = 64: no registers for them)
+            u32x4 x[XB][2];
+            xfetch(0, dil, x[0]);
+#pragma unroll
+            for (int s = 0; s < STEPS; ++s) {
+                const u32x4 wh = wq[s % PD];
+                u32x4 nh = wh;
+                wfetch(ci, s + PD, nh);                            // in flight under PD steps of MFMAs (and the epilogue)
+                if (XB == 2 && s + 1 < STEPS) xfetch(s + 1, dil, x[(s + 1) % XB]);
+                sched_fence();
+#pragma unroll
+                for (int tt = 0; tt < 2; ++tt) acc[tt] = mfma32_f16(wh, x[s % XB][tt], acc[tt]);
+                wq[s % PD] = nh;
+                if (XB == 1 && s + 1 < STEPS) xfetch(s + 1, dil, x[0]);
+            }
+            // bias, residual, zero outside the sequence; the last conv's result goes straight out
+            const float* bias = p.conv[ci].bias + 32 * mt + 4 * h;
+            const bool add_res = p.conv[ci].add_res != 0;
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {
+                const int row = row0 + 32 * tt;
+                const bool emit = last && inside[tt] && row >= p.halo && row < p.halo + p.TL;
+                float* o = p.out + ((long)b * p.n + (emit ? t0 + row : 0)) * C + 32 * mt + 4 * h;
+#pragma unroll
+                for (int g = 0; g < CG; ++g) {
+                    const f32x4 bv = ld4(bias + 8 * g);
+                    f32x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = fmaf(acc[tt][4 * g + e], kF16WScaleInv, bv[e]);
+                    if (add_res) v = v + xres[tt][g];
+                    if (!inside[tt]) v = zero4();
+                    if (last) {
+                        if (emit) {
+                            if (p.accum) v = v + ld4(o + 8 * g);
+                            *reinterpret_cast<f32x4*>(o + 8 * g) = v;
+                        }
+                    } else {
+                        if (add_res) xres[tt][g] = v;
+                        pl[tt][g] = lrelu_round4(v, p.slope);
+                    }
+                }
+            }
+        }
+        if (last) break;
+        __syncthreads();       // every wave has read what it needs of the old plane
+        if (active) {
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+                for (int g = 0; g < CG; ++g) put_plane(row0 + 32 * tt, 32 * mt + 8 * g + 4 * h, pl[tt][g]);
+        }
+        __syncthreads();       // the new plane is complete
+    }
+}
+
+// C <= 16 on v_mfma_f32_16x16x32_f16 tiles, one product
+template <int C, int K>
+__global__ __launch_bounds__(64 * kRbWaves, kRbWps) void hifigan_resblock16_amp_kernel(const ResblockP p) {
+    static_assert(C == 8 || C == 16, "narrow-tile kernel");
+    constexpr int RS = rb_row_bytes(C), STEPS = rb_ksteps16(C, K), HALF = (K - 1) / 2;
+    ESMI_DYN_LDS(lds_f);
+    char* lds = reinterpret_cast<char*>(lds_f);
+    const int lane = lane_id(), w = wave_id(), n = lane & 15, kb = lane >> 4;
+    const bool active = w * 64 < p.R, chan_ok = 4 * kb < C;      // C = 8: k-blocks 2, 3 hold the zero rows of the M tile
+    const int b = (int)blockIdx.x / p.tiles_per_b;
+    const int t0 = ((int)blockIdx.x - b * p.tiles_per_b) * p.TL - p.halo;
+    const int n_eff = rb_n_eff(p, b);
+    if (t0 + p.halo >= n_eff) return;             // the whole output window lies behind the utterance's end (workgroup-uniform)
+    const int row0 = 64 * w + n;
+
+    f32x4 xres[4];
+    bool inside[4];
+    auto put_plane = [&](int row, const rb_u32x2& v) __attribute__((always_inline)) {
+        *reinterpret_cast<rb_u32x2*>(lds + row * RS + 8 * kb) = v;
+    };
+    u32x4 wf[STEPS];
+    auto wfetch = [&](int ci) __attribute__((always_inline)) {
+        if (ci < p.n_conv && n < C) {              // rows past C are zero padding: those lanes keep their zeros
+            const unsigned* q = p.conv[ci].wp + lane * 4;
+#pragma unroll
+            for (int s = 0; s < STEPS; ++s) wf[s] = *reinterpret_cast<const u32x4*>(q + s * 512);   // the blob's first plane
+        }
+    };
+#pragma unroll
+    for (int s = 0; s < STEPS; ++s) wf[s] = u32x4{0, 0, 0, 0};
+    if (active) {
+        wfetch(0);
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            const int row = row0 + 16 * nt, pos = t0 + row;
+            inside[nt] = pos >= 0 && pos < n_eff;
+            xres[nt] = (inside[nt] && chan_ok) ? ld4(p.x + ((long)b * p.n + pos) * C + 4 * kb) : zero4();
+            if (chan_ok) put_plane(row, lrelu_round4(xres[nt], p.slope));
+        }
+    }
+    __syncthreads();
+
+    for (int ci = 0; ci < p.n_conv; ++ci) {
+        const bool last = ci + 1 == p.n_conv;
+        rb_u32x2 pl[4];
+        if (active) {
+            const int dil = p.conv[ci].dil;
+            f32x4 acc[4] = {zero4(), zero4(), zero4(), zero4()};
+#pragma unroll
+            for (int s = 0; s < STEPS; ++s) {
+                const int kidx = 32 * s + 8 * kb;
+                int tap = kidx / C;
+                const int ch = kidx - tap * C;
+                tap = tap < K ? tap : K - 1;       // zero weight columns past the last tap
+                const int shift = (tap - HALF) * dil;
+                u32x4 x[4];
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) {
+                    int r = row0 + 16 * nt + shift;
+                    r = r < 0 ? 0 : (r >= p.R ? p.R - 1 : r);
+                    x[nt] = *reinterpret_cast<const u32x4*>(lds + opaque_i(r * RS + ch * 2));
+                }
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) acc[nt] = mfma16_f16(wf[s], x[nt], acc[nt]);
+            }
+            wfetch(ci + 1);                        // under the epilogue and the two barriers
+            const f32x4 bv = chan_ok ? ld4(p.conv[ci].bias + 4 * kb) : zero4();
+            const bool add_res = p.conv[ci].add_res != 0;
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                const int row = row0 + 16 * nt;
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = fmaf(acc[nt][e], kF16WScaleInv, bv[e]);
+                if (add_res) v = v + xres[nt];
+                if (!inside[nt]) v = zero4();
+                if (last) {
+                    if (chan_ok && inside[nt] && row >= p.halo && row < p.halo + p.TL) {
+                        float* o = p.out + ((long)b * p.n + t0 + row) * C + 4 * kb;
+                        if (p.accum) v = v + ld4(o);
+                        *reinterpret_cast<f32x4*>(o) = v;
+                    }
+                } else {
+                    if (add_res) xres[nt] = v;
+                    pl[nt] = lrelu_round4(v, p.slope);
+                }
+            }
+        }
+        if (last) break;
+        __syncthreads();       // every wave has read what it needs of the old plane
+        if (active && chan_ok) {
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) put_plane(row0 + 16 * nt, pl[nt]);
+        }
+        __syncthreads();       // the new plane is complete
+    }
+}
+
 }  // namespace esmi

@@ -105,6 +105,8 @@ int launch_enc_post_attn128(const PostAttn128P& p, hipStream_t st);   // enc_ffn
 int launch_enc_merge_q256(const MergeQ256P& p, hipStream_t st);   // enc_merge256.h: merge conv k = 3 stride 2, 128 -> 256, + the folded query GEMM, N <= 128
 // tu_hifigan.hip (which also holds the generator's host side: esmi_hifigan_*)
 int launch_resblock(const ResblockP& p, int c, hipStream_t st);
+// tu_hifigan_amp.hip: the same block with one binary16 product per contraction (the generator at precision 16; p.R <= rb_amp_rmax(c))
+int launch_resblock_amp(const ResblockP& p, int c, hipStream_t st);
 
 // Does enc_attn_ffn serve this block (the shapes it is instantiated for)?  Not beyond 128 positions: there the chain kernel runs one
 // latency chain per 32 rows against up to 256 keys, and the same ops as launches (LDS-staged attention + GEMMs) are faster (launches
@@ -135,6 +137,7 @@ int set_range_flag_dec_128_3(int* flag);
 int set_range_flag_dec_256_5(int* flag);
 int set_range_flag_dec_256_3(int* flag);
 int set_range_flag_hifigan(int* flag);
+int set_range_flag_hifigan_amp(int* flag);
 int set_range_flag_train(int* flag);
 // development (-DESMI_CHAIN_TRACE): every translation unit with chain kernels owns a copy of the trace pointer
 #ifdef ESMI_CHAIN_TRACE

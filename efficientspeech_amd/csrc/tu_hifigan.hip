@@ -100,7 +100,8 @@ HgMargins hg_margins(const esmi_hifigan_shape* s) {
     return g;
 }
 
-bool resblock_fused_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, int rb, int c, int k, int n, ResblockP* o) {
+// amp (precision 16): the window of the one-product kernels -- half the LDS per row, and 16 waves at 64 channels (rb_amp_rmax)
+bool resblock_fused_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, int rb, int c, int k, int n, bool amp, ResblockP* o) {
 #if !ESMI_CHAIN_SPLIT
     return false;   // the exact-fp32 build keeps the per-conv fp32-MFMA launches
 #endif
@@ -118,7 +119,8 @@ bool resblock_fused_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* 
             p.conv[q++] = RbConv{static_cast<const unsigned*>(w->rb_wp2[rb * 3 + m]), w->rb_b2[rb * 3 + m], 1, 1};
         }
     }
-    const int r_max = c == 64 ? 256 : 512;    // 8 waves = 8 (row pair, 32-channel tile) items; LDS <= 80 KB: two workgroups per CU
+    // 8 waves = 8 (row pair, 32-channel tile) items; LDS <= 80 KB: two workgroups per CU
+    const int r_max = amp ? rb_amp_rmax(c) : (c == 64 ? 256 : 512);
     int R = ((n + 2 * halo + 63) / 64) * 64;
     R = R < r_max ? R : r_max;
     if (R - 2 * halo < 32 && R - 2 * halo < n) return false;
@@ -142,11 +144,11 @@ struct HgStage {
 
 // ResBlock rb of stage g one launch per convolution: x (+)= block(y), j = rb % n_kernels > 0 accumulates; r, t: the block's own state
 int resblock_conv_by_conv(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const HgStage& g, int rb, const float* y, float* x,
-                          float* r, float* t, hipStream_t st) {
+                          float* r, float* t, int amp, hipStream_t st) {
     const int j = rb % s->n_kernels, k = s->rb_kernels[j], nconv = s->resblock == 1 ? 3 : 2, c = g.c;
     auto conv = [&](int dil, const float* in, const float* wt, const float* bias, float* out) {   // out = conv(leaky_relu(in))
         ConvGemmP p = conv1d(g.B, g.n, c, c, k, dil, in, c, {wt, nullptr}, bias, out, c);
-        p.act_in = 1; p.act_in_slope = kSlope;
+        p.act_in = 1; p.act_in_slope = kSlope; p.amp = amp;
         g.limit(&p);
         return p;
     };
@@ -177,14 +179,14 @@ int resblock_conv_by_conv(const esmi_hifigan_weights* w, const esmi_hifigan_shap
 // Every weight the call is going to read, looked at before the first launch: conv_pre, conv_post and the ConvTranspose1d's their fp32
 // tensor and bias; a ResBlock that runs as one launch (fp[rb].n_conv > 0 then, and fp[rb] holds its parameters) its packed weights
 // and biases (resblock_fused_ok has looked), any other its fp32 tensors and biases.
-bool hg_weights_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, int L, ResblockP* fp) {
+bool hg_weights_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, int L, bool amp, ResblockP* fp) {
     bool ok = w->pre_w && w->pre_b && w->post_w && w->post_b;
     int n = L, c = s->initial_channel;
     for (int i = 0, rb = 0; i < s->n_up; ++i) {
         ok = ok && w->up_w[i] && w->up_b[i];
         n *= s->up_rates[i]; c /= 2;
         for (int j = 0; j < s->n_kernels; ++j, ++rb) {
-            if (resblock_fused_ok(w, s, rb, c, s->rb_kernels[j], n, &fp[rb])) continue;
+            if (resblock_fused_ok(w, s, rb, c, s->rb_kernels[j], n, amp, &fp[rb])) continue;
             fp[rb].n_conv = 0;
             for (int m = rb * 3; m < rb * 3 + (s->resblock == 1 ? 3 : 2); ++m)
                 ok = ok && w->rb_w1[m] && w->rb_b1[m] && (s->resblock == 2 || (w->rb_w2[m] && w->rb_b2[m]));
@@ -199,15 +201,21 @@ bool hg_weights_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, i
 // stage's limit from hg_margins: a limited stage reads only rows the stage before it wrote, full or limited.  What that leaves
 // unlimited, by multiply-adds (n . c^2 per stage): v2 (64 / 32 / 16 / 8 channels) conv_pre alone, a few per cent; v3 its 128-channel
 // stage, about a fifth; v1 its 256- and 128-channel stages, about two thirds -- on v1 most of the padded work is still done.
+// precision 0 / 32: the fp32-accurate split products.  16 (include/esmi.h): conv_pre, every ConvTranspose1d and every ResBlock convolution
+// carry ConvGemmP::amp, a one-launch ResBlock runs on hifigan_resblock_amp_kernel / hifigan_resblock16_amp_kernel; conv_post is unchanged.
 int hifigan_generator(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
-                      const int32_t* mel_len, float* wav, int16_t* pcm, void* workspace, size_t workspace_bytes, esmi_stream_t stream) {
+                      const int32_t* mel_len, float* wav, int16_t* pcm, int precision, void* workspace, size_t workspace_bytes,
+                      esmi_stream_t stream) {
+    if (precision != 0 && precision != 32 && precision != 16) return ESMI_ERR_ARG;
+    const int amp = precision == 16;
     size_t buf;
     int rc = hg_plan(s, B, L, &buf);
     if (rc) return rc;
+    if (amp && !ESMI_CHAIN_SPLIT) return ESMI_ERR_UNSUPPORTED;   // the exact-fp32 build has no binary16 products
     if (!w || !mel || (!wav && !pcm) || !workspace) return ESMI_ERR_ARG;
     if (workspace_bytes < 4 * buf) return ESMI_ERR_WORKSPACE;
     ResblockP fused[ESMI_HIFIGAN_MAX_RBCONV / 3];   // (hg_plan: n_up . n_kernels fit)
-    if (!hg_weights_ok(w, s, L, fused)) return ESMI_ERR_ARG;
+    if (!hg_weights_ok(w, s, L, amp, fused)) return ESMI_ERR_ARG;
     const HgMargins mg = hg_margins(s);
     hipStream_t st = S(stream);
     auto ws = [&](int q) { return reinterpret_cast<float*>(static_cast<char*>(workspace) + q * buf); };
@@ -215,6 +223,7 @@ int hifigan_generator(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s
     HgStage g = {B, L, s->initial_channel, nullptr, 0, 0, 0};
     // conv_pre, models.py:112: Conv1d(n_mel, C0, 7, padding 3)
     ConvGemmP p = conv1d(B, L, s->n_mel, g.c, 7, 1, mel, s->n_mel, {w->pre_w, nullptr}, w->pre_b, x, g.c);
+    p.amp = amp;
     if ((rc = launch_convgemm(p, st))) return rc;
     float in_scale = 1.0f;           // the mean over the ResBlocks of the previous stage, folded into the next input activation
     for (int i = 0; i < s->n_up; ++i) {
@@ -224,7 +233,7 @@ int hifigan_generator(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s
         g = HgStage{B, in.n * u, in.c / 2, lim ? mel_len : nullptr, L, mg.mul[i], mg.add[i]};
         // x = ups[i](leaky_relu(x, 0.1)), models.py:114-115: ConvTranspose1d(c, c/2, k, u, padding (k-u)//2)
         p = conv_transpose1d(B, in.n, g.n, in.c, g.c, k, u, (k - u) / 2, x, in.c, {w->up_w[i], nullptr}, w->up_b[i], y, g.c);
-        p.act_in = 1; p.act_in_slope = kSlope; p.a_scale = in_scale;
+        p.act_in = 1; p.act_in_slope = kSlope; p.a_scale = in_scale; p.amp = amp;
         g.limit(&p);
         if ((rc = launch_convgemm(p, st))) return rc;
         for (int j = 0; j < s->n_kernels; ++j) {   // xs += resblocks[i*num_kernels + j](x), models.py:116-121
@@ -233,9 +242,9 @@ int hifigan_generator(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s
             if (fp.n_conv) {   // the whole block on an LDS-resident window: y -> x (+)=
                 fp.x = y; fp.out = x; fp.B = B; fp.accum = j > 0; fp.slope = kSlope;
                 g.limit(&fp);
-                rc = launch_resblock(fp, g.c, st);
+                rc = amp ? launch_resblock_amp(fp, g.c, st) : launch_resblock(fp, g.c, st);
             } else {
-                rc = resblock_conv_by_conv(w, s, g, rb, y, x, r, t, st);
+                rc = resblock_conv_by_conv(w, s, g, rb, y, x, r, t, amp, st);
             }
             if (rc) return rc;
         }
@@ -260,14 +269,21 @@ size_t esmi_hifigan_workspace_bytes(const esmi_hifigan_shape* s, int B, int L) {
 
 int esmi_hifigan_generator_f32(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
                                float* wav, void* workspace, size_t workspace_bytes, esmi_stream_t stream) {
-    return hifigan_generator(w, s, mel, B, L, nullptr, wav, nullptr, workspace, workspace_bytes, stream);
+    return hifigan_generator(w, s, mel, B, L, nullptr, wav, nullptr, 32, workspace, workspace_bytes, stream);
 }
 
 int esmi_hifigan_generator_ragged_f32(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
                                       const int32_t* mel_len, float* wav, int16_t* pcm, void* workspace, size_t workspace_bytes,
                                       esmi_stream_t stream) {
     if (!mel_len) return ESMI_ERR_ARG;
-    return hifigan_generator(w, s, mel, B, L, mel_len, wav, pcm, workspace, workspace_bytes, stream);
+    return hifigan_generator(w, s, mel, B, L, mel_len, wav, pcm, 32, workspace, workspace_bytes, stream);
+}
+
+int esmi_hifigan_generator_prec_f32(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
+                                    const int32_t* mel_len, float* wav, int16_t* pcm, int precision, void* workspace,
+                                    size_t workspace_bytes, esmi_stream_t stream) {
+    if (!mel_len && pcm) return ESMI_ERR_ARG;   // the plain call has no PCM plane
+    return hifigan_generator(w, s, mel, B, L, mel_len, wav, pcm, precision, workspace, workspace_bytes, stream);
 }
 
 size_t esmi_pack_resblock_bytes(int c, int k) {

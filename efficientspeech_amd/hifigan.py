@@ -62,6 +62,12 @@ HIFIGAN_CONFIGS = {
 }
 
 
+def _check_precision(precision):
+    if precision not in (16, 32):
+        raise ValueError(f"vocoder precision must be 32 or 16, got {precision!r}")
+    return int(precision)
+
+
 def get_padding(kernel_size, dilation=1):
     return int((kernel_size * dilation - dilation) / 2)
 
@@ -89,8 +95,9 @@ class ResBlock2(nn.Module):
 class Generator(_PackedModule):
     """hifigan/models.py:84-135.  `h`: a HifiGanConfig, a config.json path / dict, or anything with the same attributes."""
 
-    def __init__(self, h=None):
+    def __init__(self, h=None, precision=32):
         super().__init__()
+        self.precision = _check_precision(precision)   # forward's default: 32, or 16 (include/esmi.h: one binary16 product per contraction)
         if h is None:
             h = HifiGanConfig()
         elif isinstance(h, (str, os.PathLike, dict)) and not hasattr(h, "upsample_rates"):
@@ -176,8 +183,12 @@ class Generator(_PackedModule):
         return self._cache.get(lambda: list(self.parameters()), build)
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x, lengths=None, pcm16=False):
+    def forward(self, x, lengths=None, pcm16=False, precision=None):
         """x: mel (B, num_mels, L) as the reference takes it -> wav (B, 1, L * hop).
+
+        `precision`: 32 (fp32-accurate products) or 16 (every convolution but conv_post on binary16 operands with fp32 accumulation, as
+        the reference's `--precision 16` autocast vocodes: 2-4 PCM LSB rms away from 32, see include/esmi.h); None: `self.precision`.
+        Both read the same packed weights.
 
         `lengths`: int tensor (B,) on the device, the mel frames of each utterance (`Phoneme2Mel`'s `mel_len` as it is: no host
         synchronisation).  The stages of at most 64 channels (all of v2; the last two of v1 and v3) then do no work for frames no
@@ -185,12 +196,13 @@ class Generator(_PackedModule):
         `lengths[b] * hop` on are exactly zero; the kept samples are bit for bit those of `forward(x)`.  `pcm16`: int16 PCM
         (trunc(clamp(wav * 32768, -32768, 32767))) instead of float.  `lengths=None`, `pcm16=False`: the plain call; `pcm16=True` without
         lengths takes every utterance as L frames long."""
+        precision = _check_precision(self.precision if precision is None else precision)
         with _on_device_of(self.conv_post.weight):
             if lengths is None and not pcm16:
-                return self._forward(x)
-            return self._forward_ragged(x, lengths, pcm16)
+                return self._forward(x, precision)
+            return self._forward_ragged(x, lengths, pcm16, precision)
 
-    def _forward(self, x):
+    def _forward(self, x, precision=32):
         lib, stream = networks._runtime(self.conv_post.weight)
         mel = _f32(x.transpose(1, 2))                  # (B, L, 80) channels-last: a free view of the acoustic model's own output
         B, L, nm = mel.shape
@@ -201,10 +213,13 @@ class Generator(_PackedModule):
         w, s, _keep = self._packed(lib, stream)
         nbytes = lib.esmi_hifigan_workspace_bytes(C.byref(s), B, L)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=mel.device)
-        lib.esmi_hifigan_generator_f32(C.byref(w), C.byref(s), _ptr(mel), B, L, _ptr(wav), _ptr(ws), nbytes, stream)
+        if precision == 32:
+            lib.esmi_hifigan_generator_f32(C.byref(w), C.byref(s), _ptr(mel), B, L, _ptr(wav), _ptr(ws), nbytes, stream)
+        else:
+            lib.esmi_hifigan_generator_prec_f32(C.byref(w), C.byref(s), _ptr(mel), B, L, None, _ptr(wav), None, precision, _ptr(ws), nbytes, stream)
         return wav
 
-    def _forward_ragged(self, x, lengths, pcm16):
+    def _forward_ragged(self, x, lengths, pcm16, precision=32):
         lib, stream = networks._runtime(self.conv_post.weight)
         mel = _f32(x.transpose(1, 2))
         B, L, nm = mel.shape
@@ -219,8 +234,11 @@ class Generator(_PackedModule):
         w, s, _keep = self._packed(lib, stream)
         nbytes = lib.esmi_hifigan_workspace_bytes(C.byref(s), B, L)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=mel.device)
-        lib.esmi_hifigan_generator_ragged_f32(C.byref(w), C.byref(s), _ptr(mel), B, L, _ptr(lengths), None if pcm16 else _ptr(out),
-                                              _ptr(out) if pcm16 else None, _ptr(ws), nbytes, stream)
+        planes = (None, _ptr(out)) if pcm16 else (_ptr(out), None)
+        if precision == 32:
+            lib.esmi_hifigan_generator_ragged_f32(C.byref(w), C.byref(s), _ptr(mel), B, L, _ptr(lengths), *planes, _ptr(ws), nbytes, stream)
+        else:
+            lib.esmi_hifigan_generator_prec_f32(C.byref(w), C.byref(s), _ptr(mel), B, L, _ptr(lengths), *planes, precision, _ptr(ws), nbytes, stream)
         return out
 
 
@@ -261,14 +279,15 @@ def fold_weight_norm(sd):
     return out
 
 
-def get_hifigan(checkpoint="hifigan/LJ_V2/generator_v2", infer_device=None, verbose=False):
-    """model.py:23-49: config.json next to the checkpoint, `ckpt['generator']` (weight-norm form), eval, on `infer_device`."""
+def get_hifigan(checkpoint="hifigan/LJ_V2/generator_v2", infer_device=None, verbose=False, precision=32):
+    """model.py:23-49: config.json next to the checkpoint, `ckpt['generator']` (weight-norm form), eval, on `infer_device`.
+    `precision`: the generator's default (Generator.forward)."""
     main_path = os.path.dirname(os.path.abspath(checkpoint))
     cfg = HifiGanConfig.from_json(os.path.join(main_path, "config.json"))
     if verbose:
         print("Using hifigan checkpoint: ", checkpoint)
     ckpt = torch.load(checkpoint, map_location="cpu")
-    voc = Generator(cfg)
+    voc = Generator(cfg, precision=precision)
     voc.load_state_dict(fold_weight_norm(ckpt["generator"]), strict=True)
     voc.eval()
     if infer_device is not None:

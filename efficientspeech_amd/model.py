@@ -147,7 +147,7 @@ class EfficientSpeech(nn.Module):
             return mel, mel_len, duration
         return self.hifigan(mel).squeeze(1), mel_len, duration
 
-    def synthesize(self, batch, pcm16=False, pitch_control=None, energy_control=None, duration_control=None):
+    def synthesize(self, batch, pcm16=False, pitch_control=None, energy_control=None, duration_control=None, precision=None):
         """Length-aware `predict_step`: (wav (B, L * hop), wav_len = mel_len * hop, duration).  `mel_len` goes to the vocoder as the
         device tensor it is (no host synchronisation): the generator's stages of at most 64 channels skip the frames behind each
         utterance's end (hifigan.Generator.forward), the samples from
@@ -156,7 +156,10 @@ class EfficientSpeech(nn.Module):
         full scale clamps to 32767 instead of wrapping.  Needs a vocoder that takes `lengths` (the HIP `Generator`).
         `pitch_control`, `energy_control`, `duration_control`: per-utterance prosody scales (a number, or a tensor of shape (B,) or ()),
         the same as the input-dict keys of those names (`networks._prosody_controls`: the prediction that is bucketized / rounded is
-        multiplied inside the kernels; `duration_control=1.25` speaks 25 % slower).  An argument that is given replaces the batch's key."""
+        multiplied inside the kernels; `duration_control=1.25` speaks 25 % slower).  An argument that is given replaces the batch's key.
+        `precision`: the vocoder's, 32 or 16 (hifigan.Generator.forward; the acoustic model is fp32 either way); None: the vocoder's own."""
+        if precision is not None and precision not in (16, 32):
+            raise ValueError(f"vocoder precision must be 32 or 16, got {precision!r}")
         if self.hifigan is None:
             raise RuntimeError("synthesize() needs a vocoder: attach one (hifigan=Generator(...) / get_hifigan(...)); "
                                "predict_step returns the mel when there is none")
@@ -164,7 +167,8 @@ class EfficientSpeech(nn.Module):
         if any(v is not None for v in controls.values()):
             batch = dict(batch, **{k: v for k, v in controls.items() if v is not None})
         mel, mel_len, duration = self.phoneme2mel(batch, train=False)
-        wav = self.hifigan(mel.transpose(1, 2), lengths=mel_len, pcm16=pcm16).squeeze(1)
+        kw = {} if precision is None else {"precision": precision}
+        wav = self.hifigan(mel.transpose(1, 2), lengths=mel_len, pcm16=pcm16, **kw).squeeze(1)
         return wav, mel_len * self.hifigan.h.hop, duration
 
     @classmethod

@@ -33,7 +33,7 @@ extern "C" {
 #endif
 
 #define ESMI_VERSION 501 /* 0.5.1: esmi_train_conv_ln_fwd_f32, then esmi_hifigan_generator_ragged_f32, then esmi_prosody_control and the three
-                            *_ctl_f32 entry points (additions; nothing else changed shape).  0.5.0 (round 5): esmi_mel_decoder_clock_probe;
+                            *_ctl_f32 entry points, then esmi_hifigan_generator_prec_f32 (additions; nothing else changed shape).  0.5.0 (round 5): esmi_mel_decoder_clock_probe;
                             0.4.0: esmi_decoder_head.proj_w (the decoder's first stage at phoneme rate for every model size:
                           * esmi_decoder_head_f32).  0.3.0: training entry points changed shape (esmi_conv_desc: act / packed_fwd / packed_grad; LayerNorm with
                           * residual / row mask / activation arguments; esmi_train_loss_args.grad_seed; esmi_train_pack_weights_f32,
@@ -542,6 +542,30 @@ int esmi_hifigan_generator_f32(const esmi_hifigan_weights* w, const esmi_hifigan
 int esmi_hifigan_generator_ragged_f32(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
                                       const int32_t* mel_len, float* wav, int16_t* pcm, void* workspace, size_t workspace_bytes,
                                       esmi_stream_t stream);
+
+/* HiFi-GAN generator at precision 16 (opt-in; the reference vocodes under its Trainer's `--precision 16` autocast, utils/tools.py:326-327,
+ * model.py:246-264).  Every convolution of the generator EXCEPT conv_post:
+ *   - both operands are rounded to binary16, round to nearest even; the activation is rounded AFTER its input-side
+ *     leaky_relu(a_scale * x, slope);
+ *   - accumulation is fp32, with ONE MFMA product per k-step (v_mfma_f32_*_f16) instead of the three of the fp32-accurate split;
+ *   - tensors in memory stay fp32; the ResBlock residual stream, the sum over a stage's ResBlocks and the biases stay fp32;
+ *   - conv_post (plain fp32 FMAs) and the tanh are unchanged, and so are the length-aware call's guarantees: kept samples bit for bit
+ *     those of the plain precision-16 call, exact zeros behind them, the same PCM conversion.
+ * The weight operand: in the per-convolution launches the nearest binary16 of 2^8 * w, rounded as the weight is read (what the training
+ * step's precision 16 does); in the one-launch ResBlock kernels the FIRST plane of the esmi_pack_resblock_f16 blob, which already is
+ * the nearest binary16 of 2^8 * w -- no second pack format, no second copy of the weights; the accumulator is rescaled by 2^-8 as at
+ * precision 32.  The 2^8 scale keeps weights down to 2^-22 normal binary16 numbers; an autocast's plain `w.to(float16)` differs from
+ * both only where it is subnormal, |w| < 2^-14, by less than 2^-25 absolute.
+ * An activation at or beyond the binary16 range (|a| >= 65520) becomes +-inf, as under torch autocast, and the waveform nan / +-1 from
+ * there on; nothing guards against it (precision 32 saturates silently instead).  Expect the error of any binary16-operand
+ * implementation: 2e-4 .. 5e-4 L-inf, 6e-5 .. 1.2e-4 rms on waveforms of rms 0.06 .. 0.18 for v1 / v2 / v3 (2-4 PCM LSB rms).
+ *
+ * mel_len == NULL: the plain call (pcm must be NULL); else the length-aware one.  precision 0 / 32: exactly
+ * esmi_hifigan_generator_f32 / _ragged_f32; 16: as defined above; anything else: ESMI_ERR_ARG, nothing launched.
+ * libesmi_fp32mfma.so has no binary16 products: precision 16 is ESMI_ERR_UNSUPPORTED there, nothing launched.  Workspace as above. */
+int esmi_hifigan_generator_prec_f32(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
+                                    const int32_t* mel_len, float* wav, int16_t* pcm, int precision,
+                                    void* workspace, size_t workspace_bytes, esmi_stream_t stream);
 
 /* x.masked_fill(mask[:, :, None], 0) on (rows, C) fp32 -- used by the module-level API when the
  * decoder is called stand-alone.                                                              */

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Development: time the HiFi-GAN generator (esmi_hifigan_generator_f32) alone.  python tools/bench_vocoder.py [--config v2] [--batch 16] [--frames 768]
 --ragged lo:hi[:seed]: utterance lengths uniform in [lo, hi] frames, the batch padded to hi; the full run and the length-aware run
-(esmi_hifigan_generator_ragged_f32) of that batch alternate, and the ideal ratio sum(min(len + margin, L)) / (B L) is printed."""
+(esmi_hifigan_generator_ragged_f32) of that batch alternate, and the ideal ratio sum(min(len + margin, L)) / (B L) is printed.
+--precision {32,16}: 16 (esmi_hifigan_generator_prec_f32: one binary16 product per contraction) times precision 32 and 16 of the same call,
+alternating in one process, and prints the ratio and the difference of the two waveforms; with --ragged both are the length-aware call."""
 import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -12,6 +14,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="v2"); ap.add_argument("--batch", type=int, default=16); ap.add_argument("--frames", type=int, default=768)
 ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--ragged", default=None, metavar="lo:hi[:seed]"); ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--precision", type=int, default=32, choices=(32, 16))
 a = ap.parse_args()
 h = HIFIGAN_CONFIGS[a.config]
 if a.ragged:
@@ -34,12 +37,33 @@ def timed(fn):
     return (time.perf_counter() - t0) / a.iters
 
 
+def precision_ab(what, call):
+    """call(precision) at 32 and 16, alternating (both see the same clocks and neighbours)"""
+    t32, t16 = [], []
+    with torch.no_grad():
+        for _ in range(2):
+            w32, w16 = call(32), call(16)
+        for _ in range(a.rounds):
+            t32.append(timed(lambda: call(32)))
+            t16.append(timed(lambda: call(16)))
+    d = (w16 - w32).double()
+    ms = lambda v: " ".join(f"{x * 1e3:.2f}" for x in v)      # noqa: E731
+    print(f"hifigan {a.config}: B={a.batch} L={a.frames} {what}")
+    print(f"  precision 32 ms: {ms(t32)}   median {np.median(t32) * 1e3:.2f}")
+    print(f"  precision 16 ms: {ms(t16)}   median {np.median(t16) * 1e3:.2f}")
+    print(f"  16 / 32 = {np.median(t16) / np.median(t32):.3f}   wav16 - wav32: L-inf {float(d.abs().max()):.2e} rms {float(d.pow(2).mean().sqrt()):.2e} "
+          f"(wav32 rms {float(w32.double().pow(2).mean().sqrt()):.3f})   finite={bool(torch.isfinite(w16).all())}")
+    sys.exit(0)
+
+
 if a.ragged:
     from efficientspeech_amd.hifigan import ragged_margins
     lens = np.random.default_rng(seed[0] if seed else 0).integers(lo, hi + 1, size=a.batch)
     lengths = torch.from_numpy(lens.astype(np.int32)).cuda()
     margin = ragged_margins(h)[1]
     ideal = float(np.minimum(lens + margin, a.frames).sum()) / (a.batch * a.frames)
+    if a.precision == 16:
+        precision_ab(f"lengths U[{lo},{hi}] mean {lens.mean():.1f}, length-aware call", lambda pr: voc(mel.transpose(1, 2), lengths=lengths, precision=pr))
     full, rag = [], []
     with torch.no_grad():
         for _ in range(2):
@@ -55,6 +79,8 @@ if a.ragged:
     print(f"  ragged ms: {ms(rag)}   median {np.median(rag) * 1e3:.2f}")
     print(f"  ragged / full = {np.median(rag) / np.median(full):.3f}   ideal ratio = {ideal:.3f}   kept samples identical, tails zero: {same}")
     sys.exit(0)
+if a.precision == 16:
+    precision_ab("plain call", lambda pr: voc(mel.transpose(1, 2), precision=pr))
 with torch.no_grad():
     for _ in range(2):
         wav = voc(mel.transpose(1, 2))

@@ -2,8 +2,10 @@
 # On the GPU box: kernel trace of the HiFi-GAN generator forward -> gpurun_out/<tag>/vocoder_kernel_stats.md
 set -u
 TAG=${1:-r03}; REPO=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT
-python $REPO/tools/bench_vocoder.py --batch 16 --iters 20 2>/dev/null | tail -2 > $OUT/vocoder_unprofiled.txt
-(cd /tmp && TMPDIR=/tmp timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/voc_stats -o r -- python $REPO/tools/bench_vocoder.py --batch 16 --iters 20 > $OUT/voc_stats.log 2>&1 < /dev/null)
+# further arguments go to bench_vocoder.py, e.g. `r10 --precision 16 --rounds 1`: that mode's last forwards are the precision-16 ones
+shift || true
+python $REPO/tools/bench_vocoder.py --batch 16 --iters 20 "$@" 2>/dev/null | tail -2 > $OUT/vocoder_unprofiled.txt
+(cd /tmp && TMPDIR=/tmp timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/voc_stats -o r -- python $REPO/tools/bench_vocoder.py --batch 16 --iters 20 "$@" > $OUT/voc_stats.log 2>&1 < /dev/null)
 python - $OUT <<'PY'
 import csv, glob, sys, collections, re
 out = sys.argv[1]
