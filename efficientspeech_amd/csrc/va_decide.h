@@ -31,7 +31,10 @@ __device__ __forceinline__ int va_scan_term(float dval, bool out_of_range) {
 }
 
 // torch.bucketize(v, edges, right=False) = the number of edges strictly below v: this lane's share over N4 float4 of LDS, as an fp32
-// count (sums of 0 / 1: exact in any order); the caller's row_sum4 adds the four lanes of the row
+// count (sums of 0 / 1: exact in any order); the caller's row_sum4 adds the four lanes of the row.
+// NaN: `e < NaN` is false for every edge, so a NaN value gets bucket 0 -- here, in enc_fuse_va's register-resident edges, in
+// bucketize_left (va_tail, bucket_embed_kernel) and in the C oracle alike.  torch.bucketize sorts NaN above everything and answers
+// dim - 1.  Either index is inside the embedding table; the project's rule is 0 and tests/test_va_ties.py pins it.
 template <int N4>
 __device__ __forceinline__ float bucket_count_lds(const float* edges, float v) {
     float cnt = 0.0f;
