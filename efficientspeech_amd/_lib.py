@@ -154,6 +154,7 @@ EXPORTS = (
     "esmi_forward_arena_bytes", "esmi_phoneme2mel_forward_f32", "esmi_hifigan_workspace_bytes", "esmi_hifigan_generator_f32",
     "esmi_hifigan_generator_ragged_f32", "esmi_hifigan_generator_prec_f32",
     "esmi_variance_adaptor_ctl_f32", "esmi_fuse_variance_adaptor_ctl_f32", "esmi_phoneme2mel_forward_ctl_f32",
+    "esmi_mel_decoder_prec_f32", "esmi_phoneme2mel_forward_prec_f32",
     "esmi_pack_resblock_bytes", "esmi_pack_resblock_f16",
     "esmi_train_conv_fwd_f32", "esmi_train_conv_ln_fwd_f32", "esmi_train_conv_dgrad_f32", "esmi_train_conv_wgrad_f32", "esmi_train_layernorm_fwd_f32",
     "esmi_train_conv_wgrad_workspace_bytes", "esmi_train_layernorm_bwd_workspace_bytes", "esmi_train_conv_workspace_bytes",
@@ -207,6 +208,7 @@ def bind(lib):
     lib.esmi_mel_decoder_blob_bytes.restype = sz
     lib.esmi_mel_decoder_pack_f32.argtypes = [P(DecoderWeights), P(DecoderShape), fp, fp]
     lib.esmi_mel_decoder_f32.argtypes = [fp, P(DecoderShape), fp, fp, fp, fp, fp, i, i, i, i, i, fp, fp, sz, fp]
+    lib.esmi_mel_decoder_prec_f32.argtypes = [fp, P(DecoderShape), fp, fp, fp, fp, fp, i, i, i, i, i, fp, fp, sz, i, fp]
     lib.esmi_mel_decoder_workspace_bytes.argtypes = [P(DecoderShape), i, i]
     lib.esmi_mel_decoder_workspace_bytes.restype = sz
     lib.esmi_mel_decoder_clock_probe.argtypes = [fp]
@@ -226,6 +228,7 @@ def bind(lib):
     lib.esmi_forward_arena_bytes.restype = sz
     lib.esmi_phoneme2mel_forward_f32.argtypes = [P(ForwardArgs), i, fp]
     lib.esmi_phoneme2mel_forward_ctl_f32.argtypes = [P(ForwardArgs), P(ProsodyControl), i, fp]
+    lib.esmi_phoneme2mel_forward_prec_f32.argtypes = [P(ForwardArgs), P(ProsodyControl), i, i, fp]
     i64, f, dbl = C.c_int64, C.c_float, C.c_double
     lib.esmi_train_conv_fwd_f32.argtypes = [P(ConvDesc), fp, fp, fp, fp, fp, sz, fp]
     lib.esmi_train_conv_ln_fwd_f32.argtypes = [P(ConvDesc), fp, fp, fp, fp, fp, fp, fp, i, fp, fp, fp, fp, fp, sz, fp]

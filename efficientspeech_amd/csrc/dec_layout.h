@@ -171,5 +171,10 @@ template <int DX2, int KD>
 int launch_mel_decoder(const MelDecP& p, dim3 grid, hipStream_t st);
 template <int DX2, int KD>
 int set_dec_clock(long long* slots);
+// ... and the same pair of the precision-16 kernel (tu_dec_<dx2>_<k>_p16.hip, ESMI_DEC_INSTANCE_P16; split build only)
+template <int DX2, int KD>
+int launch_mel_decoder_p16(const MelDecP& p, dim3 grid, hipStream_t st);
+template <int DX2, int KD>
+int set_dec_clock_p16(long long* slots);
 
 }  // namespace esmi

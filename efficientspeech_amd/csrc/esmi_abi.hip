@@ -789,14 +789,22 @@ size_t esmi_forward_arena_bytes(const esmi_forward_args* a) {
     return fwd_arena(a, &o) == ESMI_OK ? o.total + fwd_dec_tail(a, o) : 0;
 }
 
-static int forward_impl(const esmi_forward_args* a, const esmi_prosody_control* ctl, int stage, esmi_stream_t stream);
+static int forward_impl(const esmi_forward_args* a, const esmi_prosody_control* ctl, int precision, int stage, esmi_stream_t stream);
 int esmi_phoneme2mel_forward_f32(const esmi_forward_args* a, int stage, esmi_stream_t stream) {
     return esmi_phoneme2mel_forward_ctl_f32(a, nullptr, stage, stream);
 }
 int esmi_phoneme2mel_forward_ctl_f32(const esmi_forward_args* a, const esmi_prosody_control* ctl, int stage, esmi_stream_t stream) {
+    return esmi_phoneme2mel_forward_prec_f32(a, ctl, 32, stage, stream);
+}
+int esmi_phoneme2mel_forward_prec_f32(const esmi_forward_args* a, const esmi_prosody_control* ctl, int precision, int stage, esmi_stream_t stream) {
     if (!a) return ESMI_ERR_ARG;
+    if (stage == 1) precision = 32;   // (the encoder side has one arithmetic: stage 1 ignores the argument)
+    if (precision != 0 && precision != 32 && precision != 16) return ESMI_ERR_ARG;
+#if ESMI_DEC_SPLIT != 2
+    if (precision == 16) return ESMI_ERR_UNSUPPORTED;   // no binary16 products in this build: refused before the encoder side is enqueued
+#endif
     if (stage != 2 && ctl_conflict(ctl, nullptr, nullptr, a->dur_forced)) return ESMI_ERR_ARG;   // (a forced duration is final)
-    if (!a->range_flag) return forward_impl(a, ctl, stage, stream);
+    if (!a->range_flag) return forward_impl(a, ctl, precision, stage, stream);
 #if ESMI_RANGE_CHECK
     // validation mode: clear the word, point every translation unit's kernels at it, run, wait, read it back
     hipError_t e = hipMemsetAsync(a->range_flag, 0, sizeof(int32_t), S(stream));
@@ -804,10 +812,11 @@ int esmi_phoneme2mel_forward_ctl_f32(const esmi_forward_args* a, const esmi_pros
     int (*const setters[])(int*) = {set_range_flag_abi, set_range_flag_convgemm, set_range_flag_attention, set_range_flag_enc_merge,
                                     set_range_flag_enc_block, set_range_flag_enc_attn_ffn, set_range_flag_enc_fuse_va, set_range_flag_enc_va16, set_range_flag_enc_va64, set_range_flag_enc_pred128, set_range_flag_enc_block16,
                                     set_range_flag_decoder, set_range_flag_dec_128_5, set_range_flag_dec_128_3, set_range_flag_dec_256_5,
-                                    set_range_flag_dec_256_3, set_range_flag_hifigan, set_range_flag_hifigan_amp, set_range_flag_train};
+                                    set_range_flag_dec_256_3, set_range_flag_dec_128_5_p16, set_range_flag_dec_128_3_p16, set_range_flag_dec_256_5_p16,
+                                    set_range_flag_dec_256_3_p16, set_range_flag_hifigan, set_range_flag_hifigan_amp, set_range_flag_train};
     for (auto set : setters)
         if (int rc = set(reinterpret_cast<int*>(a->range_flag))) return rc;
-    int rc = forward_impl(a, ctl, stage, stream);
+    int rc = forward_impl(a, ctl, precision, stage, stream);
     int32_t flag = 0;
     if (!rc) rc = read_device_flag(a->range_flag, S(stream), &flag);
     for (auto set : setters) set(nullptr);
@@ -855,7 +864,7 @@ int encoder_side_one_launch(const esmi_forward_args* a, const esmi_encoder_block
 }
 }  // namespace
 
-static int forward_impl(const esmi_forward_args* a, const esmi_prosody_control* ctl, int stage, esmi_stream_t stream) {
+static int forward_impl(const esmi_forward_args* a, const esmi_prosody_control* ctl, int precision, int stage, esmi_stream_t stream) {
     FwdArena o;
     int rc = fwd_arena(a, &o);
     if (rc) return rc;
@@ -903,10 +912,10 @@ static int forward_impl(const esmi_forward_args* a, const esmi_prosody_control* 
         // the decoder's carried rows: the encoder side's scratch (free again), or the arena's tail region when that is too small
         const size_t dec_need = esmi_mel_decoder_workspace_bytes(&a->dec_shape, B, a->L_out);
         const bool use_tail = dec_need > o.feat - o.ws && a->arena_bytes >= o.total + dec_need;
-        rc = esmi_mel_decoder_f32(a->dec_blob, &a->dec_shape, feat, head_ok ? h0 : nullptr, cum, a->mel_len,
-                                  a->lmax_host < 0 ? a->lmax_dev : nullptr, a->lmax_host, mask != nullptr && B > 1, B, T, a->L_out,
-                                  a->mel, use_tail ? base + o.total : base + o.ws, use_tail ? a->arena_bytes - o.total : o.feat - o.ws,
-                                  stream);
+        rc = esmi_mel_decoder_prec_f32(a->dec_blob, &a->dec_shape, feat, head_ok ? h0 : nullptr, cum, a->mel_len,
+                                       a->lmax_host < 0 ? a->lmax_dev : nullptr, a->lmax_host, mask != nullptr && B > 1, B, T, a->L_out,
+                                       a->mel, use_tail ? base + o.total : base + o.ws, use_tail ? a->arena_bytes - o.total : o.feat - o.ws,
+                                       precision, stream);
         if (rc) return rc;
     }
     return ESMI_OK;

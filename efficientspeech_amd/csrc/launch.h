@@ -136,6 +136,10 @@ int set_range_flag_dec_128_5(int* flag);
 int set_range_flag_dec_128_3(int* flag);
 int set_range_flag_dec_256_5(int* flag);
 int set_range_flag_dec_256_3(int* flag);
+int set_range_flag_dec_128_5_p16(int* flag);
+int set_range_flag_dec_128_3_p16(int* flag);
+int set_range_flag_dec_256_5_p16(int* flag);
+int set_range_flag_dec_256_3_p16(int* flag);
 int set_range_flag_hifigan(int* flag);
 int set_range_flag_hifigan_amp(int* flag);
 int set_range_flag_train(int* flag);

@@ -121,6 +121,13 @@ __device__ __forceinline__ void dec_store_planes(unsigned* base, int off, const 
     *reinterpret_cast<u32x2*>(rowp + DX2 / 2) = u32x2{h2a, h2b};
 }
 
+// precision 16 (include/esmi.h): four floats -> ONE plane, the nearest binary16 of each (round to nearest even), same dwords as the first
+// plane above; the second plane's dwords are neither written nor read
+__device__ __forceinline__ void dec_store_plane16(unsigned* base, int off, const f32x4& v) {
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    *reinterpret_cast<u32x2*>(base + off) = u32x2{round_f16_pair(v[0], v[1]), round_f16_pair(v[2], v[3])};   // (checked build: range-noted there)
+}
+
 // measurement aid (g_dec_clk, dec_layout.h): the FIRST workgroup stamps {shader clock, 100 MHz clock} when it starts -> slot 0, and again
 // -> slot 1 at the start of each later chunk (dx2 = 256) / in front of its mel stage (dx2 = 128, one chunk).  (slot 1 - slot 0) is a
 // long stretch of the workgroup's life: shader ticks / 100 MHz ticks = the clock the CU ran at.  Both stamps come from ONE workgroup:
@@ -149,8 +156,13 @@ __device__ __forceinline__ void dec_zero_acc(f32x16 (&acc)[MT][NTW]) {
 // NW waves per window (8 or 16): wave (mh = w>>2, ns = w&3) owns rows [128/MH*mh, +128/MH) x columns [ns*DX2/4, +DX2/4).
 // NW = 16 (dx2 = 256, one workgroup per CU either way): four waves per SIMD instead of two inside every barrier-separated
 // phase -- the phases are latency-bound, so the extra waves are what hides it -- at 128 VGPRs (one 32-row tile per wave).
-template <int DX2, int KD, int NW>
+// P16 (precision 16, include/esmi.h; split build only): every contraction runs ONE f16 product per 16-channel step on operands rounded
+// to the nearest binary16 -- the weights' first plane, one activation plane -- instead of the three of the fp32-accurate split.  Phases,
+// barriers, LDS layout, grid and the chunk walk are those of the default kernel; every difference is an `if constexpr (P16)` below.
+template <int DX2, int KD, int NW, bool P16 = false>
 __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void mel_decoder_kernel(const MelDecP p) {
+    static_assert(!P16 || ESMI_DEC_SPLIT == 2, "precision 16 exists in the split build only");
+    constexpr int NPL = P16 ? 1 : 2;        // operand planes per 16-channel step
     constexpr int kDecThreads = 64 * NW;    // shadows the namespace constant inside this kernel
     constexpr int NS = 4;                   // column slices per workgroup
     constexpr int MH = NW / NS;             // row groups (2 or 4)
@@ -414,7 +426,7 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
     constexpr int KSUB = DX2 <= 128 ? (SPLIT ? 4 : 8) / NTW : (NW > 8 ? 2 : 8);   // k-steps (of 8 channels) of weights in registers at a time
     // the wave's B fragments of KSUB k-steps: the split form's two f16 planes per 16-channel step / the exact-fp32 form's float4 per k-step
     constexpr int KS16 = KSUB / 2;
-    std::conditional_t<SPLIT, u32x4[NTW][KS16][2], f32x4[NTW][KSUB]> bf;
+    std::conditional_t<SPLIT, u32x4[NTW][KS16][NPL], f32x4[NTW][KSUB]> bf;
     auto load_b = [&](int wsl, int k0) __attribute__((always_inline)) {   // wsl: float offset of the wave's weight slice in the blob
         if constexpr (SPLIT) {
 #pragma unroll
@@ -422,7 +434,7 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
 #pragma unroll
                 for (int st = 0; st < KS16; ++st) {
 #pragma unroll
-                    for (int pl = 0; pl < 2; ++pl)
+                    for (int pl = 0; pl < NPL; ++pl)
                         bf[t][st][pl] = __builtin_bit_cast(u32x4, blob_ld(wsl + ((t * 8 + (k0 >> 1) + st) * 2 + pl) * 256, lane16));
                 }
             }
@@ -443,9 +455,15 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
                     const float* ap = a_base + 32 * mt * LDSROW + a_col0 + 8 * k0 + 16 * st;
-                    const f16x2p a2 = split_f16x2(*reinterpret_cast<const f32x4*>(ap), *reinterpret_cast<const f32x4*>(ap + 4));
+                    if constexpr (P16) {
+                        const u32x4 a1 = round_f16x8(*reinterpret_cast<const f32x4*>(ap), *reinterpret_cast<const f32x4*>(ap + 4));
 #pragma unroll
-                    for (int t = 0; t < NTW; ++t) acc[mt][t] = mfma32_split2_wx(bf[t][st][0], bf[t][st][1], a2, acc[mt][t]);
+                        for (int t = 0; t < NTW; ++t) acc[mt][t] = mfma32_f16(bf[t][st][0], a1, acc[mt][t]);
+                    } else {
+                        const f16x2p a2 = split_f16x2(*reinterpret_cast<const f32x4*>(ap), *reinterpret_cast<const f32x4*>(ap + 4));
+#pragma unroll
+                        for (int t = 0; t < NTW; ++t) acc[mt][t] = mfma32_split2_wx(bf[t][st][0], bf[t][st][1], a2, acc[mt][t]);
+                    }
                 }
             }
         } else {
@@ -479,7 +497,7 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
     constexpr int WD = DX2 > 128 ? kDecWeightRing256 : 0;
     constexpr int NSTEP = 8 * KCH, NITEM = NSTEP * MT;
     static_assert(WD >= 0 && WD <= NSTEP, "ring depth");
-    u32x4 wr[WD > 0 ? WD : 1][NTW][2];
+    u32x4 wr[WD > 0 ? WD : 1][NTW][NPL];
     // (`ntc`: 32-column tiles per wave of THIS contraction -- NTW for the conv layers; 1 for the mel Linear of the dx2 = 256 kernel, whose
     // n_mel <= 96 columns are packed as three one-tile slices so that three SIMDs share them instead of two)
     auto w_fetch = [&](int off, int s, int slot, auto ntc) __attribute__((always_inline)) {
@@ -488,7 +506,7 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
 #pragma unroll
-            for (int pl = 0; pl < 2; ++pl) wr[slot][t][pl] = __builtin_bit_cast(u32x4, blob_ld(wsl + ((t * 8 + (s & 7)) * 2 + pl) * 256, lane16));
+            for (int pl = 0; pl < NPL; ++pl) wr[slot][t][pl] = __builtin_bit_cast(u32x4, blob_ld(wsl + ((t * 8 + (s & 7)) * 2 + pl) * 256, lane16));
         }
     };
     // the first WD weight steps of the matrix at `off` (issued ahead of the barrier that precedes the K loop: the L2 round
@@ -515,11 +533,17 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
 #pragma unroll
                         for (int mt = 0; mt < MT; ++mt) {
                             const unsigned* ap = a_base + 32 * mt * LDSROW + 64 * c + 4 * k0 + 8 * st;
-                            f16x2p a2;
-                            a2.h1 = *reinterpret_cast<const u32x4*>(ap);
-                            a2.h2 = *reinterpret_cast<const u32x4*>(ap + DX2 / 2);
+                            if constexpr (P16) {
+                                const u32x4 a1 = *reinterpret_cast<const u32x4*>(ap);
 #pragma unroll
-                            for (int t = 0; t < NTW; ++t) acc[mt][t] = mfma32_split2_wx(bf[t][st][0], bf[t][st][1], a2, acc[mt][t]);
+                                for (int t = 0; t < NTW; ++t) acc[mt][t] = mfma32_f16(bf[t][st][0], a1, acc[mt][t]);
+                            } else {
+                                f16x2p a2;
+                                a2.h1 = *reinterpret_cast<const u32x4*>(ap);
+                                a2.h2 = *reinterpret_cast<const u32x4*>(ap + DX2 / 2);
+#pragma unroll
+                                for (int t = 0; t < NTW; ++t) acc[mt][t] = mfma32_split2_wx(bf[t][st][0], bf[t][st][1], a2, acc[mt][t]);
+                            }
                         }
                     }
                 }
@@ -530,7 +554,7 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
                 const int s = q / MT, mt = q % MT;
                 const unsigned* ap = a_base + 32 * mt * LDSROW + 64 * (s >> 3) + 8 * (s & 7);
                 ar.h1 = *reinterpret_cast<const u32x4*>(ap);
-                ar.h2 = *reinterpret_cast<const u32x4*>(ap + DX2 / 2);
+                if constexpr (!P16) ar.h2 = *reinterpret_cast<const u32x4*>(ap + DX2 / 2);
             };
             a_fetch(0);
             sched_fence();
@@ -538,8 +562,10 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
             for (int q = 0; q < NITEM; ++q) {
                 const int s = q / MT, mt = q % MT;
 #pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    acc[mt][t] = mfma32_split2_wx(wr[s % (WD > 0 ? WD : 1)][t][0], wr[s % (WD > 0 ? WD : 1)][t][1], ar, acc[mt][t]);
+                for (int t = 0; t < NT; ++t) {
+                    if constexpr (P16) acc[mt][t] = mfma32_f16(wr[s % (WD > 0 ? WD : 1)][t][0], ar.h1, acc[mt][t]);
+                    else acc[mt][t] = mfma32_split2_wx(wr[s % (WD > 0 ? WD : 1)][t][0], wr[s % (WD > 0 ? WD : 1)][t][1], ar, acc[mt][t]);
+                }
                 if (q + 1 < NITEM) a_fetch(q + 1);
                 if (mt == MT - 1 && s + WD < NSTEP) w_fetch(off, s + WD, s % (WD > 0 ? WD : 1), ntc);
                 sched_fence();
@@ -686,7 +712,8 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = inside[mt] ? acc[mt][t][4 * g + e] : 0.0f;
                     if (SPLIT && planes_) {
-                        dec_store_planes<DX2>(pbase, 32 * mt * LDSROW + 4 * g, v);
+                        if constexpr (P16) dec_store_plane16(pbase, 32 * mt * LDSROW + 4 * g, v);
+                        else dec_store_planes<DX2>(pbase, 32 * mt * LDSROW + 4 * g, v);
                     } else if (keep_row[mt]) {
                         *reinterpret_cast<f32x4*>(base + 32 * mt * LDSROW + 8 * g) = v;
                     }
@@ -735,13 +762,17 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
 #pragma unroll
                 for (int k = 0; k < NV; ++k) {   // (spelled out, not dec_store_planes: with the call the dx2 = 128 kernels' listing differs from
                                                  // its predecessor's -- the same instructions in another order; whether that costs time is unmeasured)
-                    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-                    unsigned h1a, h2a, h1b, h2b;
-                    split_f16_pair(v[j][k][0], v[j][k][1], h1a, h2a);
-                    split_f16_pair(v[j][k][2], v[j][k][3], h1b, h2b);
-                    unsigned* rowp = reinterpret_cast<unsigned*>(ln_ptr + j * LDSROW) - 2 * ln_c + 2 * TPR * k;   // dword 2*(channel group)
-                    *reinterpret_cast<u32x2*>(rowp) = u32x2{h1a, h1b};
-                    *reinterpret_cast<u32x2*>(rowp + DX2 / 2) = u32x2{h2a, h2b};
+                    if constexpr (P16) {
+                        dec_store_plane16(reinterpret_cast<unsigned*>(ln_ptr + j * LDSROW) - 2 * ln_c, 2 * TPR * k, v[j][k]);
+                    } else {
+                        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+                        unsigned h1a, h2a, h1b, h2b;
+                        split_f16_pair(v[j][k][0], v[j][k][1], h1a, h2a);
+                        split_f16_pair(v[j][k][2], v[j][k][3], h1b, h2b);
+                        unsigned* rowp = reinterpret_cast<unsigned*>(ln_ptr + j * LDSROW) - 2 * ln_c + 2 * TPR * k;   // dword 2*(channel group)
+                        *reinterpret_cast<u32x2*>(rowp) = u32x2{h1a, h1b};
+                        *reinterpret_cast<u32x2*>(rowp + DX2 / 2) = u32x2{h2a, h2b};
+                    }
                 }
             }
             return;
@@ -939,7 +970,8 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
                     for (int e = 0; e < 4; ++e) a[e] = fmaf(win[r + j][e], tap[j][e], a[e]);
                 }
                 if (SPLIT) {   // the K loop's A operand, already split (esmi_dev.h): 4 channels = 2 dwords per plane
-                    dec_store_planes<DX2>(prow, r * LDSROW, a);
+                    if constexpr (P16) dec_store_plane16(prow, r * LDSROW, a);   // (one plane, nearest binary16)
+                    else dec_store_planes<DX2>(prow, r * LDSROW, a);
                 } else {
                     *reinterpret_cast<f32x4*>(col + (r + PAD) * LDSROW) = a;
                 }
@@ -1124,7 +1156,25 @@ int launch_mel_decoder(const MelDecP& p, dim3 grid, hipStream_t st) {
     return launch_status();
 }
 
+// ... and of the precision-16 kernel of (DX2, KD): tu_dec_<dx2>_<k>_p16.hip (split build only; an empty unit otherwise)
+template <int DX2, int KD>
+int set_dec_clock_p16(long long* slots) { return store_dec_clock_pointer(slots); }
+
+template <int DX2, int KD>
+int launch_mel_decoder_p16(const MelDecP& p, dim3 grid, hipStream_t st) {
+    constexpr int NW = 8;
+    const int lds = (dec_lds_floats<DX2>(KD) + p.carry_lds_layers * (KD / 2) * DX2) * (int)sizeof(float);
+    ESMI_LAUNCH_LDS((mel_decoder_kernel<DX2, KD, NW, true>), grid, dim3(64 * NW), lds, st, p);
+    return launch_status();
+}
+
 }  // namespace esmi
+
+#define ESMI_DEC_INSTANCE_P16(DX2, KD)                                                                \
+    namespace esmi {                                                                                  \
+    template int set_dec_clock_p16<DX2, KD>(long long*);                                              \
+    template int launch_mel_decoder_p16<DX2, KD>(const MelDecP&, dim3, hipStream_t);                  \
+    }
 
 #define ESMI_DEC_INSTANCE(DX2, KD)                                                                    \
     ESMI_TU_RANGE_SETTER(dec_##DX2##_##KD)                                                            \

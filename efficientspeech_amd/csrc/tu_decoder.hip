@@ -65,17 +65,25 @@ int dec_pack(const esmi_decoder_weights* w, const esmi_decoder_shape* s, float* 
     return launch_status();
 }
 
-// the (dx2, kernel) instantiations: launcher and clock-probe setter (defined in tu_dec_<dx2>_<k>.hip), blob size and packer
+// the (dx2, kernel) instantiations: launcher and clock-probe setter (defined in tu_dec_<dx2>_<k>.hip), those of the precision-16 kernel
+// (tu_dec_<dx2>_<k>_p16.hip; NULL in the exact-fp32 build, which has no binary16 products), blob size and packer
 struct DecInst {
     int dx2, kd;
     int (*launch)(const MelDecP&, dim3, hipStream_t);
     int (*set_clock)(long long*);
+    int (*launch16)(const MelDecP&, dim3, hipStream_t);
+    int (*set_clock16)(long long*);
     long (*blob_floats)(int d4, int n_blocks, int block_depth);
     int (*pack)(const esmi_decoder_weights*, const esmi_decoder_shape*, float*, hipStream_t);
 };
 template <int DX2, int KD>
 constexpr DecInst dec_inst_of() {
-    return {DX2, KD, launch_mel_decoder<DX2, KD>, set_dec_clock<DX2, KD>, DecLay<DX2, KD>::floats, dec_pack<DX2, KD>};
+#if ESMI_DEC_SPLIT == 2
+    return {DX2, KD, launch_mel_decoder<DX2, KD>, set_dec_clock<DX2, KD>, launch_mel_decoder_p16<DX2, KD>, set_dec_clock_p16<DX2, KD>,
+            DecLay<DX2, KD>::floats, dec_pack<DX2, KD>};
+#else
+    return {DX2, KD, launch_mel_decoder<DX2, KD>, set_dec_clock<DX2, KD>, nullptr, nullptr, DecLay<DX2, KD>::floats, dec_pack<DX2, KD>};
+#endif
 }
 const DecInst kDecInst[] = {dec_inst_of<128, 5>(), dec_inst_of<128, 3>(), dec_inst_of<256, 5>(), dec_inst_of<256, 3>()};
 const DecInst* dec_inst(const esmi_decoder_shape* s) {   // (after dec_check: the shape is one of the table's)
@@ -91,8 +99,11 @@ extern "C" {
 // measurement aid (include/esmi.h): arm / disarm the clock probe of every decoder instantiation (one device global per unit)
 int esmi_mel_decoder_clock_probe(int64_t* dev_slots) {
     long long* s = reinterpret_cast<long long*>(dev_slots);
-    for (const DecInst& d : kDecInst)
+    for (const DecInst& d : kDecInst) {
         if (int rc = d.set_clock(s)) return rc;
+        if (d.set_clock16)
+            if (int rc = d.set_clock16(s)) return rc;
+    }
     return ESMI_OK;
 }
 
@@ -163,7 +174,9 @@ size_t esmi_mel_decoder_workspace_bytes(const esmi_decoder_shape* s, int B, int 
 
 static int mel_decoder_launch(const float* blob, const esmi_decoder_shape* s, const float* x, const float* h0,
                               const int32_t* cum, const int32_t* mel_len, const int32_t* lmax_dev, int lmax_host, int apply_mask, int B, int T,
-                              int L_out, float* mel, void* workspace, size_t workspace_bytes, esmi_stream_t stream) {
+                              int L_out, float* mel, void* workspace, size_t workspace_bytes, int precision, esmi_stream_t stream) {
+    // precision (include/esmi.h): 0 / 32 the fp32-accurate kernel; 16 one binary16 product per contraction; refused before anything else
+    if (precision != 0 && precision != 32 && precision != 16) return ESMI_ERR_ARG;
     int rc = dec_check(s);
     if (rc) return rc;
     if (!blob || (!x && !h0) || !mel || B <= 0 || L_out <= 0 || !aligned16(blob) || (x && !aligned16(x))) return ESMI_ERR_ARG;
@@ -174,6 +187,7 @@ static int mel_decoder_launch(const float* blob, const esmi_decoder_shape* s, co
     MelDecP p;
     p.blob = blob;
     const DecInst* inst = dec_inst(s);
+    if (precision == 16 && !inst->launch16) return ESMI_ERR_UNSUPPORTED;   // (checked before the first launch: nothing is enqueued)
     if (inst->blob_floats(s->d4, s->n_blocks, s->block_depth) > kDecBlobMaxFloats) return ESMI_ERR_UNSUPPORTED;
     p.d4 = s->d4; p.n_blocks = s->n_blocks; p.block_depth = s->block_depth; p.n_mel = s->n_mel;
     p.x = x; p.h0 = h0; p.cum = cum; p.mel_len = mel_len; p.lmax_dev = lmax_dev; p.lmax_host = lmax_host;
@@ -204,12 +218,19 @@ static int mel_decoder_launch(const float* blob, const esmi_decoder_shape* s, co
         p.n_seg = (L_out + p.seg_len - 1) / p.seg_len;
     }
     dim3 grid((unsigned)(p.n_seg * ((B + 7) / 8) * 8)), block(kDecThreads);
-    return inst->launch(p, grid, st);
+    return precision == 16 ? inst->launch16(p, grid, st) : inst->launch(p, grid, st);
 }
 
 int esmi_mel_decoder_f32(const float* blob, const esmi_decoder_shape* s, const float* x, const float* h0,
                          const int32_t* cum, const int32_t* mel_len, const int32_t* lmax_dev, int lmax_host, int apply_mask, int B, int T,
                          int L_out, float* mel, void* workspace, size_t workspace_bytes, esmi_stream_t stream) {
-    return mel_decoder_launch(blob, s, x, h0, cum, mel_len, lmax_dev, lmax_host, apply_mask, B, T, L_out, mel, workspace, workspace_bytes, stream);
+    return mel_decoder_launch(blob, s, x, h0, cum, mel_len, lmax_dev, lmax_host, apply_mask, B, T, L_out, mel, workspace, workspace_bytes, 32, stream);
+}
+
+int esmi_mel_decoder_prec_f32(const float* blob, const esmi_decoder_shape* s, const float* x, const float* h0,
+                              const int32_t* cum, const int32_t* mel_len, const int32_t* lmax_dev, int lmax_host, int apply_mask, int B, int T,
+                              int L_out, float* mel, void* workspace, size_t workspace_bytes, int precision, esmi_stream_t stream) {
+    return mel_decoder_launch(blob, s, x, h0, cum, mel_len, lmax_dev, lmax_host, apply_mask, B, T, L_out, mel, workspace, workspace_bytes, precision,
+                              stream);
 }
 }  // extern "C"

@@ -142,6 +142,18 @@ __device__ __forceinline__ void split_f16_pair_rn(float a, float b, unsigned& h1
     h2 = __builtin_bit_cast(unsigned, r);
 #endif
 }
+// two values rounded to binary16 (nearest even), a in the low half: one dword of a single-piece (`precision 16`) operand
+__device__ __forceinline__ unsigned round_f16_pair(float a, float b) {
+    range_note(a);
+    range_note(b);
+#ifdef ESMI_WAVESIM
+    return f32_to_f16_bits(a, false) | (f32_to_f16_bits(b, false) << 16);
+#else
+    typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+    const f16x2_t h = {(_Float16)a, (_Float16)b};
+    return __builtin_bit_cast(unsigned, h);
+#endif
+}
 // 8 consecutive k of one row rounded to binary16 (nearest even), in the k-slot order of split_f16x2: the single-piece operand of the
 // `precision=16` training GEMMs
 __device__ __forceinline__ u32x4 round_f16x8(const f32x4& x0, const f32x4& x1) {

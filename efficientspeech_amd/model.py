@@ -147,7 +147,8 @@ class EfficientSpeech(nn.Module):
             return mel, mel_len, duration
         return self.hifigan(mel).squeeze(1), mel_len, duration
 
-    def synthesize(self, batch, pcm16=False, pitch_control=None, energy_control=None, duration_control=None, precision=None):
+    def synthesize(self, batch, pcm16=False, pitch_control=None, energy_control=None, duration_control=None, precision=None,
+                   decoder_precision=None):
         """Length-aware `predict_step`: (wav (B, L * hop), wav_len = mel_len * hop, duration).  `mel_len` goes to the vocoder as the
         device tensor it is (no host synchronisation): the generator's stages of at most 64 channels skip the frames behind each
         utterance's end (hifigan.Generator.forward), the samples from
@@ -157,13 +158,20 @@ class EfficientSpeech(nn.Module):
         `pitch_control`, `energy_control`, `duration_control`: per-utterance prosody scales (a number, or a tensor of shape (B,) or ()),
         the same as the input-dict keys of those names (`networks._prosody_controls`: the prediction that is bucketized / rounded is
         multiplied inside the kernels; `duration_control=1.25` speaks 25 % slower).  An argument that is given replaces the batch's key.
-        `precision`: the vocoder's, 32 or 16 (hifigan.Generator.forward; the acoustic model is fp32 either way); None: the vocoder's own."""
+        `precision`: the vocoder's, 32 or 16 (hifigan.Generator.forward); None: the vocoder's own.
+        `decoder_precision`: the mel decoder's, 32 or 16 -- the input-dict key of that name (`Phoneme2Mel._launch`; the argument replaces
+        the batch's key); None: the decoder's own `precision` attribute.  The encoder side is fp32-accurate either way, so `wav_len` and
+        `duration` do not depend on it.  `precision=16, decoder_precision=16` is the reference's `--precision 16` for both the decoder
+        and the vocoder."""
         if precision is not None and precision not in (16, 32):
             raise ValueError(f"vocoder precision must be 32 or 16, got {precision!r}")
         if self.hifigan is None:
             raise RuntimeError("synthesize() needs a vocoder: attach one (hifigan=Generator(...) / get_hifigan(...)); "
                                "predict_step returns the mel when there is none")
-        controls = {"pitch_control": pitch_control, "energy_control": energy_control, "duration_control": duration_control}
+        if decoder_precision is not None and (isinstance(decoder_precision, bool) or decoder_precision not in (16, 32)):
+            raise ValueError(f"decoder precision must be 32 or 16, got {decoder_precision!r}")
+        controls = {"pitch_control": pitch_control, "energy_control": energy_control, "duration_control": duration_control,
+                    "decoder_precision": decoder_precision}
         if any(v is not None for v in controls.values()):
             batch = dict(batch, **{k: v for k, v in controls.items() if v is not None})
         mel, mel_len, duration = self.phoneme2mel(batch, train=False)

@@ -563,8 +563,20 @@ class FeatureUpsampler(nn.Module):
         return features, masks.bool().unsqueeze(-1).expand(-1, -1, Cc), mel_len
 
 
+def _decoder_precision(precision, default=32):
+    """The mel decoder's precision argument (32, or 16: include/esmi.h, esmi_mel_decoder_prec_f32) validated on the host; None -> `default`."""
+    if precision is None:
+        precision = default
+    if isinstance(precision, bool) or precision not in (16, 32):
+        raise ValueError(f"decoder precision must be 32 or 16, got {precision!r}")
+    return int(precision)
+
+
 class MelDecoder(_PackedModule):
-    """Mel spectrogram decoder (networks.py:261-304), one fused HIP kernel per call."""
+    """Mel spectrogram decoder (networks.py:261-304), one fused HIP kernel per call.
+    `precision` (a plain attribute, not in the state_dict; default 32): 16 runs every contraction of the kernel as ONE binary16
+    product with fp32 accumulation (include/esmi.h) -- the same packed weights, the same launch geometry.  It is the default of
+    `forward` and of the inference forward of `Phoneme2Mel`; `Phoneme2Mel.forward(x, train=True)` runs the decoder at 32 regardless."""
 
     def __init__(self, dim, kernel_size=5, n_mel_channels=80, n_blocks=2, block_depth=2):
         super().__init__()
@@ -587,6 +599,7 @@ class MelDecoder(_PackedModule):
         self.timing = None      # bench.py sets this to a list to collect (start, end) HIP events per timed launch
         self.timing_every = 1   # ... on every n-th launch only (an event pair costs ~10 us of pipeline drain per step)
         self._launches = 0
+        self.precision = 32     # forward's default: 32, or 16 (one binary16 product per contraction)
 
     def _shape(self):
         return _lib.DecoderShape(self.dim_x4, self.dim_x2, self.kernel_size, self.n_blocks, self.block_depth,
@@ -626,12 +639,20 @@ class MelDecoder(_PackedModule):
             return blob
         return self._cache.get(lambda: list(self.parameters()), build)
 
-    def forward(self, features):
+    def forward(self, features, precision=None):
         with _on_device_of(self.mel_linear.weight):
-            return self._forward(features)
+            return self._forward(features, precision)
 
-    def _forward(self, features):
-        """features (B,L,4*dim) -> mel (B,L,n_mel).  (Direct mode: rows exactly as given.)"""
+    def _decode(self, lib, precision, *args):
+        """the decoder launch: the plain entry point at precision 32, esmi_mel_decoder_prec_f32 at 16 (args: those of the plain one)"""
+        if precision == 32:
+            lib.esmi_mel_decoder_f32(*args)
+        else:
+            lib.esmi_mel_decoder_prec_f32(*args[:-1], precision, args[-1])
+
+    def _forward(self, features, precision=None):
+        """features (B,L,4*dim) -> mel (B,L,n_mel).  (Direct mode: rows exactly as given.)  precision: 32 or 16; None: `self.precision`."""
+        precision = _decoder_precision(precision, self.precision)
         x = _f32(features)
         lib, stream = _runtime(x)
         B, L, _ = x.shape
@@ -639,8 +660,8 @@ class MelDecoder(_PackedModule):
         if L > 0:
             shape = self._shape()
             ws, ws_bytes = self._workspace(lib, shape, B, L, x.device)
-            lib.esmi_mel_decoder_f32(_ptr(self._packed(lib, stream)), C.byref(shape), _ptr(x), None, None, None, None, L, 0,
-                                     B, 0, L, _ptr(mel), _ptr(ws), ws_bytes, stream)
+            self._decode(lib, precision, _ptr(self._packed(lib, stream)), C.byref(shape), _ptr(x), None, None, None, None, L, 0,
+                         B, 0, L, _ptr(mel), _ptr(ws), ws_bytes, stream)
         return mel
 
     @staticmethod
@@ -665,9 +686,10 @@ class MelDecoder(_PackedModule):
             return _lib.DecoderHead(d4=self.dim_x4, dx2=self.dim_x2, **{k: _ptr(v) for k, v in t.items()}), list(t.values())
         return self._head_cache.get(lambda: list(self.proj.parameters()), build)
 
-    def _fused(self, feat, cum, mel_len, lmax_dev, lmax_host, apply_mask, L_out, h0=None):
+    def _fused(self, feat, cum, mel_len, lmax_dev, lmax_host, apply_mask, L_out, h0=None, precision=None):
         """Length-regulator gather fused into the decoder: feat (B,T,d4) phoneme-rate; h0 (B,T,dx2) = the first stage's
         output at phoneme rate when the encoder side computed it."""
+        precision = _decoder_precision(precision, self.precision)
         lib, stream = _runtime(feat)
         B, T, _ = feat.shape
         mel = torch.empty((B, L_out, self.n_mel_channels), dtype=torch.float32, device=feat.device)
@@ -680,8 +702,8 @@ class MelDecoder(_PackedModule):
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
             ws, ws_bytes = self._workspace(lib, shape, B, L_out, feat.device)
-            lib.esmi_mel_decoder_f32(_ptr(blob), C.byref(shape), _ptr(feat), _ptr(h0), _ptr(cum), _ptr(mel_len), _ptr(lmax_dev),
-               int(lmax_host), int(apply_mask), B, T, L_out, _ptr(mel), _ptr(ws), ws_bytes, stream)
+            self._decode(lib, precision, _ptr(blob), C.byref(shape), _ptr(feat), _ptr(h0), _ptr(cum), _ptr(mel_len), _ptr(lmax_dev),
+                         int(lmax_host), int(apply_mask), B, T, L_out, _ptr(mel), _ptr(ws), ws_bytes, stream)
             if ev is not None:
                 ev[1].record()
                 self.timing.append(ev)
@@ -833,8 +855,11 @@ class Phoneme2Mel(nn.Module):
         if isinstance(x, list):                                       # ONNX-export quirk kept (:418-419)
             x = x[0]
         if train:
+            if "decoder_precision" in x:
+                raise ValueError("decoder_precision: an inference extension, as the prosody controls are (train=True always runs the "
+                                 "decoder at precision 32)")
             pred = self.encoder(x, train=True)
-            mel = self.decoder(pred["features"])
+            mel = self.decoder(pred["features"], precision=32)     # (whatever `decoder.precision` says: that is inference's default)
             mask = pred["masks"]
             if mask is not None and mel.size(0) > 1:                  # :424-427
                 lib, stream = _runtime(mel)
@@ -907,7 +932,9 @@ class Phoneme2Mel(nn.Module):
         """Enqueue the inference forward (stage 0), its encoder side only (1), or the decoder (2) on the `state` a stage-1
         call returned (a multi-GPU caller MAX-reduces `state.lmax` in between).  -> namespace with mel, mel_len,
         duration (B,T,1), lmax (device scalar or None).
-        Inference extension keys of x: `duration_forced`, `max_mel_len` (`max_mel_len_exact`), and the per-utterance prosody controls
+        Inference extension keys of x: `duration_forced`, `max_mel_len` (`max_mel_len_exact`), `decoder_precision` (16 or 32, validated on
+        the host: the mel decoder's arithmetic for this call, overriding `self.decoder.precision`; the encoder side is untouched by it, so
+        mel_len and the durations are the same bits either way -- include/esmi.h), and the per-utterance prosody controls
         `pitch_control`, `energy_control`, `duration_control` (a number or a (B,) / () tensor each; numbers are validated on the host,
         device tensors are not synchronised for it: `_prosody_controls`).
         taps (tests): also return what `PhonemeEncoder._encode` exposes -- `state.taps` = pitch, energy (B,T) raw predictions,
@@ -934,6 +961,8 @@ class Phoneme2Mel(nn.Module):
                 tap = {k: torch.empty((B, T), dtype=torch.float32 if k in ("pitch", "energy") else torch.int32, device=dev)
                        for k in ("pitch", "energy", "pitch_idx", "energy_idx", "dur", "cum")}
             st = SimpleNamespace(ids=ids, m8=_mask_u8(phoneme_mask), dur_t=dur_t, B=B, T=T, lmax=None, mel=None, L_out=None,
+                                 precision=_decoder_precision(x.get("decoder_precision"), self.decoder.precision),
+                                 prec_entry="decoder_precision" in x or self.decoder.precision != 32,
                                  ctl=ctl, ctl_keep=ctl_keep, taps=tap,
                                  lmax_host=None, plan=_lib.current_plan(),
                                  mel_len=torch.empty((B,), dtype=torch.int32, device=dev),
@@ -960,7 +989,9 @@ class Phoneme2Mel(nn.Module):
         dec = self.decoder
 
         def forward(stage_):                   # (with controls: the _ctl entry point; stage 2 ignores them)
-            if st.ctl is None:
+            if st.prec_entry and stage_ != 1:   # (a precision was asked for -- 32 included: the _prec entry point; stage 1 has one arithmetic)
+                lib.esmi_phoneme2mel_forward_prec_f32(C.byref(a), None if st.ctl is None else C.byref(st.ctl), st.precision, stage_, stream)
+            elif st.ctl is None:
                 lib.esmi_phoneme2mel_forward_f32(C.byref(a), stage_, stream)
             else:
                 lib.esmi_phoneme2mel_forward_ctl_f32(C.byref(a), C.byref(st.ctl), stage_, stream)

@@ -16,6 +16,7 @@ throughput.
 import torch
 import torch.distributed as dist
 
+from .networks import _decoder_precision
 
 
 def _encode_with_head(net, x, need_lmax=True):
@@ -127,6 +128,9 @@ class GraphedForward:
         assert "max_mel_len" in x, "graph replay needs a static output length (x['max_mel_len'])"
         _refuse_controls_in_graph(x)
         self.net = net
+        # the decoder's precision is captured with its launch: the key of `x`, else the decoder's attribute AS IT IS NOW (`load` refuses
+        # a step that asks for another one)
+        self.precision = _decoder_precision(x.get("decoder_precision"), net.decoder.precision)
         self.L = int(x["max_mel_len"])
         self.x = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in x.items()}
         B = self.x["phoneme"].shape[0]
@@ -136,7 +140,8 @@ class GraphedForward:
         with torch.cuda.stream(side), torch.no_grad():       # warm-up off the capture: weight packing, attributes
             for _ in range(warmup):
                 enc = _encode_with_head(net, self.x)
-                net.decoder._fused(enc["feat"], enc["cum"], enc["mel_len"], enc["lmax"], self.L, self.apply_mask, self.L, h0=enc["h0"])
+                net.decoder._fused(enc["feat"], enc["cum"], enc["mel_len"], enc["lmax"], self.L, self.apply_mask, self.L, h0=enc["h0"],
+                                   precision=self.precision)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.g_enc = torch.cuda.CUDAGraph()
@@ -147,13 +152,17 @@ class GraphedForward:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g), torch.no_grad():
                 mel = net.decoder._fused(self.enc["feat"], self.enc["cum"], self.enc["mel_len"], self.enc["lmax"],
-                                         self.L, self.apply_mask, self.L, h0=self.enc["h0"])
+                                         self.L, self.apply_mask, self.L, h0=self.enc["h0"], precision=self.precision)
             self.g_dec.append(g)
             self.mels.append(mel)
         self.i = 0
 
     def load(self, x):
         _refuse_controls_in_graph(x)
+        want = _decoder_precision(x.get("decoder_precision"), self.net.decoder.precision)
+        if want != self.precision:   # (refuse, never drop: the captured decoder launch has one arithmetic)
+            raise NotImplementedError(f"decoder_precision: this step asks for precision {want}, the captured graph runs the decoder at "
+                                      f"{self.precision} (the key, or `decoder.precision`, at capture time); build a new GraphedForward")
         for k, v in x.items():
             if torch.is_tensor(v) and v.data_ptr() != self.x[k].data_ptr():
                 self.x[k].copy_(v, non_blocking=True)

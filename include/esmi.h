@@ -33,7 +33,8 @@ extern "C" {
 #endif
 
 #define ESMI_VERSION 501 /* 0.5.1: esmi_train_conv_ln_fwd_f32, then esmi_hifigan_generator_ragged_f32, then esmi_prosody_control and the three
-                            *_ctl_f32 entry points, then esmi_hifigan_generator_prec_f32 (additions; nothing else changed shape).  0.5.0 (round 5): esmi_mel_decoder_clock_probe;
+                            *_ctl_f32 entry points, then esmi_hifigan_generator_prec_f32, then esmi_mel_decoder_prec_f32 and
+                            esmi_phoneme2mel_forward_prec_f32 (additions; nothing else changed shape).  0.5.0 (round 5): esmi_mel_decoder_clock_probe;
                             0.4.0: esmi_decoder_head.proj_w (the decoder's first stage at phoneme rate for every model size:
                           * esmi_decoder_head_f32).  0.3.0: training entry points changed shape (esmi_conv_desc: act / packed_fwd / packed_grad; LayerNorm with
                           * residual / row mask / activation arguments; esmi_train_loss_args.grad_seed; esmi_train_pack_weights_f32,
@@ -481,6 +482,33 @@ int esmi_phoneme2mel_forward_f32(const esmi_forward_args* a, int stage, esmi_str
  * rounding of :379-382): applied inside the encoder-side kernels, the one-launch form included.  ctl == NULL: exactly the call above.
  * duration_scale together with a->dur_forced is ESMI_ERR_ARG (nothing launched).  Stage 2 (the decoder alone) ignores ctl. */
 int esmi_phoneme2mel_forward_ctl_f32(const esmi_forward_args* a, const esmi_prosody_control* ctl, int stage, esmi_stream_t stream);
+
+/* Mel decoder at precision 16 (opt-in; the same rule as the vocoder's, esmi_hifigan_generator_prec_f32 below: the reference synthesises
+ * under its Trainer's `--precision 16` autocast, utils/tools.py:326-327).  EVERY contraction the decoder kernel runs -- the pointwise
+ * convolutions, the mel Linear, and the `proj` Linear when the kernel runs its first stage itself (direct mode, or no h0):
+ *   - both operands are rounded to binary16, round to nearest even.  The activation is rounded as it is written as the K loop's
+ *     operand: the depthwise convolution's output, the last LayerNorm's rows (mel Linear), the fp32 input rows (`proj`);
+ *   - accumulation is fp32, with ONE MFMA product per 16-channel step (v_mfma_f32_32x32x16_f16) instead of the three of the
+ *     fp32-accurate split, one LDS operand plane instead of two, half the weight bytes read;
+ *   - everything else stays fp32: depthwise taps, biases, tanh, every LayerNorm, the skip tensor, the h0 gather, the rows carried between
+ *     chunks, the mel output.  Phases, grid, LDS and workspace are those of precision 32.
+ * The weight operand is the FIRST plane of the esmi_mel_decoder_pack_f32 blob, which already is the nearest binary16 of 2^8 * W: one blob
+ * serves both precisions, and the 2^-8 comes out in the epilogue as at precision 32.
+ * The encoder side is NOT touched (a deliberate scope line): pitch / energy buckets, durations, the scan and h0 stay fp32-accurate, so
+ * mel_len, the durations and cum of a forward are bit for bit the same at precision 16 and 32; only the mel differs, by the error of any
+ * binary16-operand implementation: 7e-4 .. 2e-3 rms, 3e-3 .. 2e-2 L-inf on mels of magnitude 4 .. 15 (tiny / small / base).
+ * Activations beyond the binary16 range (|a| >= 65520) become +-inf, as under torch autocast; libesmi_checked.so range-checks every value
+ * it rounds.
+ * precision 0 / 32: exactly esmi_mel_decoder_f32 (the same kernel, the same bits); 16: as above; anything else: ESMI_ERR_ARG.
+ * libesmi_fp32mfma.so has no binary16 products: precision 16 is ESMI_ERR_UNSUPPORTED there.  Nothing is launched by a refused call. */
+int esmi_mel_decoder_prec_f32(const float* blob, const esmi_decoder_shape* s, const float* x, const float* h0, const int32_t* cum,
+                              const int32_t* mel_len, const int32_t* lmax_dev, int lmax_host, int apply_mask, int B, int T, int L_out,
+                              float* mel, void* workspace, size_t workspace_bytes, int precision, esmi_stream_t stream);
+/* The whole forward with the decoder's precision: ctl == NULL as in esmi_phoneme2mel_forward_f32, else as in the _ctl call.  Stage 1 (the
+ * encoder side alone) ignores `precision`; stages 0 and 2 hand it to the decoder.  A refused precision launches nothing, the encoder
+ * side included. */
+int esmi_phoneme2mel_forward_prec_f32(const esmi_forward_args* a, const esmi_prosody_control* ctl, int precision, int stage,
+                                      esmi_stream_t stream);
 
 /* ------------------------------------------------------------------ HiFi-GAN generator (the vocoder behind model.py:161-162)
  * hifigan/models.py:84-135 Generator.forward with ResBlock1 (:20-58) or ResBlock2 (:61-82), weights as after

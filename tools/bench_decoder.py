@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Development tool: time mel_decoder_kernel alone (fused-LR mode, D-const) for one or more library builds.
-   python tools/bench_decoder.py [--config tiny] [--libs a.so b.so ...]"""
+   python tools/bench_decoder.py [--config tiny] [--libs a.so b.so ...]
+--precision 16 (esmi_mel_decoder_prec_f32: one binary16 product per contraction): times precision 32 and 16 of the same call in alternating
+legs 32 / 16 / 32 / 16 in one process, and prints per-leg medians, the spread of the two precision-32 legs (the noise a ratio has to
+beat), the ratio and the difference of the two mels."""
 import argparse, ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -12,6 +15,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="tiny"); ap.add_argument("--batch", type=int, default=256)
 ap.add_argument("--phonemes", type=int, default=128); ap.add_argument("--dur", type=int, default=6)
 ap.add_argument("--zeros", action="store_true", help="zero activations (DVFS probe: same instruction stream, less switching power)"); ap.add_argument("--iters", type=int, default=30); ap.add_argument("--h0", action="store_true", help="phoneme-rate first stage supplied (what the full forward does for tiny, T <= 128)"); ap.add_argument("--burst", type=int, default=20, help="launches per timed burst (back-to-back, one event pair)"); ap.add_argument("--libs", nargs="*", default=[_lib.LIB_PATH])
+ap.add_argument("--precision", type=int, default=32, choices=(32, 16))
 a = ap.parse_args()
 cfg = CONFIGS[a.config]
 B, T, L = a.batch, a.phonemes, a.phonemes * a.dur
@@ -29,6 +33,32 @@ for path in a.libs:
     if a.zeros:
         feat.zero_()
         if h0 is not None: h0.zero_()
+    if a.precision == 16:
+        def leg(pr):
+            ts = []
+            for _ in range(a.iters):
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                for _ in range(a.burst):
+                    m = dec._fused(feat, cum, mel_len, None, L, True, L, h0=h0, precision=pr)
+                e.record()
+                torch.cuda.synchronize(); ts.append(s.elapsed_time(e) / a.burst)
+            return float(np.median(ts)) * 1e3, m
+        for _ in range(3):
+            for pr in (32, 16):
+                dec._fused(feat, cum, mel_len, None, L, True, L, h0=h0, precision=pr)
+        torch.cuda.synchronize()
+        legs = [(pr,) + leg(pr) for pr in (32, 16, 32, 16)]      # alternating: both precisions see the same clocks and neighbours
+        t32, t16 = [t for pr, t, _ in legs if pr == 32], [t for pr, t, _ in legs if pr == 16]
+        m32, m16 = legs[0][2].double(), legs[1][2].double()
+        d = m16 - m32
+        noise = abs(t32[0] - t32[1]) / np.mean(t32)
+        print(f"{os.path.basename(path)} {a.config} B={B} T={T} D={a.dur} h0={bool(a.h0)}: legs us " + "  ".join(f"p{pr} {t:.1f}" for pr, t, _ in legs))
+        print(f"  precision 32 {np.mean(t32):8.1f} us (two legs, spread {noise * 100:.2f} %)   precision 16 {np.mean(t16):8.1f} us (spread "
+              f"{abs(t16[0] - t16[1]) / np.mean(t16) * 100:.2f} %)   16 / 32 = {np.mean(t16) / np.mean(t32):.3f}   speed-up {np.mean(t32) / np.mean(t16):.3f}x")
+        print(f"  mel16 - mel32: L-inf {float(d.abs().max()):.2e} rms {float(d.pow(2).mean().sqrt()):.2e} (mel32 rms {float(m32.pow(2).mean().sqrt()):.3f}, "
+              f"max {float(m32.abs().max()):.2f})   finite={bool(torch.isfinite(legs[1][2]).all())}", flush=True)
+        continue
     for _ in range(5):
         mel = dec._fused(feat, cum, mel_len, None, L, True, L, h0=h0)
     torch.cuda.synchronize()
