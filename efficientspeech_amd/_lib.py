@@ -106,6 +106,12 @@ class ProsodyControl(C.Structure):
     _fields_ = [("pitch_scale", fp), ("energy_scale", fp), ("duration_scale", fp)]
 
 
+class ProsodyCurves(C.Structure):
+    """esmi_prosody_curves (include/esmi.h): per quantity NULL = 1, a (B) array, or -- `*_per_phoneme` != 0 -- a (B, T) curve."""
+    _fields_ = [("pitch_scale", fp), ("energy_scale", fp), ("duration_scale", fp),
+                ("pitch_per_phoneme", C.c_int32), ("energy_per_phoneme", C.c_int32), ("duration_per_phoneme", C.c_int32)]
+
+
 class ForwardArgs(C.Structure):
     """esmi_forward_args (include/esmi.h): the whole inference forward behind one call."""
     _fields_ = [(n, C.c_int) for n in ("B", "T", "depth", "dim", "fuse_kernel", "plan")] + \
@@ -155,6 +161,7 @@ EXPORTS = (
     "esmi_hifigan_generator_ragged_f32", "esmi_hifigan_generator_prec_f32",
     "esmi_variance_adaptor_ctl_f32", "esmi_fuse_variance_adaptor_ctl_f32", "esmi_phoneme2mel_forward_ctl_f32",
     "esmi_mel_decoder_prec_f32", "esmi_phoneme2mel_forward_prec_f32",
+    "esmi_variance_adaptor_curve_f32", "esmi_fuse_variance_adaptor_curve_f32", "esmi_phoneme2mel_forward_curve_f32",
     "esmi_pack_resblock_bytes", "esmi_pack_resblock_f16",
     "esmi_train_conv_fwd_f32", "esmi_train_conv_ln_fwd_f32", "esmi_train_conv_dgrad_f32", "esmi_train_conv_wgrad_f32", "esmi_train_layernorm_fwd_f32",
     "esmi_train_conv_wgrad_workspace_bytes", "esmi_train_layernorm_bwd_workspace_bytes", "esmi_train_conv_workspace_bytes",
@@ -194,11 +201,13 @@ def bind(lib):
     lib.esmi_variance_adaptor_workspace_bytes.restype = sz
     lib.esmi_variance_adaptor_f32.argtypes = [P(PredictorWeights)] * 3 + [i, i, i] + [fp] * 11 + [fp, sz, fp]
     lib.esmi_variance_adaptor_ctl_f32.argtypes = lib.esmi_variance_adaptor_f32.argtypes + [P(ProsodyControl)]
+    lib.esmi_variance_adaptor_curve_f32.argtypes = lib.esmi_variance_adaptor_f32.argtypes + [P(ProsodyCurves)]
     lib.esmi_fuse_variance_adaptor_workspace_bytes.argtypes = [i, i, i, i]
     lib.esmi_fuse_variance_adaptor_workspace_bytes.restype = sz
     lib.esmi_fuse_variance_adaptor_f32.argtypes = [P(FuseWeights), i, i, i, i, i, P(fp), P(i)] + [P(PredictorWeights)] * 3 + \
         [fp] * 13 + [P(DecoderHead), fp, i] + [fp, sz, fp]
     lib.esmi_fuse_variance_adaptor_ctl_f32.argtypes = lib.esmi_fuse_variance_adaptor_f32.argtypes + [P(ProsodyControl)]
+    lib.esmi_fuse_variance_adaptor_curve_f32.argtypes = lib.esmi_fuse_variance_adaptor_f32.argtypes + [P(ProsodyCurves)]
     lib.esmi_decoder_head_f32.argtypes = [P(DecoderHead), C.c_long, fp, fp, fp]
     lib.esmi_max_i32.argtypes = [fp, i, fp, fp]
     lib.esmi_length_regulate_i32.argtypes = [fp, i, i, fp, fp, fp, fp]
@@ -229,6 +238,7 @@ def bind(lib):
     lib.esmi_phoneme2mel_forward_f32.argtypes = [P(ForwardArgs), i, fp]
     lib.esmi_phoneme2mel_forward_ctl_f32.argtypes = [P(ForwardArgs), P(ProsodyControl), i, fp]
     lib.esmi_phoneme2mel_forward_prec_f32.argtypes = [P(ForwardArgs), P(ProsodyControl), i, i, fp]
+    lib.esmi_phoneme2mel_forward_curve_f32.argtypes = [P(ForwardArgs), P(ProsodyCurves), i, i, fp]
     i64, f, dbl = C.c_int64, C.c_float, C.c_double
     lib.esmi_train_conv_fwd_f32.argtypes = [P(ConvDesc), fp, fp, fp, fp, fp, sz, fp]
     lib.esmi_train_conv_ln_fwd_f32.argtypes = [P(ConvDesc), fp, fp, fp, fp, fp, fp, fp, i, fp, fp, fp, fp, fp, sz, fp]

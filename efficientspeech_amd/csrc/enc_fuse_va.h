@@ -327,6 +327,7 @@ __device__ __forceinline__ void enc_fuse_va_body(const FuseVaP& p) {
         lb[q] = w_.lin_b[0];
     }
     const float sc[3] = {ctl_scale(p.pitch_s, b), ctl_scale(p.energy_s, b), ctl_scale(p.dur_s, b)};   // prosody controls (scalars)
+    const bool cv[3] = {(p.curve & kCurvePitch) != 0, (p.curve & kCurveEnergy) != 0, (p.curve & kCurveDur) != 0};   // ... or (B, T) curves in tv[]
 #pragma unroll
     for (int nt = 0; nt < ND; ++nt) {
         g2[nt] = p.pred[2].ln2_g[32 * nt + i];
@@ -488,7 +489,8 @@ __device__ __forceinline__ void enc_fuse_va_body(const FuseVaP& p) {
             if (q == 2) s = fmaxf(s, 0.0f);
             pr[q][r] = s;
             if (q < 2) {   // compile-time branch; the ballots are executed by all lanes
-                const float v = (has_t && !rout[r]) ? tv[q][r] : s * sc[q];   // (a teacher value is never scaled)
+                // (a teacher value is never scaled; a curve's entry sits in the teacher slot: va_row_scale)
+                const float v = (has_t && !rout[r] && !cv[q]) ? tv[q][r] : s * va_row_scale(cv[q], tv[q][r], sc[q], rz[r] || rout[r]);
                 int bi = 0;
 #pragma unroll
                 for (int e = 0; e < ND; ++e) {
@@ -523,7 +525,8 @@ __device__ __forceinline__ void enc_fuse_va_body(const FuseVaP& p) {
             if (q == 2) {
 #pragma unroll
                 for (int nt = 0; nt < ND; ++nt) buf_st(r_feat, frow + 128u * nt, rz[r] ? 0.0f : c[2][nt][r]);
-                float d = p.dur_t ? (float)__builtin_bit_cast(int, tv[2][r]) : rintf(pr[2][r] * sc[2]);   // torch.round: half to even
+                float d = (p.dur_t && !cv[2]) ? (float)__builtin_bit_cast(int, tv[2][r])
+                                              : rintf(pr[2][r] * va_row_scale(cv[2], tv[2][r], sc[2], rz[r] || rout[r]));   // torch.round: half to even
                 if (p.mask) {                                                                        // networks.py:381-382
                     if (rz[r]) d = 0.0f;
                     d = fmaxf(d, 0.0f);

@@ -24,6 +24,7 @@ struct Pred128P {
     int* mel_len;                   // (B)
     int B, T;
     const float *pitch_s, *energy_s, *dur_s;   // prosody controls: (B) scale of the prediction that is bucketized / rounded, or NULL = 1
+    int curve;                      // kCurve* bits: that quantity's teacher pointer above holds a (B, T) fp32 prosody curve instead (FuseVaP::curve)
 };
 // enc_ffn64.h (everything behind the attention of a C = 64, one-head block: one workgroup per utterance)
 struct PostAttn64P {
@@ -85,6 +86,10 @@ struct FuseVaP {
     // prosody controls (inference): (B) fp32 each or NULL = 1.  The value that is bucketized is pred * pitch_s[b] / pred * energy_s[b], the
     // duration rounds pred * dur_s[b]; one fp32 multiply each (va_decide.h).  Teacher / forced values are never scaled, preds[] stay the raw predictions.
     const float *pitch_s, *energy_s, *dur_s;
+    // per-phoneme prosody curves: bit q set (kCurvePitch / kCurveEnergy / kCurveDur) = pitch_t / energy_t / dur_t does not hold teacher
+    // values but a (B, T) fp32 curve, the scale of each row's own prediction (va_decide.h: va_row_scale); that quantity's *_s is NULL then.
+    // A runtime field, wave-uniform: the kernels keep one instantiation and the row's one teacher-slot load serves either meaning.
+    int curve;
 };
 
 }  // namespace esmi

@@ -140,8 +140,15 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_pred128_kernel(const Pred128P p
         buf_st(r_pred, srow, pr);
         if (q < 2) {   // torch.bucketize(v, edges, right=False) = number of edges strictly below v; the embedding row -> feat
             const float* tv = q == 0 ? p.pitch_t : p.energy_t;
+            const bool cv = (p.curve & (q == 0 ? kCurvePitch : kCurveEnergy)) != 0;   // (a curve sits in the teacher slot: va_row_scale)
             // (the rules of va_decide.h, called per side so that only a teacher row loads its teacher value)
-            const float v = (tv && !rout[t]) ? va_bucket_input(true, tv[(long)b * p.T + pos[t]], 0.0f, 1.0f) : va_bucket_input(false, 0.0f, pr, sc);
+            float v;
+            if (tv && !rout[t]) {
+                const float tvq = tv[(long)b * p.T + pos[t]];
+                v = cv ? va_bucket_input(false, 0.0f, pr, va_row_scale(true, tvq, sc, rz[t])) : va_bucket_input(true, tvq, 0.0f, 1.0f);
+            } else {
+                v = va_bucket_input(false, 0.0f, pr, va_row_scale(cv, 1.0f, sc, true));
+            }
             const int bidx = (int)row_sum4(bucket_count_lds<8>(par + PP_EDGE + 32 * g, v));
             int* idx = q == 0 ? p.pitch_idx : p.energy_idx;
             if (idx) {
@@ -163,8 +170,15 @@ __global__ __launch_bounds__(64 * 8, 1) void enc_pred128_kernel(const Pred128P p
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
                 buf_st4(r_feat, frow == kBufOOB ? kBufOOB : frow + (unsigned)((3 * DIM + 16 * nt + 4 * g) * 4), rz[t] ? z4 : c[t][nt]);
-            const float dval = (p.dur_t && !rout[t]) ? va_duration(true, (float)p.dur_t[(long)b * p.T + pos[t]], 0.0f, 1.0f, p.mask != nullptr, rz[t])
-                                                     : va_duration(false, 0.0f, pr, sc, p.mask != nullptr, rz[t]);
+            const bool cv = (p.curve & kCurveDur) != 0;
+            float dval;
+            if (p.dur_t && !rout[t]) {
+                const int tvd = p.dur_t[(long)b * p.T + pos[t]];    // (a forced duration, or the curve's fp32 entry in the same slot)
+                dval = cv ? va_duration(false, 0.0f, pr, va_row_scale(true, __builtin_bit_cast(float, tvd), sc, rz[t]), p.mask != nullptr, rz[t])
+                          : va_duration(true, (float)tvd, 0.0f, 1.0f, p.mask != nullptr, rz[t]);
+            } else {
+                dval = va_duration(false, 0.0f, pr, va_row_scale(cv, 1.0f, sc, true), p.mask != nullptr, rz[t]);
+            }
             if (g == 0) sdur[pos[t]] = va_scan_term(dval, rout[t]);
             const BufRsrc r_dur = make_rsrc(p.dur + (long)b * p.T, (long)p.T * 4);
             buf_st_i(r_dur, srow, (int)dval);

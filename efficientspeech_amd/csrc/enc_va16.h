@@ -320,7 +320,9 @@ __device__ __forceinline__ void enc_va16_body(const FuseVaP& p) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const bool has_t = q == 0 ? p.pitch_t != nullptr : p.energy_t != nullptr;
-        const float v = va_bucket_input(has_t && !rout, q == 0 ? tv_p : tv_e, pr[q], q == 0 ? sc_p : sc_e);
+        const bool cv = (p.curve & (q == 0 ? kCurvePitch : kCurveEnergy)) != 0;   // (a curve sits in the teacher slot: va_row_scale)
+        const float tvq = q == 0 ? tv_p : tv_e;
+        const float v = va_bucket_input(has_t && !rout && !cv, tvq, pr[q], va_row_scale(cv, tvq, q == 0 ? sc_p : sc_e, rz || rout));
         bidx[q] = (int)row_sum4(bucket_count_lds<2>(par + PV_EDGE + 32 * q + 8 * g, v));
     }
     // embedding rows from the LDS copies of the tables, in the head's B-operand order (k-step 1 = pitch, 2 = energy: the lane's eight
@@ -344,7 +346,9 @@ __device__ __forceinline__ void enc_va16_body(const FuseVaP& p) {
         layernorm<2>(df, gg, bb);
         if (rz) { df[0] = z4; df[1] = z4; }
     }
-    const float dval = va_duration(p.dur_t != nullptr, (float)__builtin_bit_cast(int, tv_d), pr[2], sc_d, p.mask != nullptr, rz);
+    const bool cv_d = (p.curve & kCurveDur) != 0;
+    const float dval = va_duration(p.dur_t != nullptr && !cv_d, (float)__builtin_bit_cast(int, tv_d), pr[2], va_row_scale(cv_d, tv_d, sc_d, rz || rout),
+                                   p.mask != nullptr, rz);
     if (p.cum && g == 0) sdur[pos] = va_scan_term(dval, rout);
     ESMI_CT();   // 6: predictions done
     // ---------------- outputs behind the last barrier that waits for the vector-memory queue (no barrier waits for a store)

@@ -321,7 +321,9 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const bool has_t = q == 0 ? p.pitch_t != nullptr : p.energy_t != nullptr;
-            const float v = va_bucket_input(has_t && !rout[t], q == 0 ? tv_p[t] : tv_e[t], pr[q][t], q == 0 ? sc_p : sc_e);
+            const bool cv = (p.curve & (q == 0 ? kCurvePitch : kCurveEnergy)) != 0;   // (a curve sits in the teacher slot: va_row_scale)
+            const float tvq = q == 0 ? tv_p[t] : tv_e[t];
+            const float v = va_bucket_input(has_t && !rout[t] && !cv, tvq, pr[q][t], va_row_scale(cv, tvq, q == 0 ? sc_p : sc_e, rz[t] || rout[t]));
             bidx[q] = (int)row_sum4(bucket_count_lds<4>(par + VP_EDGE + 64 * q + 16 * g, v));
             hidx[t][q] = bidx[q];
             if (p.feat) {           // the embedding row: lane group g copies floats [16 g, 16 g + 16) of it
@@ -347,7 +349,9 @@ __device__ __forceinline__ void enc_va64_body(const FuseVaP& p) {
             }
             if (p.h0) to_bop(df, DF[t], lower);
         }
-        const float dval = va_duration(p.dur_t != nullptr, (float)__builtin_bit_cast(int, tv_d[t]), pr[2][t], sc_d, p.mask != nullptr, rz[t]);
+        const bool cv_d = (p.curve & kCurveDur) != 0;
+        const float dval = va_duration(p.dur_t != nullptr && !cv_d, (float)__builtin_bit_cast(int, tv_d[t]), pr[2][t],
+                                       va_row_scale(cv_d, tv_d[t], sc_d, rz[t] || rout[t]), p.mask != nullptr, rz[t]);
         if (p.cum && g == 0) sdur[pos[t]] = va_scan_term(dval, rout[t]);
         const unsigned srow = (!rout[t] && g == 0) ? (unsigned)(pos[t] * 4) : kBufOOB;   // one lane per row
 #pragma unroll

@@ -369,9 +369,33 @@ int esmi_fuse_f32(const esmi_fuse_weights* w, int depth, int dim, int kernel, in
 
 size_t esmi_variance_adaptor_workspace_bytes(int B, int T, int dim) { return align256((size_t)B * T * dim * 4); }
 
-// a prosody scale next to the teacher / forced values of the same quantity: the caller asked for two things at once
-static bool ctl_conflict(const esmi_prosody_control* ctl, const void* pitch_t, const void* energy_t, const void* dur_t) {
+// a prosody scale or curve next to the teacher / forced values of the same quantity: the caller asked for two things at once
+static bool ctl_conflict(const esmi_prosody_curves* ctl, const void* pitch_t, const void* energy_t, const void* dur_t) {
     return ctl && ((ctl->pitch_scale && pitch_t) || (ctl->energy_scale && energy_t) || (ctl->duration_scale && dur_t));
+}
+// the per-utterance struct as the general one: every pointer is (B)
+static esmi_prosody_curves per_utterance(const esmi_prosody_control* ctl) {
+    esmi_prosody_curves c{};
+    if (ctl) { c.pitch_scale = ctl->pitch_scale; c.energy_scale = ctl->energy_scale; c.duration_scale = ctl->duration_scale; }
+    return c;
+}
+// What the deciding kernels get (enc_params.h FuseVaP::curve, va_decide.h va_row_scale).  A (B, T) curve and the teacher / forced array of
+// its quantity are mutually exclusive (ctl_conflict), and every kernel loads that array's entry per row anyway: the curve takes the
+// array's place, its kCurve* bit says so, and the quantity's (B) scale is absent.
+struct VaControls {
+    const float *pitch_t, *energy_t;
+    const int32_t* dur_t;
+    const float *pitch_s, *energy_s, *dur_s;
+    int curve;
+};
+static VaControls va_controls(const esmi_prosody_curves& c, const float* pitch_t, const float* energy_t, const int32_t* dur_t) {
+    VaControls v{pitch_t, energy_t, dur_t, c.pitch_scale, c.energy_scale, c.duration_scale, 0};
+    if (c.pitch_scale && c.pitch_per_phoneme) { v.pitch_t = c.pitch_scale; v.pitch_s = nullptr; v.curve |= kCurvePitch; }
+    if (c.energy_scale && c.energy_per_phoneme) { v.energy_t = c.energy_scale; v.energy_s = nullptr; v.curve |= kCurveEnergy; }
+    if (c.duration_scale && c.duration_per_phoneme) {
+        v.dur_t = reinterpret_cast<const int32_t*>(c.duration_scale); v.dur_s = nullptr; v.curve |= kCurveDur;
+    }
+    return v;
 }
 
 int esmi_variance_adaptor_f32(const esmi_predictor_weights* pitch, const esmi_predictor_weights* energy,
@@ -390,6 +414,17 @@ int esmi_variance_adaptor_ctl_f32(const esmi_predictor_weights* pitch, const esm
                                   float* feat, float* pitch_pred, float* energy_pred, float* duration_pred,
                                   int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur, void* workspace,
                                   size_t workspace_bytes, esmi_stream_t stream, const esmi_prosody_control* ctl) {
+    const esmi_prosody_curves c = per_utterance(ctl);
+    return esmi_variance_adaptor_curve_f32(pitch, energy, duration, dim, B, T, mask, pitch_target, energy_target, duration_target, feat, pitch_pred,
+                                           energy_pred, duration_pred, pitch_idx, energy_idx, dur, workspace, workspace_bytes, stream, &c);
+}
+
+int esmi_variance_adaptor_curve_f32(const esmi_predictor_weights* pitch, const esmi_predictor_weights* energy,
+                                    const esmi_predictor_weights* duration, int dim, int B, int T, const uint8_t* mask,
+                                    const float* pitch_target, const float* energy_target, const int32_t* duration_target,
+                                    float* feat, float* pitch_pred, float* energy_pred, float* duration_pred,
+                                    int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur, void* workspace,
+                                    size_t workspace_bytes, esmi_stream_t stream, const esmi_prosody_curves* ctl) {
     if (ctl_conflict(ctl, pitch_target, energy_target, duration_target)) return ESMI_ERR_ARG;
     if (!pitch || !energy || !duration || !feat || !pitch_pred || !energy_pred || !duration_pred || !dur || !workspace)
         return ESMI_ERR_ARG;
@@ -404,10 +439,11 @@ int esmi_variance_adaptor_ctl_f32(const esmi_predictor_weights* pitch, const esm
     VaTailP v;
     v.rows = B * T; v.T = T; v.dim = dim; v.mask = mask;
     v.pitch_pred = pitch_pred; v.energy_pred = energy_pred; v.dur_pred = duration_pred;
-    v.pitch_t = pitch_target; v.energy_t = energy_target; v.dur_t = duration_target;
+    const VaControls vc = va_controls(ctl ? *ctl : esmi_prosody_curves{}, pitch_target, energy_target, duration_target);
+    v.pitch_t = vc.pitch_t; v.energy_t = vc.energy_t; v.dur_t = vc.dur_t;
+    v.pitch_s = vc.pitch_s; v.energy_s = vc.energy_s; v.dur_s = vc.dur_s; v.curve = vc.curve;
     v.pbins = pitch->bins; v.ebins = energy->bins; v.pemb = pitch->emb; v.eemb = energy->emb;
     v.feat = feat; v.pitch_idx = pitch_idx; v.energy_idx = energy_idx; v.dur = dur;
-    v.pitch_s = ctl ? ctl->pitch_scale : nullptr; v.energy_s = ctl ? ctl->energy_scale : nullptr; v.dur_s = ctl ? ctl->duration_scale : nullptr;
     if (!v.pbins || !v.ebins || !v.pemb || !v.eemb) return ESMI_ERR_ARG;
     if (dim & 3) return ESMI_ERR_UNSUPPORTED;                  // (dim = embed_dim // reduction: 32 / 64 / 128 for the published sizes)
     const long n = (long)B * T * (dim >> 2);                   // one thread per four channels
@@ -443,7 +479,7 @@ struct VaArgs {
     // h0, the phoneme-rate feature tensor, the pitch / energy predictions and the bucket indices are not written at all (16.8 MB of
     // stores per tiny-ES batch that nobody reads: the decoder gathers h0)
     bool lean;
-    esmi_prosody_control ctl;   // per-utterance scales of the predictions that are bucketized / rounded (all NULL: none)
+    esmi_prosody_curves ctl;    // (B) scales or (B, T) curves of the predictions that are bucketized / rounded (all NULL: none)
 };
 
 // does the fused Fuse + variance-adaptor chain kernel family (enc_va16 / enc_va64 / enc_fuse_va) serve this call?  (packed weights)
@@ -496,8 +532,9 @@ void pred_weights(const VaArgs& a, PredW* out) {
 FuseVaP va_chain_params(const VaArgs& a, bool head_in_chain, int* nw) {
     FuseVaP p = fuse_params(a);
     pred_weights(a, p.pred);
-    p.pitch_t = a.pitch_t; p.energy_t = a.energy_t; p.dur_t = a.dur_t;
-    p.pitch_s = a.ctl.pitch_scale; p.energy_s = a.ctl.energy_scale; p.dur_s = a.ctl.duration_scale;
+    const VaControls vc = va_controls(a.ctl, a.pitch_t, a.energy_t, a.dur_t);
+    p.pitch_t = vc.pitch_t; p.energy_t = vc.energy_t; p.dur_t = vc.dur_t;
+    p.pitch_s = vc.pitch_s; p.energy_s = vc.energy_s; p.dur_s = vc.dur_s; p.curve = vc.curve;
     for (int q = 0; q < 3; ++q) p.preds[q] = a.preds[q];
     p.pitch_idx = a.pitch_idx; p.energy_idx = a.energy_idx; p.dur = a.dur;
     fuse_va_plan(a.T, a.dim, a.depth, nw, &p.wgs_per_b, &p.useful, &p.halo);
@@ -572,14 +609,15 @@ int fuse_variance_adaptor(const VaArgs& a) {
         };
         auto predictors = [&]() -> int {
             if (chain16 && a.dim == 128 && pred128_weights_ok(a)) {
-                Pred128P q{{}, a.mask, a.pitch_t, a.energy_t, a.dur_t, a.feat, {a.preds[0], a.preds[1], a.preds[2]}, a.pitch_idx, a.energy_idx,
-                           a.dur, a.cum, a.mel_len, a.B, a.T, a.ctl.pitch_scale, a.ctl.energy_scale, a.ctl.duration_scale};
+                const VaControls vc = va_controls(a.ctl, a.pitch_t, a.energy_t, a.dur_t);
+                Pred128P q{{}, a.mask, vc.pitch_t, vc.energy_t, vc.dur_t, a.feat, {a.preds[0], a.preds[1], a.preds[2]}, a.pitch_idx, a.energy_idx,
+                           a.dur, a.cum, a.mel_len, a.B, a.T, vc.pitch_s, vc.energy_s, vc.dur_s, vc.curve};
                 pred_weights(a, q.pred);
                 ESMI_TRY(true, launch_enc_pred128(q, a.dim, st))
             }
-            const int r = esmi_variance_adaptor_ctl_f32(a.pw[0], a.pw[1], a.pw[2], a.dim, a.B, a.T, a.mask, a.pitch_t, a.energy_t, a.dur_t, a.feat,
-                                                        a.preds[0], a.preds[1], a.preds[2], a.pitch_idx, a.energy_idx, a.dur,
-                                                        static_cast<char*>(a.workspace) + fws, a.workspace_bytes - fws, a.stream, &a.ctl);
+            const int r = esmi_variance_adaptor_curve_f32(a.pw[0], a.pw[1], a.pw[2], a.dim, a.B, a.T, a.mask, a.pitch_t, a.energy_t, a.dur_t, a.feat,
+                                                          a.preds[0], a.preds[1], a.preds[2], a.pitch_idx, a.energy_idx, a.dur,
+                                                          static_cast<char*>(a.workspace) + fws, a.workspace_bytes - fws, a.stream, &a.ctl);
             if (r) return r;
             if (a.cum) launch_length_regulate(a.dur, a.B, a.T, a.cum, a.mel_len, nullptr, st);
             return ESMI_OK;
@@ -613,9 +651,23 @@ int esmi_fuse_variance_adaptor_ctl_f32(const esmi_fuse_weights* fw, int depth, i
                                        float* duration_pred, int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur,
                                        int32_t* cum, int32_t* mel_len, const esmi_decoder_head* head, float* h0, int plan,
                                        void* workspace, size_t workspace_bytes, esmi_stream_t stream, const esmi_prosody_control* ctl) {
+    const esmi_prosody_curves c = per_utterance(ctl);
+    return esmi_fuse_variance_adaptor_curve_f32(fw, depth, dim, kernel, B, T, feats, n_i, pitch, energy, duration, mask, pitch_target, energy_target,
+                                                duration_target, feat, pitch_pred, energy_pred, duration_pred, pitch_idx, energy_idx, dur, cum,
+                                                mel_len, head, h0, plan, workspace, workspace_bytes, stream, &c);
+}
+
+int esmi_fuse_variance_adaptor_curve_f32(const esmi_fuse_weights* fw, int depth, int dim, int kernel, int B, int T,
+                                         const float* const* feats, const int* n_i, const esmi_predictor_weights* pitch,
+                                         const esmi_predictor_weights* energy, const esmi_predictor_weights* duration,
+                                         const uint8_t* mask, const float* pitch_target, const float* energy_target,
+                                         const int32_t* duration_target, float* feat, float* pitch_pred, float* energy_pred,
+                                         float* duration_pred, int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur,
+                                         int32_t* cum, int32_t* mel_len, const esmi_decoder_head* head, float* h0, int plan,
+                                         void* workspace, size_t workspace_bytes, esmi_stream_t stream, const esmi_prosody_curves* ctl) {
     return fuse_variance_adaptor(VaArgs{fw, depth, dim, kernel, B, T, feats, n_i, {pitch, energy, duration}, mask, pitch_target, energy_target,
                                         duration_target, feat, {pitch_pred, energy_pred, duration_pred}, pitch_idx, energy_idx, dur, cum, mel_len,
-                                        head, h0, plan, workspace, workspace_bytes, stream, false, ctl ? *ctl : esmi_prosody_control{}});
+                                        head, h0, plan, workspace, workspace_bytes, stream, false, ctl ? *ctl : esmi_prosody_curves{}});
 }
 
 // MelDecoder's first stage at phoneme rate as one launch: GEMM (k = 1) + bias + tanh + LayerNorm in the epilogue (networks.py:291-293)
@@ -789,7 +841,7 @@ size_t esmi_forward_arena_bytes(const esmi_forward_args* a) {
     return fwd_arena(a, &o) == ESMI_OK ? o.total + fwd_dec_tail(a, o) : 0;
 }
 
-static int forward_impl(const esmi_forward_args* a, const esmi_prosody_control* ctl, int precision, int stage, esmi_stream_t stream);
+static int forward_impl(const esmi_forward_args* a, const esmi_prosody_curves* ctl, int precision, int stage, esmi_stream_t stream);
 int esmi_phoneme2mel_forward_f32(const esmi_forward_args* a, int stage, esmi_stream_t stream) {
     return esmi_phoneme2mel_forward_ctl_f32(a, nullptr, stage, stream);
 }
@@ -797,6 +849,10 @@ int esmi_phoneme2mel_forward_ctl_f32(const esmi_forward_args* a, const esmi_pros
     return esmi_phoneme2mel_forward_prec_f32(a, ctl, 32, stage, stream);
 }
 int esmi_phoneme2mel_forward_prec_f32(const esmi_forward_args* a, const esmi_prosody_control* ctl, int precision, int stage, esmi_stream_t stream) {
+    const esmi_prosody_curves c = per_utterance(ctl);
+    return esmi_phoneme2mel_forward_curve_f32(a, ctl ? &c : nullptr, precision, stage, stream);
+}
+int esmi_phoneme2mel_forward_curve_f32(const esmi_forward_args* a, const esmi_prosody_curves* ctl, int precision, int stage, esmi_stream_t stream) {
     if (!a) return ESMI_ERR_ARG;
     if (stage == 1) precision = 32;   // (the encoder side has one arithmetic: stage 1 ignores the argument)
     if (precision != 0 && precision != 32 && precision != 16) return ESMI_ERR_ARG;
@@ -864,7 +920,7 @@ int encoder_side_one_launch(const esmi_forward_args* a, const esmi_encoder_block
 }
 }  // namespace
 
-static int forward_impl(const esmi_forward_args* a, const esmi_prosody_control* ctl, int precision, int stage, esmi_stream_t stream) {
+static int forward_impl(const esmi_forward_args* a, const esmi_prosody_curves* ctl, int precision, int stage, esmi_stream_t stream) {
     FwdArena o;
     int rc = fwd_arena(a, &o);
     if (rc) return rc;
@@ -886,7 +942,7 @@ static int forward_impl(const esmi_forward_args* a, const esmi_prosody_control* 
               a->pitch_idx ? a->pitch_idx : I(o.idx[0]), a->energy_idx ? a->energy_idx : I(o.idx[1]), a->dur ? a->dur : I(o.dur), cum,
               a->mel_len, nullptr, nullptr, plan, base + o.ws, esmi_fuse_variance_adaptor_workspace_bytes(B, T, a->dim, a->depth), stream,
               !a->pitch_pred && !a->energy_pred && !a->pitch_idx && !a->energy_idx,
-              (ctl && stage != 2) ? *ctl : esmi_prosody_control{}};   // (stage 2, the decoder alone, ignores the controls)
+              (ctl && stage != 2) ? *ctl : esmi_prosody_curves{}};   // (stage 2, the decoder alone, ignores the controls)
     // the decoder's first stage at phoneme rate: stage 1 produces h0, stage 2 reads it (a stage-2 call re-derives the same static test)
     const Head head = phoneme_rate_head(va, &a->head);
     const bool head_ok = head == Head::in_chain || (head == Head::gemm && a->head.dx2 == a->dec_shape.dx2);

@@ -106,6 +106,7 @@ struct VaTailP {
     float* feat;  // (rows, 4*dim): channels [dim,2dim) pitch emb, [2dim,3dim) energy emb
     int *pitch_idx, *energy_idx, *dur;
     const float *pitch_s, *energy_s, *dur_s;            // prosody controls: (B) scale of the prediction (never of a teacher value) or NULL = 1
+    int curve;                                          // kCurve* bits (va_decide.h): pitch_t / energy_t / dur_t holds a (rows) fp32 prosody curve instead
 };
 
 // networks.py:349-384 minus the convolutions: one thread per (row, channel)
@@ -117,11 +118,14 @@ static __global__ void va_tail_kernel(const VaTailP p) {   // one thread = (row,
     const bool pad = p.mask && p.mask[row];
     const int b = row / p.T;   // (a wave's rows may belong to two utterances here: the scales are per-lane loads of one or two addresses)
     const float sc_p = p.pitch_s ? p.pitch_s[b] : 1.0f, sc_e = p.energy_s ? p.energy_s[b] : 1.0f;
-    // (the rules of va_decide.h, called per side so that only the side's own value is loaded)
-    const int pi = bucketize_left(p.pitch_t ? va_bucket_input(true, p.pitch_t[row], 0.0f, 1.0f) : va_bucket_input(false, 0.0f, p.pitch_pred[row], sc_p),
-                                  p.pbins, p.dim - 1);
-    const int ei = bucketize_left(p.energy_t ? va_bucket_input(true, p.energy_t[row], 0.0f, 1.0f) : va_bucket_input(false, 0.0f, p.energy_pred[row], sc_e),
-                                  p.ebins, p.dim - 1);
+    // (the rules of va_decide.h, called per side so that only the side's own value is loaded; a curve's entry sits in the teacher slot)
+    auto bucket_input = [&](const float* tvp, const float* pred, float sc, bool cv) -> float {
+        if (!tvp) return va_bucket_input(false, 0.0f, pred[row], sc);
+        const float tv = tvp[row];
+        return cv ? va_bucket_input(false, 0.0f, pred[row], va_row_scale(true, tv, sc, pad)) : va_bucket_input(true, tv, 0.0f, 1.0f);
+    };
+    const int pi = bucketize_left(bucket_input(p.pitch_t, p.pitch_pred, sc_p, (p.curve & kCurvePitch) != 0), p.pbins, p.dim - 1);
+    const int ei = bucketize_left(bucket_input(p.energy_t, p.energy_pred, sc_e, (p.curve & kCurveEnergy) != 0), p.ebins, p.dim - 1);
     float* fr = p.feat + (long)row * 4 * p.dim;
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
     *reinterpret_cast<f32x4*>(fr + p.dim + c) = pad ? z : *reinterpret_cast<const f32x4*>(p.pemb + (long)pi * p.dim + c);
@@ -129,8 +133,14 @@ static __global__ void va_tail_kernel(const VaTailP p) {   // one thread = (row,
     if (c == 0) {
         if (p.pitch_idx) p.pitch_idx[row] = pi;
         if (p.energy_idx) p.energy_idx[row] = ei;
-        const float d = p.dur_t ? va_duration(true, (float)p.dur_t[row], 0.0f, 1.0f, p.mask, pad)
-                                : va_duration(false, 0.0f, p.dur_pred[row], p.dur_s ? p.dur_s[b] : 1.0f, p.mask, pad);
+        float d;
+        if (p.dur_t) {
+            const int tvd = p.dur_t[row];       // (a forced duration, or the curve's fp32 entry in the same slot)
+            d = (p.curve & kCurveDur) ? va_duration(false, 0.0f, p.dur_pred[row], va_row_scale(true, __builtin_bit_cast(float, tvd), 1.0f, pad), p.mask, pad)
+                                      : va_duration(true, (float)tvd, 0.0f, 1.0f, p.mask, pad);
+        } else {
+            d = va_duration(false, 0.0f, p.dur_pred[row], p.dur_s ? p.dur_s[b] : 1.0f, p.mask, pad);
+        }
         p.dur[row] = (int)d;  // FeatureUpsampler `.int()`, networks.py:234
     }
 }

@@ -1,17 +1,28 @@
 // The variance adaptor's discrete decisions (networks.py:349-384, 233-244), one definition each: which value is bucketized, how a
 // duration is rounded, masked and clamped, what the length regulator's scan sums, the LDS edge count, and the workgroup scan.
 // The kernels that decide -- enc_va16 (also enc_all16's tail), enc_va64, enc_pred128, enc_fuse_va, va_tail -- call these; which
-// kernel still spells which piece out, and why (its listing against the parent's), is in profiles/va_decide_refactor.md.
+// kernel still spells which piece out (enc_fuse_va: the bucket input and the duration, on va_row_scale's scale), and why (its listing against the parent's), is in profiles/va_decide_refactor.md.
 // Only __device__ __forceinline__ functions on values the caller already holds.
 #pragma once
 #include "esmi_dev.h"
 
 namespace esmi {
 
+// bits of the parameter structs' `curve` field (FuseVaP, Pred128P, VaTailP): the quantity's teacher pointer holds a (B, T) prosody curve
+constexpr int kCurvePitch = 1, kCurveEnergy = 2, kCurveDur = 4;
+
 // the value torch.bucketize sees: the teacher value on a row that has one, else the prediction times the utterance's prosody scale
 // (a teacher value is never scaled)
 __device__ __forceinline__ float va_bucket_input(bool teacher_row, float teacher, float pred, float scale) {
     return teacher_row ? teacher : pred * scale;
+}
+
+// the scale of a row's prediction: the utterance's (B) control, or -- `curve`, a wave-uniform bit of the parameter struct's `curve`
+// field -- the row's own entry of a (B, T) curve.  The curve's entry arrives in the row's teacher-value slot (the host points the
+// teacher resource at the curve: the two are mutually exclusive, so a curve costs no load of its own).  A padding row and a row past
+// the utterance's end take 1: whatever the curve holds there (NaN, 1e30) is never used.
+__device__ __forceinline__ float va_row_scale(bool curve, float row_val, float utt_scale, bool pad_or_out) {
+    return curve ? (pad_or_out ? 1.0f : row_val) : utt_scale;
 }
 
 // the fp32 duration that is stored as (int)dval: the forced duration, else torch.round (half to even) of the scaled prediction;

@@ -93,12 +93,15 @@ CONTROL_KEYS = ("pitch_control", "energy_control", "duration_control")
 
 
 def _prosody_controls(x, B, dev, train=False):
-    """The per-utterance prosody controls of an input dict (extension keys `pitch_control`, `energy_control`, `duration_control`;
-    the reference declares `control=1.` and never wires it, layers/networks.py:128-149) -> (`_lib.ProsodyControl` or None when no
-    key is present, the (B,) fp32 device tensors it points into -- keep them alive until the launch is enqueued).
+    """The prosody controls of an input dict (extension keys `pitch_control`, `energy_control`, `duration_control`; the reference
+    declares `control=1.` and never wires it, layers/networks.py:128-149) -> (the control struct or None when no key is present, the
+    fp32 device tensors it points into -- keep them alive until the launch is enqueued).  The struct is `_lib.ProsodyControl` while
+    every key is per utterance (the entry points and results of before, bit for bit) and `_lib.ProsodyCurves` once a key is a curve.
 
-    A value is a Python number (broadcast over the batch) or a tensor of shape (B,) or ().  The prediction that is bucketized
-    (pitch, energy) or rounded (duration) is multiplied by it inside the kernels; the returned predictions stay the raw ones.
+    A value is a Python number (broadcast over the batch), a tensor of shape (B,) or () -- one scale per utterance -- or a tensor
+    of shape (B, T): a per-phoneme curve (`prosody_curve` builds one from spans).  Each key chooses its form on its own.  The
+    prediction that is bucketized (pitch, energy) or rounded (duration) is multiplied by it inside the kernels; the returned
+    predictions stay the raw ones.  A curve's entries at padding positions are never used (the scale there is 1).
     Numbers are validated here (finite; `duration_control >= 0`).  Tensors are NOT: reading a device tensor would cost a host
     synchronisation per forward, so a non-finite or negative entry is the caller's responsibility (a negative duration scale
     yields zero frames for that utterance).  ValueError: a control while training, `duration_control` together with
@@ -112,7 +115,9 @@ def _prosody_controls(x, B, dev, train=False):
         raise ValueError(f"{given[0]}: the prosody controls are an inference extension (train=True takes teacher values)")
     if "duration_control" in given and x.get("duration_forced") is not None:
         raise ValueError("duration_control together with duration_forced: a forced duration is final and is never scaled")
-    ctl, keep = _lib.ProsodyControl(), []
+    T = int(x["phoneme"].shape[1])
+    curves = [k for k in given if torch.is_tensor(x[k]) and x[k].dim() == 2 and tuple(x[k].shape) == (B, T)]
+    ctl, keep = (_lib.ProsodyCurves() if curves else _lib.ProsodyControl()), []
     for k in given:
         v = x[k]
         if isinstance(v, numbers.Real):
@@ -121,14 +126,40 @@ def _prosody_controls(x, B, dev, train=False):
                 raise ValueError(f"{k} = {v}: must be finite" + (" and >= 0" if k == "duration_control" else ""))
             t = torch.full((B,), v, dtype=torch.float32, device=dev)
         elif torch.is_tensor(v):
-            if tuple(v.shape) not in ((B,), ()):
-                raise ValueError(f"{k}: shape {tuple(v.shape)}, expected ({B},) (one scale per utterance) or ()")
-            t = v.detach().to(device=dev, dtype=torch.float32).expand(B).contiguous()
+            if k in curves:
+                t = v.detach().to(device=dev, dtype=torch.float32).contiguous()
+                setattr(ctl, k.replace("control", "per_phoneme"), 1)
+            elif tuple(v.shape) not in ((B,), ()):
+                raise ValueError(f"{k}: shape {tuple(v.shape)}, expected ({B},) (one scale per utterance), () or "
+                                 f"({B}, {T}) (a per-phoneme curve)")
+            else:
+                t = v.detach().to(device=dev, dtype=torch.float32).expand(B).contiguous()
         else:
-            raise ValueError(f"{k}: a number or a tensor of shape ({B},) or (), not {type(v).__name__}")
+            raise ValueError(f"{k}: a number or a tensor of shape ({B},), () or ({B}, {T}), not {type(v).__name__}")
         keep.append(t)
         setattr(ctl, k.replace("control", "scale"), _ptr(t))
     return ctl, tuple(keep)
+
+
+def prosody_curve(lengths_or_shape, spans, default=1.0):
+    """A (B, T) fp32 prosody curve (host tensor) for `pitch_control` / `energy_control` / `duration_control`, built from spans so that
+    a caller can mark a word range without index code.  `lengths_or_shape`: a (B, T) tuple, or the utterances' lengths (a list or
+    1-D array / tensor: B of them, T = the longest).  `spans`: (b, start, stop, value) each -- phonemes start .. stop - 1 of utterance
+    b get `value`; `stop` beyond T is clipped (None: to the end), later spans win where they overlap, `default` holds elsewhere."""
+    import numbers
+    if isinstance(lengths_or_shape, tuple) and len(lengths_or_shape) == 2 and all(isinstance(n, numbers.Integral) for n in lengths_or_shape):
+        B, T = (int(n) for n in lengths_or_shape)
+    else:
+        lens = [int(n) for n in (lengths_or_shape.tolist() if hasattr(lengths_or_shape, "tolist") else lengths_or_shape)]
+        B, T = len(lens), max(lens, default=0)
+    curve = torch.full((B, T), float(default), dtype=torch.float32)
+    for b, start, stop, value in spans:
+        if not 0 <= int(b) < B:
+            raise ValueError(f"prosody_curve: span utterance {b} outside the batch of {B}")
+        if int(start) < 0 or (stop is not None and int(stop) < int(start)):
+            raise ValueError(f"prosody_curve: span ({start}, {stop}) of utterance {b}: expected 0 <= start <= stop")
+        curve[int(b), int(start):T if stop is None else min(int(stop), T)] = float(value)
+    return curve
 
 
 def get_mask_from_lengths(lengths, max_len=None):
@@ -736,7 +767,8 @@ class PhonemeEncoder(_PackedModule):
     def _encode(self, x, train=False, need_lmax=True, head=None):
         """Everything up to (and including) the duration scan; nothing frame-rate is materialised.
         Inference extension keys: `duration_forced`, and the per-utterance prosody controls `pitch_control`, `energy_control`,
-        `duration_control` (numbers are validated on the host, device tensors are not synchronised for it: `_prosody_controls`)."""
+        `duration_control`, each per utterance or a (B, T) per-phoneme curve (numbers are validated on the host, device tensors are not
+        synchronised for it: `_prosody_controls`)."""
         phoneme = x["phoneme"]
         B = phoneme.shape[0]
         ctl, _ctl_keep = _prosody_controls(x, B, self.encoder.embed.weight.device, train)   # (_ctl_keep: alive until the launches are enqueued)
@@ -777,9 +809,11 @@ class PhonemeEncoder(_PackedModule):
                 _ptr(idxs[0]), _ptr(idxs[1]), _ptr(dur), _ptr(cum), _ptr(mel_len))
         plan = _lib.current_plan()
 
-        def stage(head_p, h0_p):              # (with controls: the _ctl entry point, same arguments + the scales)
+        def stage(head_p, h0_p):              # (with controls: the _ctl / _curve entry point, same arguments + the scales)
             if ctl is None:
                 lib.esmi_fuse_variance_adaptor_f32(*args, head_p, h0_p, plan, _ptr(ws), ws_bytes, stream)
+            elif isinstance(ctl, _lib.ProsodyCurves):
+                lib.esmi_fuse_variance_adaptor_curve_f32(*args, head_p, h0_p, plan, _ptr(ws), ws_bytes, stream, C.byref(ctl))
             else:
                 lib.esmi_fuse_variance_adaptor_ctl_f32(*args, head_p, h0_p, plan, _ptr(ws), ws_bytes, stream, C.byref(ctl))
         if h0 is not None:
@@ -935,7 +969,7 @@ class Phoneme2Mel(nn.Module):
         Inference extension keys of x: `duration_forced`, `max_mel_len` (`max_mel_len_exact`), `decoder_precision` (16 or 32, validated on
         the host: the mel decoder's arithmetic for this call, overriding `self.decoder.precision`; the encoder side is untouched by it, so
         mel_len and the durations are the same bits either way -- include/esmi.h), and the per-utterance prosody controls
-        `pitch_control`, `energy_control`, `duration_control` (a number or a (B,) / () tensor each; numbers are validated on the host,
+        `pitch_control`, `energy_control`, `duration_control` (a number, a (B,) / () tensor or a (B, T) per-phoneme curve each; numbers are validated on the host,
         device tensors are not synchronised for it: `_prosody_controls`).
         taps (tests): also return what `PhonemeEncoder._encode` exposes -- `state.taps` = pitch, energy (B,T) raw predictions,
         pitch_idx, energy_idx, dur, cum (B,T) int32."""
@@ -988,8 +1022,10 @@ class Phoneme2Mel(nn.Module):
         a.range_flag = _ptr(rf)
         dec = self.decoder
 
-        def forward(stage_):                   # (with controls: the _ctl entry point; stage 2 ignores them)
-            if st.prec_entry and stage_ != 1:   # (a precision was asked for -- 32 included: the _prec entry point; stage 1 has one arithmetic)
+        def forward(stage_):                   # (with controls: the _ctl / _curve entry point; stage 2 ignores them)
+            if isinstance(st.ctl, _lib.ProsodyCurves):   # (a per-phoneme curve: the entry point that takes them carries the precision too)
+                lib.esmi_phoneme2mel_forward_curve_f32(C.byref(a), C.byref(st.ctl), st.precision if st.prec_entry else 32, stage_, stream)
+            elif st.prec_entry and stage_ != 1:   # (a precision was asked for -- 32 included: the _prec entry point; stage 1 has one arithmetic)
                 lib.esmi_phoneme2mel_forward_prec_f32(C.byref(a), None if st.ctl is None else C.byref(st.ctl), st.precision, stage_, stream)
             elif st.ctl is None:
                 lib.esmi_phoneme2mel_forward_f32(C.byref(a), stage_, stream)

@@ -46,20 +46,48 @@ class BucketedSynthesizer:
         slots = sum(len(idx) * T for idx, T in batches)
         return 1.0 - float(lengths.sum()) / max(slots, 1)
 
+    @staticmethod
+    def _batch_control(v, idx, lengths, T):
+        """One key's control of a batch: (B,) when every request of the batch carries a number, else the (B, T) curve -- each request's
+        curve (or its number over its row) in the batch's order, 1.0 behind its end."""
+        if isinstance(v, np.ndarray):
+            return torch.from_numpy(v[idx])
+        if all(v[i].ndim == 0 for i in idx):
+            return torch.from_numpy(np.array([v[i] for i in idx], np.float32))
+        curve = np.ones((len(idx), T), np.float32)
+        for r, i in enumerate(idx):
+            curve[r, :lengths[i]] = v[i]
+        return torch.from_numpy(curve)
+
     @torch.no_grad()
     def __call__(self, sequences, extra=None, controls=None):
         """sequences: list of 1-D integer phoneme id sequences.  -> list (request order) of (mel (L_i, n_mel), duration (T_i,)), or
         with a vocoder of (wav (L_i * hop,), mel (L_i, n_mel), duration (T_i,)).
         `extra(indices, T)` may return additional input-dict entries for a batch (e.g. forced durations).
         `controls`: per-REQUEST prosody scales, a dict with any of `pitch_control`, `energy_control`, `duration_control`, each an array
-        of len(sequences) numbers; every batch gets its requests' entries (unrelated requests share a batch, each keeps its own scale)."""
+        of len(sequences) numbers; every batch gets its requests' entries (unrelated requests share a batch, each keeps its own scale).
+        A request's entry may instead be a per-phoneme curve: a 1-D array of that request's own length (then pass a list, one entry per
+        request).  A batch that holds a curve for a key gets a (B, T) tensor for it -- the requests' curves gathered in batch order,
+        a number filling its request's row, 1.0 behind each request's end; a batch of numbers only keeps the (B,) form."""
         dev = self.net.decoder.mel_linear.weight.device
         lengths = [int(len(s)) for s in sequences]
         controls = dict(controls or {})
         for k, v in controls.items():
             if k not in CONTROL_KEYS:
                 raise ValueError(f"controls: unknown key {k!r} (one of {', '.join(CONTROL_KEYS)})")
-            controls[k] = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=np.float32)
+            if torch.is_tensor(v):
+                v = v.detach().cpu().numpy()
+            if isinstance(v, (list, tuple)) and any(np.ndim(e.detach().cpu() if torch.is_tensor(e) else e) > 0 for e in v):
+                if len(v) != len(sequences):
+                    raise ValueError(f"controls[{k!r}]: {len(v)} entries, expected one per request ({len(sequences)})")
+                per = [np.asarray(e.detach().cpu() if torch.is_tensor(e) else e, dtype=np.float32) for e in v]
+                for i, e in enumerate(per):
+                    if e.ndim > 0 and e.shape != (lengths[i],):
+                        raise ValueError(f"controls[{k!r}][{i}]: shape {e.shape}, expected a number or a curve of the request's length "
+                                         f"({lengths[i]},)")
+                controls[k] = per
+                continue
+            controls[k] = np.asarray(v, dtype=np.float32)
             if controls[k].shape != (len(sequences),):
                 raise ValueError(f"controls[{k!r}]: shape {controls[k].shape}, expected one scale per request ({len(sequences)},)")
         out = [None] * len(sequences)
@@ -73,7 +101,7 @@ class BucketedSynthesizer:
             if extra is not None:
                 x.update(extra(idx, T))
             for k, v in controls.items():                      # this batch's requests, in the batch's order
-                x[k] = torch.from_numpy(v[idx]).to(dev)
+                x[k] = self._batch_control(v, idx, lengths, T).to(dev)
             mel, mel_len, dur = self.net(x)
             wav = None
             if self.vocoder is not None and mel.shape[1] > 0:      # (launched before the lengths are read back)

@@ -42,7 +42,8 @@ def shard_batch(x, rank, world):
     copies only cost their compute: they are duplicates of real utterances, so they cannot change the batch's padded length, and
     `unpad_gathered` drops their rows (they sit behind the B real ones in the gathered tensors).
     The per-utterance prosody controls (`networks.CONTROL_KEYS`) given as (B,) tensors are batch-leading tensors like any other: each
-    rank gets its utterances' scales; a number or a () tensor holds for the whole batch and travels unchanged."""
+    rank gets its utterances' scales; a number or a () tensor holds for the whole batch and travels unchanged.  A (B, T) per-phoneme curve
+    is batch-leading too: its rows travel with their utterances, and a padding copy of an utterance copies its row."""
     B = x["phoneme"].shape[0]
     lo, hi, per = shard_rows(B, rank, world)
     out = {}

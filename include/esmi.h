@@ -34,7 +34,7 @@ extern "C" {
 
 #define ESMI_VERSION 501 /* 0.5.1: esmi_train_conv_ln_fwd_f32, then esmi_hifigan_generator_ragged_f32, then esmi_prosody_control and the three
                             *_ctl_f32 entry points, then esmi_hifigan_generator_prec_f32, then esmi_mel_decoder_prec_f32 and
-                            esmi_phoneme2mel_forward_prec_f32 (additions; nothing else changed shape).  0.5.0 (round 5): esmi_mel_decoder_clock_probe;
+                            esmi_phoneme2mel_forward_prec_f32, then esmi_prosody_curves and the three *_curve_f32 entry points (additions; nothing else changed shape).  0.5.0 (round 5): esmi_mel_decoder_clock_probe;
                             0.4.0: esmi_decoder_head.proj_w (the decoder's first stage at phoneme rate for every model size:
                           * esmi_decoder_head_f32).  0.3.0: training entry points changed shape (esmi_conv_desc: act / packed_fwd / packed_grad; LayerNorm with
                           * residual / row mask / activation arguments; esmi_train_loss_args.grad_seed; esmi_train_pack_weights_f32,
@@ -268,6 +268,35 @@ int esmi_variance_adaptor_ctl_f32(const esmi_predictor_weights* pitch, const esm
                                   int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur,
                                   void* workspace, size_t workspace_bytes, esmi_stream_t stream, const esmi_prosody_control* ctl);
 
+/* Per-PHONEME prosody curves (extension): the same rule at a finer grain -- stress one word, slow one phrase, raise the pitch at the end
+ * of a question.  The reference's hook `pred = pred * control` (layers/networks.py:128-149) broadcasts, so a (B, T) control is the same
+ * multiply per row.  Each quantity chooses its form independently: NULL (none), a (B) array (`*_per_phoneme` == 0: exactly
+ * esmi_prosody_control, bit for bit), or a (B, T) fp32 device array (`*_per_phoneme` != 0).  For a live phoneme (b, t) of a curve:
+ *   pitch / energy: the value that is bucketized is pred[b,t] * curve[b,t] -- one fp32 multiply of the fp32 prediction, in the prediction
+ *                   branch only; a teacher value is never scaled;
+ *   duration:       d = rintf(duration_pred[b,t] * curve[b,t]), then the same masked_fill(mask, 0).clamp(min=0) (networks.py:381-382); the
+ *                   scan, cum and mel_len follow from d.
+ * The predictions that are RETURNED stay the raw ones.  Positions under the mask never use their entry: the scale there is 1, so whatever
+ * the curve holds at a padding position (NaN, 1e30) changes nothing (the pitch / energy index stored for a padding position is that of
+ * the raw prediction).  A curve of 1.0f gives results bit-identical to the call without controls; a curve constant per utterance gives
+ * the decisions at every live phoneme, cum, mel_len and the mel of the (B) control of that value, bit for bit.
+ * A curve together with the teacher / forced pointer of the same quantity is a caller error: ESMI_ERR_ARG, nothing launched (the kernels
+ * read the curve through the row's teacher-value slot, so the two cannot coexist; it costs no load of its own).  Curves are read on the
+ * device and not validated: a NaN product takes bucket 0 (the project's rule, as for any NaN), a negative duration product gives 0
+ * frames (the clamp, or the scan's max(d, 0) on the B == 1 path). */
+typedef struct esmi_prosody_curves {
+    const float* pitch_scale; const float* energy_scale; const float* duration_scale;   /* device fp32 or NULL = 1                 */
+    int32_t pitch_per_phoneme; int32_t energy_per_phoneme; int32_t duration_per_phoneme; /* 0: that pointer is (B); else (B, T)    */
+} esmi_prosody_curves;
+/* esmi_variance_adaptor_f32 with curves or per-utterance scales (ctl == NULL: exactly that call; all *_per_phoneme == 0: exactly the
+ * _ctl call) */
+int esmi_variance_adaptor_curve_f32(const esmi_predictor_weights* pitch, const esmi_predictor_weights* energy,
+                                    const esmi_predictor_weights* duration, int dim, int B, int T, const uint8_t* mask,
+                                    const float* pitch_target, const float* energy_target, const int32_t* duration_target,
+                                    float* feat, float* pitch_pred, float* energy_pred, float* duration_pred,
+                                    int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur,
+                                    void* workspace, size_t workspace_bytes, esmi_stream_t stream, const esmi_prosody_curves* ctl);
+
 /* Fuse + variance adaptor in ONE call (what PhonemeEncoder.forward does between the encoder and the length
  * regulator, networks.py:347-384); uses a single fused kernel when the shape allows (dim 32 or 64), else the two
  * calls above.  `feat` (B,T,4*dim) is fully written.  Arguments as in esmi_fuse_f32 / esmi_variance_adaptor_f32.
@@ -316,6 +345,17 @@ int esmi_fuse_variance_adaptor_ctl_f32(const esmi_fuse_weights* fuse, int depth,
                                        int32_t* cum, int32_t* mel_len, const esmi_decoder_head* head, float* h0, int plan,
                                        void* workspace, size_t workspace_bytes, esmi_stream_t stream,
                                        const esmi_prosody_control* ctl);
+/* ... with per-phoneme curves or per-utterance scales (esmi_prosody_curves above): whichever kernel serves the shape applies them.
+ * ctl == NULL: exactly esmi_fuse_variance_adaptor_f32. */
+int esmi_fuse_variance_adaptor_curve_f32(const esmi_fuse_weights* fuse, int depth, int dim, int kernel, int B, int T,
+                                         const float* const* feats, const int* n_i, const esmi_predictor_weights* pitch,
+                                         const esmi_predictor_weights* energy, const esmi_predictor_weights* duration,
+                                         const uint8_t* mask, const float* pitch_target, const float* energy_target,
+                                         const int32_t* duration_target, float* feat, float* pitch_pred, float* energy_pred,
+                                         float* duration_pred, int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur,
+                                         int32_t* cum, int32_t* mel_len, const esmi_decoder_head* head, float* h0, int plan,
+                                         void* workspace, size_t workspace_bytes, esmi_stream_t stream,
+                                         const esmi_prosody_curves* ctl);
 
 /* ------------------------------------------------------------------ module-level forwards
  * The reference's sub-modules called on their own (one kernel per reference op, fp32 MFMA):
@@ -509,6 +549,11 @@ int esmi_mel_decoder_prec_f32(const float* blob, const esmi_decoder_shape* s, co
  * side included. */
 int esmi_phoneme2mel_forward_prec_f32(const esmi_forward_args* a, const esmi_prosody_control* ctl, int precision, int stage,
                                       esmi_stream_t stream);
+/* ... with per-phoneme curves or per-utterance scales (esmi_prosody_curves): `precision` and `stage` as in the _prec call, which is this
+ * call with every *_per_phoneme == 0.  A duration curve or scale together with a->dur_forced is ESMI_ERR_ARG (nothing launched).  Stage 2
+ * ignores ctl. */
+int esmi_phoneme2mel_forward_curve_f32(const esmi_forward_args* a, const esmi_prosody_curves* ctl, int precision, int stage,
+                                       esmi_stream_t stream);
 
 /* ------------------------------------------------------------------ HiFi-GAN generator (the vocoder behind model.py:161-162)
  * hifigan/models.py:84-135 Generator.forward with ResBlock1 (:20-58) or ResBlock2 (:61-82), weights as after
