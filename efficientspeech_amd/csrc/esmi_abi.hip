@@ -34,6 +34,34 @@ EncWs enc_ws(const esmi_encoder_block_shape* s) {
     return w;
 }
 
+// ---- the prosody controls (include/esmi.h esmi_prosody_control / esmi_prosody_curves)
+// a prosody scale or curve next to the teacher / forced values of the same quantity: the caller asked for two things at once
+bool ctl_conflict(const esmi_prosody_curves* ctl, const void* pitch_t, const void* energy_t, const void* dur_t) {
+    return ctl && ((ctl->pitch_scale && pitch_t) || (ctl->energy_scale && energy_t) || (ctl->duration_scale && dur_t));
+}
+// the per-utterance struct as the general one: every pointer is (B).  A temporary of it lives to the end of the forwarding statement
+struct PerUtterance {
+    esmi_prosody_curves c{};
+    explicit PerUtterance(const esmi_prosody_control* ctl) {
+        if (ctl) { c.pitch_scale = ctl->pitch_scale; c.energy_scale = ctl->energy_scale; c.duration_scale = ctl->duration_scale; }
+    }
+    const esmi_prosody_curves* curves() const { return &c; }
+};
+// What the deciding kernels get (enc_params.h FuseVaP::curve, va_decide.h va_row_scale), written into their parameters: P is FuseVaP,
+// Pred128P or VaTailP, which name these seven fields alike.  A (B, T) curve and the teacher / forced array of its quantity are mutually
+// exclusive (ctl_conflict), and every kernel loads that array's entry per row anyway: the curve takes the array's place, its kCurve* bit
+// says so, and the quantity's (B) scale is absent.
+template <class P>
+void set_va_controls(P* p, const esmi_prosody_curves& c, const float* pitch_t, const float* energy_t, const int32_t* dur_t) {
+    p->pitch_t = pitch_t; p->energy_t = energy_t; p->dur_t = dur_t;
+    p->pitch_s = c.pitch_scale; p->energy_s = c.energy_scale; p->dur_s = c.duration_scale; p->curve = 0;
+    if (c.pitch_scale && c.pitch_per_phoneme) { p->pitch_t = c.pitch_scale; p->pitch_s = nullptr; p->curve |= kCurvePitch; }
+    if (c.energy_scale && c.energy_per_phoneme) { p->energy_t = c.energy_scale; p->energy_s = nullptr; p->curve |= kCurveEnergy; }
+    if (c.duration_scale && c.duration_per_phoneme) {
+        p->dur_t = reinterpret_cast<const int32_t*>(c.duration_scale); p->dur_s = nullptr; p->curve |= kCurveDur;
+    }
+}
+
 }  // namespace
 
 #ifdef ESMI_CHAIN_TRACE   // development: tools/trace_chain.py
@@ -369,43 +397,14 @@ int esmi_fuse_f32(const esmi_fuse_weights* w, int depth, int dim, int kernel, in
 
 size_t esmi_variance_adaptor_workspace_bytes(int B, int T, int dim) { return align256((size_t)B * T * dim * 4); }
 
-// a prosody scale or curve next to the teacher / forced values of the same quantity: the caller asked for two things at once
-static bool ctl_conflict(const esmi_prosody_curves* ctl, const void* pitch_t, const void* energy_t, const void* dur_t) {
-    return ctl && ((ctl->pitch_scale && pitch_t) || (ctl->energy_scale && energy_t) || (ctl->duration_scale && dur_t));
-}
-// the per-utterance struct as the general one: every pointer is (B)
-static esmi_prosody_curves per_utterance(const esmi_prosody_control* ctl) {
-    esmi_prosody_curves c{};
-    if (ctl) { c.pitch_scale = ctl->pitch_scale; c.energy_scale = ctl->energy_scale; c.duration_scale = ctl->duration_scale; }
-    return c;
-}
-// What the deciding kernels get (enc_params.h FuseVaP::curve, va_decide.h va_row_scale).  A (B, T) curve and the teacher / forced array of
-// its quantity are mutually exclusive (ctl_conflict), and every kernel loads that array's entry per row anyway: the curve takes the
-// array's place, its kCurve* bit says so, and the quantity's (B) scale is absent.
-struct VaControls {
-    const float *pitch_t, *energy_t;
-    const int32_t* dur_t;
-    const float *pitch_s, *energy_s, *dur_s;
-    int curve;
-};
-static VaControls va_controls(const esmi_prosody_curves& c, const float* pitch_t, const float* energy_t, const int32_t* dur_t) {
-    VaControls v{pitch_t, energy_t, dur_t, c.pitch_scale, c.energy_scale, c.duration_scale, 0};
-    if (c.pitch_scale && c.pitch_per_phoneme) { v.pitch_t = c.pitch_scale; v.pitch_s = nullptr; v.curve |= kCurvePitch; }
-    if (c.energy_scale && c.energy_per_phoneme) { v.energy_t = c.energy_scale; v.energy_s = nullptr; v.curve |= kCurveEnergy; }
-    if (c.duration_scale && c.duration_per_phoneme) {
-        v.dur_t = reinterpret_cast<const int32_t*>(c.duration_scale); v.dur_s = nullptr; v.curve |= kCurveDur;
-    }
-    return v;
-}
-
 int esmi_variance_adaptor_f32(const esmi_predictor_weights* pitch, const esmi_predictor_weights* energy,
                               const esmi_predictor_weights* duration, int dim, int B, int T, const uint8_t* mask,
                               const float* pitch_target, const float* energy_target, const int32_t* duration_target,
                               float* feat, float* pitch_pred, float* energy_pred, float* duration_pred,
                               int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur, void* workspace,
                               size_t workspace_bytes, esmi_stream_t stream) {
-    return esmi_variance_adaptor_ctl_f32(pitch, energy, duration, dim, B, T, mask, pitch_target, energy_target, duration_target, feat, pitch_pred,
-                                         energy_pred, duration_pred, pitch_idx, energy_idx, dur, workspace, workspace_bytes, stream, nullptr);
+    return esmi_variance_adaptor_curve_f32(pitch, energy, duration, dim, B, T, mask, pitch_target, energy_target, duration_target, feat, pitch_pred,
+                                           energy_pred, duration_pred, pitch_idx, energy_idx, dur, workspace, workspace_bytes, stream, nullptr);
 }
 
 int esmi_variance_adaptor_ctl_f32(const esmi_predictor_weights* pitch, const esmi_predictor_weights* energy,
@@ -414,9 +413,9 @@ int esmi_variance_adaptor_ctl_f32(const esmi_predictor_weights* pitch, const esm
                                   float* feat, float* pitch_pred, float* energy_pred, float* duration_pred,
                                   int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur, void* workspace,
                                   size_t workspace_bytes, esmi_stream_t stream, const esmi_prosody_control* ctl) {
-    const esmi_prosody_curves c = per_utterance(ctl);
     return esmi_variance_adaptor_curve_f32(pitch, energy, duration, dim, B, T, mask, pitch_target, energy_target, duration_target, feat, pitch_pred,
-                                           energy_pred, duration_pred, pitch_idx, energy_idx, dur, workspace, workspace_bytes, stream, &c);
+                                           energy_pred, duration_pred, pitch_idx, energy_idx, dur, workspace, workspace_bytes, stream,
+                                           PerUtterance(ctl).curves());
 }
 
 int esmi_variance_adaptor_curve_f32(const esmi_predictor_weights* pitch, const esmi_predictor_weights* energy,
@@ -439,9 +438,7 @@ int esmi_variance_adaptor_curve_f32(const esmi_predictor_weights* pitch, const e
     VaTailP v;
     v.rows = B * T; v.T = T; v.dim = dim; v.mask = mask;
     v.pitch_pred = pitch_pred; v.energy_pred = energy_pred; v.dur_pred = duration_pred;
-    const VaControls vc = va_controls(ctl ? *ctl : esmi_prosody_curves{}, pitch_target, energy_target, duration_target);
-    v.pitch_t = vc.pitch_t; v.energy_t = vc.energy_t; v.dur_t = vc.dur_t;
-    v.pitch_s = vc.pitch_s; v.energy_s = vc.energy_s; v.dur_s = vc.dur_s; v.curve = vc.curve;
+    set_va_controls(&v, ctl ? *ctl : esmi_prosody_curves{}, pitch_target, energy_target, duration_target);
     v.pbins = pitch->bins; v.ebins = energy->bins; v.pemb = pitch->emb; v.eemb = energy->emb;
     v.feat = feat; v.pitch_idx = pitch_idx; v.energy_idx = energy_idx; v.dur = dur;
     if (!v.pbins || !v.ebins || !v.pemb || !v.eemb) return ESMI_ERR_ARG;
@@ -532,9 +529,7 @@ void pred_weights(const VaArgs& a, PredW* out) {
 FuseVaP va_chain_params(const VaArgs& a, bool head_in_chain, int* nw) {
     FuseVaP p = fuse_params(a);
     pred_weights(a, p.pred);
-    const VaControls vc = va_controls(a.ctl, a.pitch_t, a.energy_t, a.dur_t);
-    p.pitch_t = vc.pitch_t; p.energy_t = vc.energy_t; p.dur_t = vc.dur_t;
-    p.pitch_s = vc.pitch_s; p.energy_s = vc.energy_s; p.dur_s = vc.dur_s; p.curve = vc.curve;
+    set_va_controls(&p, a.ctl, a.pitch_t, a.energy_t, a.dur_t);
     for (int q = 0; q < 3; ++q) p.preds[q] = a.preds[q];
     p.pitch_idx = a.pitch_idx; p.energy_idx = a.energy_idx; p.dur = a.dur;
     fuse_va_plan(a.T, a.dim, a.depth, nw, &p.wgs_per_b, &p.useful, &p.halo);
@@ -609,9 +604,9 @@ int fuse_variance_adaptor(const VaArgs& a) {
         };
         auto predictors = [&]() -> int {
             if (chain16 && a.dim == 128 && pred128_weights_ok(a)) {
-                const VaControls vc = va_controls(a.ctl, a.pitch_t, a.energy_t, a.dur_t);
-                Pred128P q{{}, a.mask, vc.pitch_t, vc.energy_t, vc.dur_t, a.feat, {a.preds[0], a.preds[1], a.preds[2]}, a.pitch_idx, a.energy_idx,
-                           a.dur, a.cum, a.mel_len, a.B, a.T, vc.pitch_s, vc.energy_s, vc.dur_s, vc.curve};
+                Pred128P q{{}, a.mask, nullptr, nullptr, nullptr, a.feat, {a.preds[0], a.preds[1], a.preds[2]}, a.pitch_idx, a.energy_idx,
+                           a.dur, a.cum, a.mel_len, a.B, a.T};
+                set_va_controls(&q, a.ctl, a.pitch_t, a.energy_t, a.dur_t);
                 pred_weights(a, q.pred);
                 ESMI_TRY(true, launch_enc_pred128(q, a.dim, st))
             }
@@ -638,9 +633,9 @@ int esmi_fuse_variance_adaptor_f32(const esmi_fuse_weights* fw, int depth, int d
                                    float* duration_pred, int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur,
                                    int32_t* cum, int32_t* mel_len, const esmi_decoder_head* head, float* h0, int plan,
                                    void* workspace, size_t workspace_bytes, esmi_stream_t stream) {
-    return esmi_fuse_variance_adaptor_ctl_f32(fw, depth, dim, kernel, B, T, feats, n_i, pitch, energy, duration, mask, pitch_target, energy_target,
-                                              duration_target, feat, pitch_pred, energy_pred, duration_pred, pitch_idx, energy_idx, dur, cum,
-                                              mel_len, head, h0, plan, workspace, workspace_bytes, stream, nullptr);
+    return esmi_fuse_variance_adaptor_curve_f32(fw, depth, dim, kernel, B, T, feats, n_i, pitch, energy, duration, mask, pitch_target, energy_target,
+                                                duration_target, feat, pitch_pred, energy_pred, duration_pred, pitch_idx, energy_idx, dur, cum,
+                                                mel_len, head, h0, plan, workspace, workspace_bytes, stream, nullptr);
 }
 
 int esmi_fuse_variance_adaptor_ctl_f32(const esmi_fuse_weights* fw, int depth, int dim, int kernel, int B, int T,
@@ -651,10 +646,9 @@ int esmi_fuse_variance_adaptor_ctl_f32(const esmi_fuse_weights* fw, int depth, i
                                        float* duration_pred, int32_t* pitch_idx, int32_t* energy_idx, int32_t* dur,
                                        int32_t* cum, int32_t* mel_len, const esmi_decoder_head* head, float* h0, int plan,
                                        void* workspace, size_t workspace_bytes, esmi_stream_t stream, const esmi_prosody_control* ctl) {
-    const esmi_prosody_curves c = per_utterance(ctl);
     return esmi_fuse_variance_adaptor_curve_f32(fw, depth, dim, kernel, B, T, feats, n_i, pitch, energy, duration, mask, pitch_target, energy_target,
                                                 duration_target, feat, pitch_pred, energy_pred, duration_pred, pitch_idx, energy_idx, dur, cum,
-                                                mel_len, head, h0, plan, workspace, workspace_bytes, stream, &c);
+                                                mel_len, head, h0, plan, workspace, workspace_bytes, stream, PerUtterance(ctl).curves());
 }
 
 int esmi_fuse_variance_adaptor_curve_f32(const esmi_fuse_weights* fw, int depth, int dim, int kernel, int B, int T,
@@ -843,17 +837,17 @@ size_t esmi_forward_arena_bytes(const esmi_forward_args* a) {
 
 static int forward_impl(const esmi_forward_args* a, const esmi_prosody_curves* ctl, int precision, int stage, esmi_stream_t stream);
 int esmi_phoneme2mel_forward_f32(const esmi_forward_args* a, int stage, esmi_stream_t stream) {
-    return esmi_phoneme2mel_forward_ctl_f32(a, nullptr, stage, stream);
+    return esmi_phoneme2mel_forward_curve_f32(a, nullptr, 32, stage, stream);
 }
 int esmi_phoneme2mel_forward_ctl_f32(const esmi_forward_args* a, const esmi_prosody_control* ctl, int stage, esmi_stream_t stream) {
-    return esmi_phoneme2mel_forward_prec_f32(a, ctl, 32, stage, stream);
+    return esmi_phoneme2mel_forward_curve_f32(a, PerUtterance(ctl).curves(), 32, stage, stream);
 }
 int esmi_phoneme2mel_forward_prec_f32(const esmi_forward_args* a, const esmi_prosody_control* ctl, int precision, int stage, esmi_stream_t stream) {
-    const esmi_prosody_curves c = per_utterance(ctl);
-    return esmi_phoneme2mel_forward_curve_f32(a, ctl ? &c : nullptr, precision, stage, stream);
+    return esmi_phoneme2mel_forward_curve_f32(a, PerUtterance(ctl).curves(), precision, stage, stream);
 }
 int esmi_phoneme2mel_forward_curve_f32(const esmi_forward_args* a, const esmi_prosody_curves* ctl, int precision, int stage, esmi_stream_t stream) {
     if (!a) return ESMI_ERR_ARG;
+    // the precision argument of every form of this call is judged here, before the encoder side is enqueued
     if (stage == 1) precision = 32;   // (the encoder side has one arithmetic: stage 1 ignores the argument)
     if (precision != 0 && precision != 32 && precision != 16) return ESMI_ERR_ARG;
 #if ESMI_DEC_SPLIT != 2

@@ -172,7 +172,7 @@ size_t esmi_mel_decoder_workspace_bytes(const esmi_decoder_shape* s, int B, int 
     return (size_t)n_seg * B * stream_ws_stride(s) * sizeof(float);   // one row set per (segment, utterance)
 }
 
-static int mel_decoder_launch(const float* blob, const esmi_decoder_shape* s, const float* x, const float* h0,
+int esmi_mel_decoder_prec_f32(const float* blob, const esmi_decoder_shape* s, const float* x, const float* h0,
                               const int32_t* cum, const int32_t* mel_len, const int32_t* lmax_dev, int lmax_host, int apply_mask, int B, int T,
                               int L_out, float* mel, void* workspace, size_t workspace_bytes, int precision, esmi_stream_t stream) {
     // precision (include/esmi.h): 0 / 32 the fp32-accurate kernel; 16 one binary16 product per contraction; refused before anything else
@@ -224,13 +224,7 @@ static int mel_decoder_launch(const float* blob, const esmi_decoder_shape* s, co
 int esmi_mel_decoder_f32(const float* blob, const esmi_decoder_shape* s, const float* x, const float* h0,
                          const int32_t* cum, const int32_t* mel_len, const int32_t* lmax_dev, int lmax_host, int apply_mask, int B, int T,
                          int L_out, float* mel, void* workspace, size_t workspace_bytes, esmi_stream_t stream) {
-    return mel_decoder_launch(blob, s, x, h0, cum, mel_len, lmax_dev, lmax_host, apply_mask, B, T, L_out, mel, workspace, workspace_bytes, 32, stream);
-}
-
-int esmi_mel_decoder_prec_f32(const float* blob, const esmi_decoder_shape* s, const float* x, const float* h0,
-                              const int32_t* cum, const int32_t* mel_len, const int32_t* lmax_dev, int lmax_host, int apply_mask, int B, int T,
-                              int L_out, float* mel, void* workspace, size_t workspace_bytes, int precision, esmi_stream_t stream) {
-    return mel_decoder_launch(blob, s, x, h0, cum, mel_len, lmax_dev, lmax_host, apply_mask, B, T, L_out, mel, workspace, workspace_bytes, precision,
-                              stream);
+    return esmi_mel_decoder_prec_f32(blob, s, x, h0, cum, mel_len, lmax_dev, lmax_host, apply_mask, B, T, L_out, mel, workspace, workspace_bytes, 32,
+                                     stream);
 }
 }  // extern "C"

@@ -95,8 +95,8 @@ CONTROL_KEYS = ("pitch_control", "energy_control", "duration_control")
 def _prosody_controls(x, B, dev, train=False):
     """The prosody controls of an input dict (extension keys `pitch_control`, `energy_control`, `duration_control`; the reference
     declares `control=1.` and never wires it, layers/networks.py:128-149) -> (the control struct or None when no key is present, the
-    fp32 device tensors it points into -- keep them alive until the launch is enqueued).  The struct is `_lib.ProsodyControl` while
-    every key is per utterance (the entry points and results of before, bit for bit) and `_lib.ProsodyCurves` once a key is a curve.
+    fp32 device tensors it points into -- keep them alive until the launch is enqueued).  The struct is a `_lib.ProsodyCurves`, what the
+    *_curve_f32 entry points take (the only ones the modules call); a per-utterance value leaves its `*_per_phoneme` at 0.
 
     A value is a Python number (broadcast over the batch), a tensor of shape (B,) or () -- one scale per utterance -- or a tensor
     of shape (B, T): a per-phoneme curve (`prosody_curve` builds one from spans).  Each key chooses its form on its own.  The
@@ -117,7 +117,7 @@ def _prosody_controls(x, B, dev, train=False):
         raise ValueError("duration_control together with duration_forced: a forced duration is final and is never scaled")
     T = int(x["phoneme"].shape[1])
     curves = [k for k in given if torch.is_tensor(x[k]) and x[k].dim() == 2 and tuple(x[k].shape) == (B, T)]
-    ctl, keep = (_lib.ProsodyCurves() if curves else _lib.ProsodyControl()), []
+    ctl, keep = _lib.ProsodyCurves(), []
     for k in given:
         v = x[k]
         if isinstance(v, numbers.Real):
@@ -160,6 +160,43 @@ def prosody_curve(lengths_or_shape, spans, default=1.0):
             raise ValueError(f"prosody_curve: span ({start}, {stop}) of utterance {b}: expected 0 <= start <= stop")
         curve[int(b), int(start):T if stop is None else min(int(stop), T)] = float(value)
     return curve
+
+
+class _Request:
+    """The inference extension keys of an input dict, read in ONE place for `PhonemeEncoder._encode`, `Phoneme2Mel._launch` and
+    `sharded.GraphedForward`: `phoneme_mask` (the B > 1 rule), `duration_forced`, the prosody controls, `decoder_precision`,
+    `max_mel_len` / `max_mel_len_exact`.  The constructor only looks at the dict (no device work, cheap enough per graph replay):
+      B, T; phoneme_mask -- None for B == 1, KeyError without the key for B > 1, as the reference (:338)
+      controls           -- the `CONTROL_KEYS` present
+      decoder_precision(default) -- the decoder's for this call, validated: the key, else `default` (the decoder's attribute)
+      L_out, lmax_host   -- from `max_mel_len`: the allocation length without a host sync, and that length again when the caller vouches
+                            for it (`max_mel_len_exact`), else -1 = the device derives the exact one; both None without the key
+    `on(dev)` adds the device side: ids, m8, dur_t (`duration_forced`; never while training: the teacher durations hold there), and
+    ctl / ctl_keep (`_prosody_controls`: the struct or None, and the tensors it points into -- alive until the launches are enqueued).
+    `Phoneme2Mel._launch` keeps the call's own state on it too (its buffers, the plan, the precision): what a stage-1 call returns."""
+
+    def __init__(self, x, train=False):
+        self.x, self.train = x, train
+        self.B, self.T = x["phoneme"].shape
+        self.phoneme_mask = x["phoneme_mask"] if self.B > 1 else None
+        self.controls = [k for k in CONTROL_KEYS if x.get(k) is not None]
+        self.L_out = self.lmax_host = None
+        if "max_mel_len" in x:
+            self.L_out = int(x["max_mel_len"])
+            self.lmax_host = self.L_out if bool(x.get("max_mel_len_exact", False)) else -1
+
+    def decoder_precision(self, default):
+        return _decoder_precision(self.x.get("decoder_precision"), default)
+
+    def on(self, dev):
+        x, B, T = self.x, self.B, self.T
+        self.ids = x["phoneme"].detach().to(device=dev, dtype=torch.int32).contiguous()
+        self.m8 = _mask_u8(self.phoneme_mask)
+        self.dur_t = None
+        if not self.train and "duration_forced" in x:
+            self.dur_t = x["duration_forced"].detach().reshape(B, T).to(device=dev, dtype=torch.int32).contiguous()
+        self.ctl, self.ctl_keep = _prosody_controls(x, B, dev, self.train)
+        return self
 
 
 def get_mask_from_lengths(lengths, max_len=None):
@@ -604,7 +641,7 @@ def _decoder_precision(precision, default=32):
 
 
 class MelDecoder(_PackedModule):
-    """Mel spectrogram decoder (networks.py:261-304), one fused HIP kernel per call.
+    """Mel spectrogram decoder (networks.py:261-304), one fused HIP kernel per call: esmi_mel_decoder_prec_f32, at either precision.
     `precision` (a plain attribute, not in the state_dict; default 32): 16 runs every contraction of the kernel as ONE binary16
     product with fp32 accumulation (include/esmi.h) -- the same packed weights, the same launch geometry.  It is the default of
     `forward` and of the inference forward of `Phoneme2Mel`; `Phoneme2Mel.forward(x, train=True)` runs the decoder at 32 regardless."""
@@ -674,13 +711,6 @@ class MelDecoder(_PackedModule):
         with _on_device_of(self.mel_linear.weight):
             return self._forward(features, precision)
 
-    def _decode(self, lib, precision, *args):
-        """the decoder launch: the plain entry point at precision 32, esmi_mel_decoder_prec_f32 at 16 (args: those of the plain one)"""
-        if precision == 32:
-            lib.esmi_mel_decoder_f32(*args)
-        else:
-            lib.esmi_mel_decoder_prec_f32(*args[:-1], precision, args[-1])
-
     def _forward(self, features, precision=None):
         """features (B,L,4*dim) -> mel (B,L,n_mel).  (Direct mode: rows exactly as given.)  precision: 32 or 16; None: `self.precision`."""
         precision = _decoder_precision(precision, self.precision)
@@ -691,8 +721,8 @@ class MelDecoder(_PackedModule):
         if L > 0:
             shape = self._shape()
             ws, ws_bytes = self._workspace(lib, shape, B, L, x.device)
-            self._decode(lib, precision, _ptr(self._packed(lib, stream)), C.byref(shape), _ptr(x), None, None, None, None, L, 0,
-                         B, 0, L, _ptr(mel), _ptr(ws), ws_bytes, stream)
+            lib.esmi_mel_decoder_prec_f32(_ptr(self._packed(lib, stream)), C.byref(shape), _ptr(x), None, None, None, None, L, 0,
+                                          B, 0, L, _ptr(mel), _ptr(ws), ws_bytes, precision, stream)
         return mel
 
     @staticmethod
@@ -733,8 +763,8 @@ class MelDecoder(_PackedModule):
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
             ws, ws_bytes = self._workspace(lib, shape, B, L_out, feat.device)
-            self._decode(lib, precision, _ptr(blob), C.byref(shape), _ptr(feat), _ptr(h0), _ptr(cum), _ptr(mel_len), _ptr(lmax_dev),
-                         int(lmax_host), int(apply_mask), B, T, L_out, _ptr(mel), _ptr(ws), ws_bytes, stream)
+            lib.esmi_mel_decoder_prec_f32(_ptr(blob), C.byref(shape), _ptr(feat), _ptr(h0), _ptr(cum), _ptr(mel_len), _ptr(lmax_dev),
+                                          int(lmax_host), int(apply_mask), B, T, L_out, _ptr(mel), _ptr(ws), ws_bytes, precision, stream)
             if ev is not None:
                 ev[1].record()
                 self.timing.append(ev)
@@ -768,14 +798,12 @@ class PhonemeEncoder(_PackedModule):
         """Everything up to (and including) the duration scan; nothing frame-rate is materialised.
         Inference extension keys: `duration_forced`, and the per-utterance prosody controls `pitch_control`, `energy_control`,
         `duration_control`, each per utterance or a (B, T) per-phoneme curve (numbers are validated on the host, device tensors are not
-        synchronised for it: `_prosody_controls`)."""
-        phoneme = x["phoneme"]
-        B = phoneme.shape[0]
-        ctl, _ctl_keep = _prosody_controls(x, B, self.encoder.embed.weight.device, train)   # (_ctl_keep: alive until the launches are enqueued)
-        phoneme_mask = x["phoneme_mask"] if B > 1 else None           # KeyError for B>1, as the reference (:338)
+        synchronised for it: `_prosody_controls`); `_Request` reads them.  The stage is one call of esmi_fuse_variance_adaptor_curve_f32."""
         dev = self.encoder.embed.weight.device
+        req = _Request(x, train).on(dev)                              # (req.ctl_keep: alive until the launches are enqueued)
+        B = req.B
         lib, stream = _runtime(self.encoder.embed.weight)
-        feats, bmasks = self.encoder._run(phoneme, phoneme_mask)
+        feats, bmasks = self.encoder._run(req.ids, req.phoneme_mask)
         T, dim = feats[0].shape[1], self.dim
         m8 = bmasks[0]
         feat = torch.empty((B, T, 4 * dim), dtype=torch.float32, device=dev)
@@ -787,9 +815,7 @@ class PhonemeEncoder(_PackedModule):
                 return None
             return x[key].detach().reshape(B, T).to(device=dev, dtype=dtype).contiguous()
         pitch_t, energy_t = tgt("pitch", torch.float32), tgt("energy", torch.float32)
-        dur_t = tgt("duration", torch.int32)
-        if not train and "duration_forced" in x:                       # extension: inject durations at inference
-            dur_t = x["duration_forced"].detach().reshape(B, T).to(device=dev, dtype=torch.int32).contiguous()
+        dur_t = tgt("duration", torch.int32) if train else req.dur_t   # (extension: inject durations at inference)
         preds = torch.empty((3, B, T, 1), dtype=torch.float32, device=dev)
         idxs = torch.empty((2, B, T), dtype=torch.int32, device=dev)
         dur = torch.empty((B, T), dtype=torch.int32, device=dev)
@@ -807,15 +833,10 @@ class PhonemeEncoder(_PackedModule):
         args = (C.byref(fw), depth, dim, self.fuse.kernel_size, B, T, fp, ni, C.byref(pw), C.byref(ew), C.byref(dw), _ptr(m8),
                 _ptr(pitch_t), _ptr(energy_t), _ptr(dur_t), _ptr(feat), _ptr(preds[0]), _ptr(preds[1]), _ptr(preds[2]),
                 _ptr(idxs[0]), _ptr(idxs[1]), _ptr(dur), _ptr(cum), _ptr(mel_len))
-        plan = _lib.current_plan()
+        plan, ctl_p = _lib.current_plan(), None if req.ctl is None else C.byref(req.ctl)
 
-        def stage(head_p, h0_p):              # (with controls: the _ctl / _curve entry point, same arguments + the scales)
-            if ctl is None:
-                lib.esmi_fuse_variance_adaptor_f32(*args, head_p, h0_p, plan, _ptr(ws), ws_bytes, stream)
-            elif isinstance(ctl, _lib.ProsodyCurves):
-                lib.esmi_fuse_variance_adaptor_curve_f32(*args, head_p, h0_p, plan, _ptr(ws), ws_bytes, stream, C.byref(ctl))
-            else:
-                lib.esmi_fuse_variance_adaptor_ctl_f32(*args, head_p, h0_p, plan, _ptr(ws), ws_bytes, stream, C.byref(ctl))
+        def stage(head_p, h0_p):
+            lib.esmi_fuse_variance_adaptor_curve_f32(*args, head_p, h0_p, plan, _ptr(ws), ws_bytes, stream, ctl_p)
         if h0 is not None:
             try:
                 stage(C.byref(head[0]), _ptr(h0))
@@ -902,7 +923,7 @@ class Phoneme2Mel(nn.Module):
             pred["mel"] = mel
             return pred
         # inference: the (B,L,4*dim) tensor is never materialised -- the decoder gathers through the duration scan and
-        # applies the final masked_fill itself; the whole forward is ONE C-ABI call (esmi_phoneme2mel_forward_f32)
+        # applies the final masked_fill itself; the whole forward is ONE C-ABI call (esmi_phoneme2mel_forward_curve_f32)
         if os.environ.get("ESMI_DEBUG_RANGE") == "1":
             # the FIRST forward of every set of weights runs on the range-checked build (check_activation_range) and raises
             # _lib.ActivationRange where the product build would saturate an activation silently; later forwards of the same
@@ -964,8 +985,9 @@ class Phoneme2Mel(nn.Module):
 
     def _launch(self, x, stage=0, state=None, taps=False):
         """Enqueue the inference forward (stage 0), its encoder side only (1), or the decoder (2) on the `state` a stage-1
-        call returned (a multi-GPU caller MAX-reduces `state.lmax` in between).  -> namespace with mel, mel_len,
-        duration (B,T,1), lmax (device scalar or None).
+        call returned (a multi-GPU caller MAX-reduces `state.lmax` in between).  -> the call's `_Request` with mel, mel_len,
+        duration (B,T,1), lmax (device scalar or None).  Every stage is one call of esmi_phoneme2mel_forward_curve_f32 (the control struct
+        or NULL, the precision): the older entry points are that call with NULL and / or 32 (include/esmi.h).
         Inference extension keys of x: `duration_forced`, `max_mel_len` (`max_mel_len_exact`), `decoder_precision` (16 or 32, validated on
         the host: the mel decoder's arithmetic for this call, overriding `self.decoder.precision`; the encoder side is untouched by it, so
         mel_len and the durations are the same bits either way -- include/esmi.h), and the per-utterance prosody controls
@@ -973,7 +995,6 @@ class Phoneme2Mel(nn.Module):
         device tensors are not synchronised for it: `_prosody_controls`).
         taps (tests): also return what `PhonemeEncoder._encode` exposes -- `state.taps` = pitch, energy (B,T) raw predictions,
         pitch_idx, energy_idx, dur, cum (B,T) int32."""
-        from types import SimpleNamespace
         w = self.decoder.mel_linear.weight
         lib, stream = _runtime(w)
         dev = w.device
@@ -981,29 +1002,16 @@ class Phoneme2Mel(nn.Module):
         if stage == 2:
             st = state
         else:
-            phoneme = x["phoneme"]
-            B = phoneme.shape[0]
-            phoneme_mask = x["phoneme_mask"] if B > 1 else None       # KeyError for B>1, as the reference (:338)
-            ids = phoneme.detach().to(device=dev, dtype=torch.int32).contiguous()
-            T = ids.shape[1]
-            dur_t = None
-            if "duration_forced" in x:                                # extension: inject durations at inference
-                dur_t = x["duration_forced"].detach().reshape(B, T).to(device=dev, dtype=torch.int32).contiguous()
-            ctl, ctl_keep = _prosody_controls(x, B, dev)
-            tap = None
+            st = _Request(x).on(dev)
+            B, T = st.B, st.T
+            st.taps = None
             if taps:
-                tap = {k: torch.empty((B, T), dtype=torch.float32 if k in ("pitch", "energy") else torch.int32, device=dev)
-                       for k in ("pitch", "energy", "pitch_idx", "energy_idx", "dur", "cum")}
-            st = SimpleNamespace(ids=ids, m8=_mask_u8(phoneme_mask), dur_t=dur_t, B=B, T=T, lmax=None, mel=None, L_out=None,
-                                 precision=_decoder_precision(x.get("decoder_precision"), self.decoder.precision),
-                                 prec_entry="decoder_precision" in x or self.decoder.precision != 32,
-                                 ctl=ctl, ctl_keep=ctl_keep, taps=tap,
-                                 lmax_host=None, plan=_lib.current_plan(),
-                                 mel_len=torch.empty((B,), dtype=torch.int32, device=dev),
-                                 duration=torch.empty((B, T, 1), dtype=torch.float32, device=dev))
-            if "max_mel_len" in x:                                    # extension: output length from the caller, no host sync
-                st.L_out = int(x["max_mel_len"])
-                st.lmax_host = st.L_out if bool(x.get("max_mel_len_exact", False)) else -1
+                st.taps = {k: torch.empty((B, T), dtype=torch.float32 if k in ("pitch", "energy") else torch.int32, device=dev)
+                           for k in ("pitch", "energy", "pitch_idx", "energy_idx", "dur", "cum")}
+            st.precision, st.plan = st.decoder_precision(self.decoder.precision), _lib.current_plan()
+            st.lmax = st.mel = None
+            st.mel_len = torch.empty((B,), dtype=torch.int32, device=dev)
+            st.duration = torch.empty((B, T, 1), dtype=torch.float32, device=dev)
             if st.L_out is None or (stage == 1 and st.lmax_host < 0):
                 st.lmax = torch.empty((1,), dtype=torch.int32, device=dev)
         # per-call fields of THIS state
@@ -1020,17 +1028,10 @@ class Phoneme2Mel(nn.Module):
         a.arena, a.arena_bytes = _ptr(st.arena), st.arena.numel()
         rf = getattr(self, "_range_flag", None)                       # validation mode only (check_activation_range)
         a.range_flag = _ptr(rf)
-        dec = self.decoder
+        dec, ctl_p = self.decoder, None if st.ctl is None else C.byref(st.ctl)
 
-        def forward(stage_):                   # (with controls: the _ctl / _curve entry point; stage 2 ignores them)
-            if isinstance(st.ctl, _lib.ProsodyCurves):   # (a per-phoneme curve: the entry point that takes them carries the precision too)
-                lib.esmi_phoneme2mel_forward_curve_f32(C.byref(a), C.byref(st.ctl), st.precision if st.prec_entry else 32, stage_, stream)
-            elif st.prec_entry and stage_ != 1:   # (a precision was asked for -- 32 included: the _prec entry point; stage 1 has one arithmetic)
-                lib.esmi_phoneme2mel_forward_prec_f32(C.byref(a), None if st.ctl is None else C.byref(st.ctl), st.precision, stage_, stream)
-            elif st.ctl is None:
-                lib.esmi_phoneme2mel_forward_f32(C.byref(a), stage_, stream)
-            else:
-                lib.esmi_phoneme2mel_forward_ctl_f32(C.byref(a), C.byref(st.ctl), stage_, stream)
+        def forward(stage_):                   # (stage 1 ignores the precision, stage 2 the controls)
+            lib.esmi_phoneme2mel_forward_curve_f32(C.byref(a), ctl_p, st.precision, stage_, stream)
         timed = False
         if stage != 1 and dec.timing is not None:                     # bench.py: HIP events around the decoder launch only
             dec._launches += 1

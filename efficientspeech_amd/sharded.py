@@ -16,7 +16,7 @@ throughput.
 import torch
 import torch.distributed as dist
 
-from .networks import _decoder_precision
+from .networks import _Request
 
 
 def _encode_with_head(net, x, need_lmax=True):
@@ -108,13 +108,11 @@ def sharded_forward(net, x_full, group=None):
     return tuple(outs)
 
 
-def _refuse_controls_in_graph(x):
+def _refuse_controls_in_graph(req):
     """The graph-replay path captures the encoder side once, with whatever scales that call had: a control key would be baked in (a
     number) or silently dropped (a key the captured step did not have).  Not built: refuse, never drop."""
-    from .networks import CONTROL_KEYS
-    given = [k for k in CONTROL_KEYS if x.get(k) is not None]
-    if given:
-        raise NotImplementedError(f"{given[0]}: the prosody controls are not captured by the graph-replay path (use_graph / "
+    if req.controls:
+        raise NotImplementedError(f"{req.controls[0]}: the prosody controls are not captured by the graph-replay path (use_graph / "
                                   "GraphedForward); run this step without use_graph")
 
 
@@ -127,12 +125,12 @@ class GraphedForward:
 
     def __init__(self, net, x, nbuf=3, warmup=3):
         assert "max_mel_len" in x, "graph replay needs a static output length (x['max_mel_len'])"
-        _refuse_controls_in_graph(x)
+        req = _Request(x)
+        _refuse_controls_in_graph(req)
         self.net = net
         # the decoder's precision is captured with its launch: the key of `x`, else the decoder's attribute AS IT IS NOW (`load` refuses
         # a step that asks for another one)
-        self.precision = _decoder_precision(x.get("decoder_precision"), net.decoder.precision)
-        self.L = int(x["max_mel_len"])
+        self.precision, self.L = req.decoder_precision(net.decoder.precision), req.L_out
         self.x = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in x.items()}
         B = self.x["phoneme"].shape[0]
         self.apply_mask = ("phoneme_mask" in self.x) and B > 1
@@ -159,8 +157,9 @@ class GraphedForward:
         self.i = 0
 
     def load(self, x):
-        _refuse_controls_in_graph(x)
-        want = _decoder_precision(x.get("decoder_precision"), self.net.decoder.precision)
+        req = _Request(x)
+        _refuse_controls_in_graph(req)
+        want = req.decoder_precision(self.net.decoder.precision)
         if want != self.precision:   # (refuse, never drop: the captured decoder launch has one arithmetic)
             raise NotImplementedError(f"decoder_precision: this step asks for precision {want}, the captured graph runs the decoder at "
                                       f"{self.precision} (the key, or `decoder.precision`, at capture time); build a new GraphedForward")

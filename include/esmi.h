@@ -233,6 +233,7 @@ typedef struct esmi_predictor_weights {
     const float* conv2_wp;
 } esmi_predictor_weights;
 size_t esmi_variance_adaptor_workspace_bytes(int B, int T, int dim);
+/* (Is esmi_variance_adaptor_curve_f32(..., NULL) below: the general form, which the two older ones forward to.) */
 int esmi_variance_adaptor_f32(const esmi_predictor_weights* pitch, const esmi_predictor_weights* energy,
                               const esmi_predictor_weights* duration, int dim, int B, int T,
                               const uint8_t* mask,          /* (B,T) or NULL (B == 1 path)              */
@@ -260,7 +261,8 @@ int esmi_variance_adaptor_f32(const esmi_predictor_weights* pitch, const esmi_pr
 typedef struct esmi_prosody_control {      /* each: (B) device fp32, or NULL = 1 */
     const float* pitch_scale; const float* energy_scale; const float* duration_scale;
 } esmi_prosody_control;
-/* esmi_variance_adaptor_f32 with the controls (ctl == NULL: exactly that call) */
+/* esmi_variance_adaptor_f32 with the controls (ctl == NULL: exactly that call).  Is esmi_variance_adaptor_curve_f32 with the same three
+ * pointers and every *_per_phoneme == 0. */
 int esmi_variance_adaptor_ctl_f32(const esmi_predictor_weights* pitch, const esmi_predictor_weights* energy,
                                   const esmi_predictor_weights* duration, int dim, int B, int T, const uint8_t* mask,
                                   const float* pitch_target, const float* energy_target, const int32_t* duration_target,
@@ -288,8 +290,8 @@ typedef struct esmi_prosody_curves {
     const float* pitch_scale; const float* energy_scale; const float* duration_scale;   /* device fp32 or NULL = 1                 */
     int32_t pitch_per_phoneme; int32_t energy_per_phoneme; int32_t duration_per_phoneme; /* 0: that pointer is (B); else (B, T)    */
 } esmi_prosody_curves;
-/* esmi_variance_adaptor_f32 with curves or per-utterance scales (ctl == NULL: exactly that call; all *_per_phoneme == 0: exactly the
- * _ctl call) */
+/* The general form: esmi_variance_adaptor_f32 with curves or per-utterance scales (ctl == NULL: exactly that call; all
+ * *_per_phoneme == 0: exactly the _ctl call) */
 int esmi_variance_adaptor_curve_f32(const esmi_predictor_weights* pitch, const esmi_predictor_weights* energy,
                                     const esmi_predictor_weights* duration, int dim, int B, int T, const uint8_t* mask,
                                     const float* pitch_target, const float* energy_target, const int32_t* duration_target,
@@ -321,6 +323,8 @@ typedef struct esmi_decoder_head {
 int esmi_decoder_head_f32(const esmi_decoder_head* head, long rows, const float* feat, float* h0, esmi_stream_t stream);
 
 size_t esmi_fuse_variance_adaptor_workspace_bytes(int B, int T, int dim, int depth);
+/* (Is esmi_fuse_variance_adaptor_curve_f32(..., NULL) below: the general form, which the two older ones forward to and the Python
+ * modules call.) */
 int esmi_fuse_variance_adaptor_f32(const esmi_fuse_weights* fuse, int depth, int dim, int kernel, int B, int T,
                                    const float* const* feats, const int* n_i, const esmi_predictor_weights* pitch,
                                    const esmi_predictor_weights* energy, const esmi_predictor_weights* duration,
@@ -335,7 +339,8 @@ int esmi_fuse_variance_adaptor_f32(const esmi_fuse_weights* fuse, int depth, int
                                    int plan,                                 /* ESMI_FUSE_* bits of this call     */
                                    void* workspace, size_t workspace_bytes, esmi_stream_t stream);
 /* ... with the prosody controls (esmi_prosody_control above; layers/networks.py:128-149, :379-382): whichever kernel serves the shape
- * applies them.  ctl == NULL: exactly esmi_fuse_variance_adaptor_f32. */
+ * applies them.  ctl == NULL: exactly esmi_fuse_variance_adaptor_f32.  Is esmi_fuse_variance_adaptor_curve_f32 with the same three
+ * pointers and every *_per_phoneme == 0. */
 int esmi_fuse_variance_adaptor_ctl_f32(const esmi_fuse_weights* fuse, int depth, int dim, int kernel, int B, int T,
                                        const float* const* feats, const int* n_i, const esmi_predictor_weights* pitch,
                                        const esmi_predictor_weights* energy, const esmi_predictor_weights* duration,
@@ -345,8 +350,8 @@ int esmi_fuse_variance_adaptor_ctl_f32(const esmi_fuse_weights* fuse, int depth,
                                        int32_t* cum, int32_t* mel_len, const esmi_decoder_head* head, float* h0, int plan,
                                        void* workspace, size_t workspace_bytes, esmi_stream_t stream,
                                        const esmi_prosody_control* ctl);
-/* ... with per-phoneme curves or per-utterance scales (esmi_prosody_curves above): whichever kernel serves the shape applies them.
- * ctl == NULL: exactly esmi_fuse_variance_adaptor_f32. */
+/* The general form: with per-phoneme curves or per-utterance scales (esmi_prosody_curves above): whichever kernel serves the shape
+ * applies them.  ctl == NULL: exactly esmi_fuse_variance_adaptor_f32. */
 int esmi_fuse_variance_adaptor_curve_f32(const esmi_fuse_weights* fuse, int depth, int dim, int kernel, int B, int T,
                                          const float* const* feats, const int* n_i, const esmi_predictor_weights* pitch,
                                          const esmi_predictor_weights* energy, const esmi_predictor_weights* duration,
@@ -454,7 +459,8 @@ int esmi_mel_decoder_pack_f32(const esmi_decoder_weights* w, const esmi_decoder_
  * lmax_dev != NULL, else lmax_host if >= 0, else max_b mel_len[b] (every workgroup derives it from
  * mel_len, which is then required).  mel is (B, L_out, n_mel); rows in [L, L_out) are zeroed.
  * mel_len != NULL && apply_mask: rows >= mel_len[b] are zeroed (Phoneme2Mel's final
- * masked_fill, networks.py:424-427).                                                          */
+ * masked_fill, networks.py:424-427).
+ * (Is esmi_mel_decoder_prec_f32(..., 32, stream) below: the general form, which the Python modules call.) */
 int esmi_mel_decoder_f32(const float* blob, const esmi_decoder_shape* s, const float* x,
                          const float* h0, /* optional, fused mode only: (B,T,dx2) = LN(tanh(proj(x))), see esmi_decoder_head */
                          const int32_t* cum, const int32_t* mel_len, const int32_t* lmax_dev, int lmax_host, int apply_mask, int B,
@@ -516,11 +522,14 @@ typedef struct esmi_forward_args {
 } esmi_forward_args;
 size_t esmi_forward_arena_bytes(const esmi_forward_args* a);
 /* stage = 0: everything; 1: encoder side only (up to cum / mel_len / lmax_dev / h0, kept in the arena); 2: mel decoder only,
- * on the arena a stage-1 call filled (same args) -- lets a multi-GPU caller put its MAX all-reduce of lmax_dev in between. */
+ * on the arena a stage-1 call filled (same args) -- lets a multi-GPU caller put its MAX all-reduce of lmax_dev in between.
+ * (Is esmi_phoneme2mel_forward_curve_f32(a, NULL, 32, stage, stream) below: the general form, which the three older ones forward to and
+ * the Python modules call.) */
 int esmi_phoneme2mel_forward_f32(const esmi_forward_args* a, int stage, esmi_stream_t stream);
 /* ... with per-utterance prosody controls (esmi_prosody_control; the reference's unwired `control`, layers/networks.py:128-149, and the
  * rounding of :379-382): applied inside the encoder-side kernels, the one-launch form included.  ctl == NULL: exactly the call above.
- * duration_scale together with a->dur_forced is ESMI_ERR_ARG (nothing launched).  Stage 2 (the decoder alone) ignores ctl. */
+ * duration_scale together with a->dur_forced is ESMI_ERR_ARG (nothing launched).  Stage 2 (the decoder alone) ignores ctl.
+ * Is esmi_phoneme2mel_forward_curve_f32 with the same three pointers, every *_per_phoneme == 0, and precision 32. */
 int esmi_phoneme2mel_forward_ctl_f32(const esmi_forward_args* a, const esmi_prosody_control* ctl, int stage, esmi_stream_t stream);
 
 /* Mel decoder at precision 16 (opt-in; the same rule as the vocoder's, esmi_hifigan_generator_prec_f32 below: the reference synthesises
@@ -546,11 +555,11 @@ int esmi_mel_decoder_prec_f32(const float* blob, const esmi_decoder_shape* s, co
                               float* mel, void* workspace, size_t workspace_bytes, int precision, esmi_stream_t stream);
 /* The whole forward with the decoder's precision: ctl == NULL as in esmi_phoneme2mel_forward_f32, else as in the _ctl call.  Stage 1 (the
  * encoder side alone) ignores `precision`; stages 0 and 2 hand it to the decoder.  A refused precision launches nothing, the encoder
- * side included. */
+ * side included.  Is esmi_phoneme2mel_forward_curve_f32 with the same three pointers, every *_per_phoneme == 0, and this precision. */
 int esmi_phoneme2mel_forward_prec_f32(const esmi_forward_args* a, const esmi_prosody_control* ctl, int precision, int stage,
                                       esmi_stream_t stream);
-/* ... with per-phoneme curves or per-utterance scales (esmi_prosody_curves): `precision` and `stage` as in the _prec call, which is this
- * call with every *_per_phoneme == 0.  A duration curve or scale together with a->dur_forced is ESMI_ERR_ARG (nothing launched).  Stage 2
+/* The general form: with per-phoneme curves or per-utterance scales (esmi_prosody_curves): `precision` and `stage` as in the _prec call,
+ * which is this call with every *_per_phoneme == 0.  A duration curve or scale together with a->dur_forced is ESMI_ERR_ARG (nothing launched).  Stage 2
  * ignores ctl. */
 int esmi_phoneme2mel_forward_curve_f32(const esmi_forward_args* a, const esmi_prosody_curves* ctl, int precision, int stage,
                                        esmi_stream_t stream);

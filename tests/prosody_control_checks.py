@@ -253,11 +253,11 @@ def check_abi_errors(device, launches=None):
             # the one-call forward: duration_scale next to dur_forced.  The Python layer refuses that combination itself, so hand the
             # library the scale behind its back
             real = networks._prosody_controls
-            ctl = _lib.ProsodyControl()
+            ctl = _lib.ProsodyCurves()
             ctl.duration_scale = p(ones)
             networks._prosody_controls = lambda *a, **k: (ctl, (ones,))
             try:
-                with pytest.raises(RuntimeError, match="esmi_phoneme2mel_forward_ctl_f32 failed: ESMI_ERR_ARG"):
+                with pytest.raises(RuntimeError, match="esmi_phoneme2mel_forward_curve_f32 failed: ESMI_ERR_ARG"):
                     net._launch(dict(x, duration_forced=tgt_i + 2))
             finally:
                 networks._prosody_controls = real
