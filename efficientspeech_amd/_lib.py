@@ -79,6 +79,9 @@ class HifiGanShape(C.Structure):
                 ("rb_kernels", C.c_int * HIFIGAN_MAX_KERNELS), ("rb_dilations", C.c_int * (HIFIGAN_MAX_KERNELS * 3))]
 
 
+PRECISION_BF16 = 0xB16      # ESMI_PRECISION_BF16 (include/esmi.h): esmi_conv_desc.precision of the bf16-mixed training GEMMs
+
+
 class ConvDesc(C.Structure):
     """esmi_conv_desc (include/esmi.h): one convolution of the training step, checkpoint weight layout."""
     _fields_ = [(n, C.c_int) for n in ("B", "n_in", "c_in", "n_out", "c_out", "k", "stride", "pad", "groups", "transposed", "precision", "act")] + \

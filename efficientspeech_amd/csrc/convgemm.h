@@ -20,6 +20,13 @@
 namespace esmi {
 
 enum ConvMode { MODE_CONV = 0, MODE_CONVT = 1 };
+// how a GEMM body forms its matrix-pipe operands (a template parameter of the bodies below; `false` / `true` of the binary16 kernels'
+// AMP parameter convert to the first two):
+//   OPK_SPLIT  fp32-accurate: two binary16 pieces per value, weights scaled by 2^8, three products per 16 channels
+//   OPK_F16    `precision = 16`: both operands rounded to binary16 (weights after the 2^8 scale), one product
+//   OPK_BF16   bf16-mixed (ConvGemmP::amp == 2): both operands rounded to bfloat16 as they are -- no weight scale, no operand scale
+//              (io_scale is NULL) --, one v_mfma_f32_32x32x16_bf16
+enum GemmOperand { OPK_SPLIT = 0, OPK_F16 = 1, OPK_BF16 = 2 };
 
 struct ConvGemmP {
     // input rows: A + (b*n_in + t)*lda + a_coff, or embedding rows table + ids[b*n_in + t]*ld_table
@@ -57,7 +64,9 @@ struct ConvGemmP {
     const float* io_scale;
     // training with `precision=16` (the reference's default, utils/tools.py:326-327 -> torch.autocast): 1 = both operands are rounded
     // to binary16 (nearest) and the contraction is ONE v_mfma_f32_32x32x16_f16 per 16 channels instead of the three products of
-    // the fp32-accurate split; fp32 accumulation, fp32 in / out (master weights and activations stay fp32 in memory)
+    // the fp32-accurate split; fp32 accumulation, fp32 in / out (master weights and activations stay fp32 in memory).
+    // 2 = bf16-mixed (the reference's `--precision bf16-mixed`): the same with bfloat16 in place of binary16 -- the weights are rounded
+    // as they are, io_scale must be NULL, and the pre-split blob `Wp` (binary16 pieces) is not read
     int amp;
     // optional: the same weights in MFMA B-fragment order with pre-split binary16 pieces (esmi_pack_bfrag_f32 of W, taps = k; the
     // `*_wp` fields of include/esmi.h).  convgemm_dma_kernel then brings its weight tile in by LDS-DMA -- each 1 KiB block of the
@@ -132,13 +141,14 @@ __device__ __forceinline__ f32x4 conv_act_in(f32x4 v, const ConvGemmP& p, float 
 
 // Fused epilogue of the implicit-GEMM kernels, in the MFMA C/D layout (row = tile_row(r), col = n0 + 32*nt + (lane&31)):
 //   out = mask( post_relu( LN( act(acc * s + bias) + residual ) ) ), optional row-dot side output on the pre-LN value.
-template <int NT>
+// WSCALED: the accumulators hold products with 2^8 W (every operand kind but OPK_BF16)
+template <int NT, bool WSCALED = true>
 __device__ __forceinline__ void convgemm_epilogue(f32x16 (&acc)[NT], const ConvGemmP& p, int b, int t0, int n0, int lane, int ts = 1, int flat_rows = 0,
                                                   int t_lim = 0x7fffffff) {
     const int n_out = flat_rows ? flat_rows : p.n_out;   // (flat_rows: the caller's rows are b * n_out + t with b = 0)
     const int t_end = t_lim < n_out ? t_lim : n_out;     // rows from here on are not written, their residual / accumulator not read (t_lim: ConvGemmP::len)
     const int i = lane & 31;
-    const float out_s = (ESMI_CHAIN_SPLIT ? kF16WScaleInv : 1.0f) * conv_out_scale(p);
+    const float out_s = ((ESMI_CHAIN_SPLIT && WSCALED) ? kF16WScaleInv : 1.0f) * conv_out_scale(p);
     int col[NT];
     bool cok[NT];
     float bias[NT];
@@ -276,9 +286,9 @@ __device__ __forceinline__ void convgemm_epilogue(f32x16 (&acc)[NT], const ConvG
     }
 }
 
-// The kernel body.  AMP: ConvGemmP::amp as a compile-time constant (a run-time branch in the K loop broke its software pipeline: base
-// ES +35 %); LEN: ConvGemmP::len likewise (convgemm_len_kernel -- the plain kernels' machine code does not carry the limit)
-template <int NT, bool AMP, bool LEN>
+// The kernel body.  OPK (GemmOperand): ConvGemmP::amp as a compile-time constant (a run-time branch in the K loop broke its software
+// pipeline: base ES +35 %); LEN: ConvGemmP::len likewise (convgemm_len_kernel -- the plain kernels' machine code does not carry the limit)
+template <int NT, int OPK, bool LEN>
 __device__ __forceinline__ void convgemm_body(const ConvGemmP& p) {
     const int lane = lane_id();
     // A strided ConvTranspose1d tile holds 32 positions of ONE phase (t mod stride): only the k/stride taps of that phase are
@@ -348,10 +358,14 @@ __device__ __forceinline__ void convgemm_body(const ConvGemmP& p) {
         // out again): this plan takes the weights exactly as stored, there is no pre-split copy.  A lane's 8 k-slots of a step are
         // the channels 8kc + 4h + (0..3) and 8(kc+1) + 4h + (0..3) on BOTH sides, i.e. a fixed permutation of the 16 channels.
         auto step16 = [&](const f32x4& a0, const f32x4& a1, const f32x4 (&b0)[NT], const f32x4 (&b1)[NT]) __attribute__((always_inline)) {
-            if constexpr (AMP) {   // binary16 operands, one product
+            if constexpr (OPK == OPK_F16) {   // binary16 operands, one product
                 const u32x4 ah = round_f16x8(a0, a1);
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) acc[nt] = mfma32_f16(ah, round_f16x8(b0[nt] * kF16WScale, b1[nt] * kF16WScale), acc[nt]);
+            } else if constexpr (OPK == OPK_BF16) {   // bfloat16 operands, one product, nothing scaled
+                const u32x4 ab = round_bf16x8(a0, a1);
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) acc[nt] = mfma32_bf16(ab, round_bf16x8(b0[nt], b1[nt]), acc[nt]);
             } else {
                 const f16x2p a2 = split_f16x2(a0, a1);
 #pragma unroll
@@ -366,7 +380,8 @@ __device__ __forceinline__ void convgemm_body(const ConvGemmP& p) {
         // arrive as one coalesced 16-byte load per lane, piece and tile, and nothing is split: the loop above spends ~58 VALU instructions
         // per column tile and 16 channels on the weights (three MFMAs' worth of issue time four times over at NT = 4), the same for every
         // wave of the launch.  (Round 5; the blob's pieces are nearest-rounded, the on-the-fly ones truncated: last-bit differences.)
-        const bool pre = p.Wp != nullptr && (p.c_in & 31) == 0;          // (kernel-uniform)
+        constexpr bool AMP = OPK == OPK_F16;
+        const bool pre = OPK != OPK_BF16 && p.Wp != nullptr && (p.c_in & 31) == 0;          // (kernel-uniform; the blob holds binary16 pieces)
         if (pre) {
             const int ntw = (p.c_out + 31) >> 5, tile0 = n0 >> 5;
             for (; kc + KG <= kcs; kc += KG) {
@@ -455,12 +470,15 @@ __device__ __forceinline__ void convgemm_body(const ConvGemmP& p) {
 #endif
     }
 
-    if constexpr (LEN) convgemm_epilogue<NT>(acc, p, b, t0, n0, lane, ts, 0, n_lim);
-    else convgemm_epilogue<NT>(acc, p, b, t0, n0, lane, ts);
+    if constexpr (LEN) convgemm_epilogue<NT, OPK != OPK_BF16>(acc, p, b, t0, n0, lane, ts, 0, n_lim);
+    else convgemm_epilogue<NT, OPK != OPK_BF16>(acc, p, b, t0, n0, lane, ts);
 }
 
 template <int NT, bool AMP = false>
 __global__ __launch_bounds__(256) void convgemm_kernel(const ConvGemmP p) { convgemm_body<NT, AMP, false>(p); }
+// ... with bfloat16 operands (ConvGemmP::amp == 2: the training step's bf16-mixed precision)
+template <int NT>
+__global__ __launch_bounds__(256) void convgemm_bf16_kernel(const ConvGemmP p) { convgemm_body<NT, OPK_BF16, false>(p); }
 // the same with ConvGemmP::len applied (the HiFi-GAN stages of at most 64 channels in a length-aware call)
 template <int NT>
 __global__ __launch_bounds__(256) void convgemm_len_kernel(const ConvGemmP p) { convgemm_body<NT, false, true>(p); }
@@ -562,8 +580,11 @@ __host__ __device__ inline int convgemm_dma_bytes(int mt, int k, int dil, bool p
     return (pre ? 2 * 4 * NT * 1024 : convgemm_lds_bytes<NT>()) + nwv * convgemm_dma_tile_rows(mt, k, dil) * 128;
 }
 
-template <int NT, int MT, int NWV = kGemmLdsWaves, bool AMP = false, bool PRE = false>
-__global__ __launch_bounds__(64 * NWV, 2) void convgemm_dma_kernel(const ConvGemmP p, int nx, int ny) {
+// the body: OPK (GemmOperand) as in convgemm_body; OPK_BF16 stages the weights it rounds itself (PRE = false: the blob holds binary16)
+template <int NT, int MT, int NWV, int OPK, bool PRE>
+__device__ __forceinline__ void convgemm_dma_body(const ConvGemmP& p, int nx, int ny) {
+    static_assert(!(PRE && OPK == OPK_BF16), "the pre-split blob holds binary16 pieces");
+    constexpr bool AMP = OPK != OPK_SPLIT;   // one operand piece, one product
     constexpr int BN = 32 * NT, PLANE = BN * kGemmRowDw, NTHR = 64 * NWV, NU = (256 * NT) / NTHR, WROWS = 32 * MT, ROWS = WROWS * NWV;
     static_assert(NU * NTHR == 256 * NT, "staging items divide evenly");
     static_assert(MT <= 2, "epilogue calls below");
@@ -654,13 +675,17 @@ __global__ __launch_bounds__(64 * NWV, 2) void convgemm_dma_kernel(const ConvGem
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
             const int q = tid + NTHR * u;
-            const f32x4 x = w_nxt[u] * kF16WScale;
-            unsigned h1a, h2a, h1b, h2b;
-            split_f16_pair_rn(x[0], x[1], h1a, h2a);   // weights: nearest-rounded pieces, as the pack-time splitters
-            split_f16_pair_rn(x[2], x[3], h1b, h2b);
             unsigned* d = wt + (buf * 2) * PLANE + (q >> 3) * kGemmRowDw + 2 * (q & 7);
-            *reinterpret_cast<u32x2*>(d) = u32x2{h1a, h1b};
-            *reinterpret_cast<u32x2*>(d + PLANE) = u32x2{h2a, h2b};
+            if constexpr (OPK == OPK_BF16) {               // one bfloat16 plane of W as it is
+                *reinterpret_cast<u32x2*>(d) = u32x2{round_bf16_pair(w_nxt[u][0], w_nxt[u][1]), round_bf16_pair(w_nxt[u][2], w_nxt[u][3])};
+            } else {
+                const f32x4 x = w_nxt[u] * kF16WScale;
+                unsigned h1a, h2a, h1b, h2b;
+                split_f16_pair_rn(x[0], x[1], h1a, h2a);   // weights: nearest-rounded pieces, as the pack-time splitters
+                split_f16_pair_rn(x[2], x[3], h1b, h2b);
+                *reinterpret_cast<u32x2*>(d) = u32x2{h1a, h1b};
+                *reinterpret_cast<u32x2*>(d + PLANE) = u32x2{h2a, h2b};
+            }
         }
     };
 #ifdef ESMI_GEMM_TRACE   // development: shader-clock stamps of one mid-grid workgroup, 7 per K chunk (tools/trace_gemm.py)
@@ -710,7 +735,8 @@ __global__ __launch_bounds__(64 * NWV, 2) void convgemm_dma_kernel(const ConvGem
                     if (!plain) { lo = conv_act_in(lo, p, in_s); hi = conv_act_in(hi, p, in_s); }
                     lo = __builtin_bit_cast(f32x4, __builtin_bit_cast(u32x4, lo) & keep);
                     hi = __builtin_bit_cast(f32x4, __builtin_bit_cast(u32x4, hi) & keep);
-                    if constexpr (AMP) a_use[mt][st].h1 = round_f16x8(lo, hi);
+                    if constexpr (OPK == OPK_BF16) a_use[mt][st].h1 = round_bf16x8(lo, hi);
+                    else if constexpr (AMP) a_use[mt][st].h1 = round_f16x8(lo, hi);
                     else a_use[mt][st] = split_f16x2(lo, hi);
                 }
             }
@@ -748,7 +774,8 @@ __global__ __launch_bounds__(64 * NWV, 2) void convgemm_dma_kernel(const ConvGem
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt) {
                         f32x16& c = acc[mt * NT + 2 * np + q];
-                        c = mfma32_f16(a_use[mt][st].h1, bf[g & 1][q][0], c);
+                        if constexpr (OPK == OPK_BF16) c = mfma32_bf16(a_use[mt][st].h1, bf[g & 1][q][0], c);
+                        else c = mfma32_f16(a_use[mt][st].h1, bf[g & 1][q][0], c);
                     }
             } else {
                 // the three products of a tile are a dependent chain on its accumulator: run the 2 MT chains side by side
@@ -775,10 +802,19 @@ __global__ __launch_bounds__(64 * NWV, 2) void convgemm_dma_kernel(const ConvGem
         __syncthreads();                           // (its fence also drains this wave's DMA: vmcnt(0))
         ESMI_GT();   // 6: barrier passed
     }
-    if (r0 < n_rows) convgemm_epilogue<NT>(*reinterpret_cast<f32x16(*)[NT]>(&acc[0]), p, 0, (int)r0, n0, lane, 1, (int)n_rows);
+    if (r0 < n_rows) convgemm_epilogue<NT, OPK != OPK_BF16>(*reinterpret_cast<f32x16(*)[NT]>(&acc[0]), p, 0, (int)r0, n0, lane, 1, (int)n_rows);
     if constexpr (MT > 1) {
-        if (r0 + 32 < n_rows) convgemm_epilogue<NT>(*reinterpret_cast<f32x16(*)[NT]>(&acc[NT]), p, 0, (int)r0 + 32, n0, lane, 1, (int)n_rows);
+        if (r0 + 32 < n_rows) convgemm_epilogue<NT, OPK != OPK_BF16>(*reinterpret_cast<f32x16(*)[NT]>(&acc[NT]), p, 0, (int)r0 + 32, n0, lane, 1, (int)n_rows);
     }
+}
+template <int NT, int MT, int NWV = kGemmLdsWaves, bool AMP = false, bool PRE = false>
+__global__ __launch_bounds__(64 * NWV, 2) void convgemm_dma_kernel(const ConvGemmP p, int nx, int ny) {
+    convgemm_dma_body<NT, MT, NWV, AMP ? OPK_F16 : OPK_SPLIT, PRE>(p, nx, ny);
+}
+// ... with bfloat16 operands (ConvGemmP::amp == 2), weights rounded as the workgroup stages them
+template <int NT, int MT, int NWV = kGemmLdsWaves>
+__global__ __launch_bounds__(64 * NWV, 2) void convgemm_dma_bf16_kernel(const ConvGemmP p, int nx, int ny) {
+    convgemm_dma_body<NT, MT, NWV, OPK_BF16, false>(p, nx, ny);
 }
 #endif
 

@@ -863,7 +863,7 @@ int esmi_phoneme2mel_forward_curve_f32(const esmi_forward_args* a, const esmi_pr
                                     set_range_flag_enc_block, set_range_flag_enc_attn_ffn, set_range_flag_enc_fuse_va, set_range_flag_enc_va16, set_range_flag_enc_va64, set_range_flag_enc_pred128, set_range_flag_enc_block16,
                                     set_range_flag_decoder, set_range_flag_dec_128_5, set_range_flag_dec_128_3, set_range_flag_dec_256_5,
                                     set_range_flag_dec_256_3, set_range_flag_dec_128_5_p16, set_range_flag_dec_128_3_p16, set_range_flag_dec_256_5_p16,
-                                    set_range_flag_dec_256_3_p16, set_range_flag_hifigan, set_range_flag_hifigan_amp, set_range_flag_train};
+                                    set_range_flag_dec_256_3_p16, set_range_flag_hifigan, set_range_flag_hifigan_amp, set_range_flag_train, set_range_flag_convgemm_bf16};
     for (auto set : setters)
         if (int rc = set(reinterpret_cast<int*>(a->range_flag))) return rc;
     int rc = forward_impl(a, ctl, precision, stage, stream);

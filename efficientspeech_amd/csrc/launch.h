@@ -81,6 +81,13 @@ inline ConvGemmP conv_transpose1d(int B, int n_in, int n_out, int c_in, int c_ou
     p.n_out = n_out; p.mode = MODE_CONVT; p.k = k; p.stride = stride; p.pad = pad;
     return p;
 }
+// tu_convgemm_bf16.hip: the three GEMM families with bfloat16 operands (ConvGemmP::amp == 2, the training step's bf16-mixed precision).
+// launch_convgemm decides the family, the tiling and the grid exactly as for the other precisions and hands them over
+int launch_convgemm_stream_bf16(const ConvGemmP& p, int nt, dim3 grid, hipStream_t st);
+#if ESMI_CHAIN_SPLIT
+int launch_pwgemm_bf16(const ConvGemmP& p, bool full_row, dim3 grid, int n_items, hipStream_t st);
+int launch_convgemm_dma_bf16(const ConvGemmP& p, bool wide, int mt, dim3 grid, int lds_bytes, int nx, int ny, hipStream_t st);
+#endif
 // tu_attention.hip
 int launch_attn(const AttnP& p, hipStream_t st);
 // tu_enc_merge.hip / tu_enc_block.hip / tu_enc_attn_ffn.hip / tu_enc_fuse_va.hip (rounds 1-4: the 32-row wave-chain kernels).  Every
@@ -122,6 +129,7 @@ inline bool enc_attn_ffn_supported(int C, int N, int expansion) {
 // calls them all.
 int set_range_flag_abi(int* flag);
 int set_range_flag_convgemm(int* flag);
+int set_range_flag_convgemm_bf16(int* flag);
 int set_range_flag_attention(int* flag);
 int set_range_flag_enc_merge(int* flag);
 int set_range_flag_enc_block(int* flag);

@@ -14,7 +14,7 @@
 // convgemm.h's (bias, activation, residual, LayerNorm, row mask, the data gradient's power-of-two scale).
 //
 // KS = c_in / 16 (5: the mel Linear's data gradient, 8: the 128-channel layers), up to 128 output channels (NT = 4 column tiles).
-// AMP: `precision = 16` -- both operands rounded to binary16, one product.
+// AMP: `precision = 16` -- both operands rounded to binary16, one product; pwgemm_bf16_kernel: the same in bfloat16, nothing scaled.
 #pragma once
 #include "convgemm.h"
 
@@ -25,8 +25,10 @@ constexpr int kPwWaves = 8;
 template <int KS>
 __host__ __device__ constexpr int pwgemm_lds_bytes() { return KS * 4 * 2 * 64 * 16; }
 
-template <int KS, int NT, bool AMP>   // NT = 2: a wave's item is (32 rows, 64 columns); NT = 4: (32 rows, all columns) -- LayerNorm / row-dot epilogues
-__global__ __launch_bounds__(64 * kPwWaves) void pwgemm_kernel(const ConvGemmP p, int n_items) {
+// the body: OPK (convgemm.h GemmOperand) is how the operands are formed
+template <int KS, int NT, int OPK>    // NT = 2: a wave's item is (32 rows, 64 columns); NT = 4: (32 rows, all columns) -- LayerNorm / row-dot epilogues
+__device__ __forceinline__ void pwgemm_body(const ConvGemmP& p, int n_items) {
+    constexpr bool AMP = OPK != OPK_SPLIT;            // one operand piece, one product
     constexpr int NTW = 4, NH = NTW / NT;             // column tiles of the staged weight; items per row tile
     ESMI_DYN_LDS(lds);
     u32x4* wl = reinterpret_cast<u32x4*>(lds);        // [st][nt][plane][lane]
@@ -84,16 +86,21 @@ __global__ __launch_bounds__(64 * kPwWaves) void pwgemm_kernel(const ConvGemmP p
         for (int u = 0; u < NI; ++u) {
             const int q = tid + 64 * kPwWaves * u, n = q / (2 * KS), pc = q % (2 * KS), st = pc >> 1, hh = pc & 1;
             if (q >= NQ) continue;
-            const f32x4 y0 = x0[u] * kF16WScale, y1 = x1[u] * kF16WScale;
-            u32x4 h1, h2;
-            unsigned a, b;
-            split_f16_pair_rn(y0[0], y0[1], a, b); h1[0] = a; h2[0] = b;   // weights: nearest-rounded pieces, as the pack-time splitters
-            split_f16_pair_rn(y0[2], y0[3], a, b); h1[1] = a; h2[1] = b;
-            split_f16_pair_rn(y1[0], y1[1], a, b); h1[2] = a; h2[2] = b;
-            split_f16_pair_rn(y1[2], y1[3], a, b); h1[3] = a; h2[3] = b;
-            const int f = st * NTW + (n >> 5), slot = 32 * hh + ((n + st + 8 * hh) & 31);
-            wl[(f * 2 + 0) * 64 + slot] = h1;
-            wl[(f * 2 + 1) * 64 + slot] = h2;
+            if constexpr (OPK == OPK_BF16) {               // one bfloat16 plane of W as it is
+                const int f = st * NTW + (n >> 5), slot = 32 * hh + ((n + st + 8 * hh) & 31);
+                wl[(f * 2 + 0) * 64 + slot] = round_bf16x8(x0[u], x1[u]);
+            } else {
+                const f32x4 y0 = x0[u] * kF16WScale, y1 = x1[u] * kF16WScale;
+                u32x4 h1, h2;
+                unsigned a, b;
+                split_f16_pair_rn(y0[0], y0[1], a, b); h1[0] = a; h2[0] = b;   // weights: nearest-rounded pieces, as the pack-time splitters
+                split_f16_pair_rn(y0[2], y0[3], a, b); h1[1] = a; h2[1] = b;
+                split_f16_pair_rn(y1[0], y1[1], a, b); h1[2] = a; h2[2] = b;
+                split_f16_pair_rn(y1[2], y1[3], a, b); h1[3] = a; h2[3] = b;
+                const int f = st * NTW + (n >> 5), slot = 32 * hh + ((n + st + 8 * hh) & 31);
+                wl[(f * 2 + 0) * 64 + slot] = h1;
+                wl[(f * 2 + 1) * 64 + slot] = h2;
+            }
         }
     }
     ESMI_PT();   // weight written
@@ -106,7 +113,8 @@ __global__ __launch_bounds__(64 * kPwWaves) void pwgemm_kernel(const ConvGemmP p
 #pragma unroll
         for (int st = 0; st < KS; ++st) {
             const f32x4 lo = nxt[st][0] * in_s, hi = nxt[st][1] * in_s;   // (in_s: the data gradient's power of two, else 1 -- exact)
-            if constexpr (AMP) a[st].h1 = round_f16x8(lo, hi);
+            if constexpr (OPK == OPK_BF16) a[st].h1 = round_bf16x8(lo, hi);
+            else if constexpr (AMP) a[st].h1 = round_f16x8(lo, hi);
             else a[st] = split_f16x2(lo, hi);
         }
         sched_fence();
@@ -137,7 +145,10 @@ __global__ __launch_bounds__(64 * kPwWaves) void pwgemm_kernel(const ConvGemmP p
             const int st = g / (NT / 2), np = g % (NT / 2);
             if constexpr (AMP) {
 #pragma unroll
-                for (int q = 0; q < 2; ++q) acc[2 * np + q] = mfma32_f16(a[st].h1, bf[g & 1][q][0], acc[2 * np + q]);
+                for (int q = 0; q < 2; ++q) {
+                    if constexpr (OPK == OPK_BF16) acc[2 * np + q] = mfma32_bf16(a[st].h1, bf[g & 1][q][0], acc[2 * np + q]);
+                    else acc[2 * np + q] = mfma32_f16(a[st].h1, bf[g & 1][q][0], acc[2 * np + q]);
+                }
             } else {
                 // the three products of a tile are a dependent chain on its accumulator: run the two chains side by side
 #pragma unroll
@@ -151,10 +162,15 @@ __global__ __launch_bounds__(64 * kPwWaves) void pwgemm_kernel(const ConvGemmP p
             sched_fence();
         }
         ESMI_PT();   // products issued
-        convgemm_epilogue<NT>(acc, p, 0, (item / NH) * 32, 32 * cn, lane, 1, (int)n_rows);
+        convgemm_epilogue<NT, OPK != OPK_BF16>(acc, p, 0, (item / NH) * 32, 32 * cn, lane, 1, (int)n_rows);
         ESMI_PT();   // epilogue issued
     }
 }
+template <int KS, int NT, bool AMP>
+__global__ __launch_bounds__(64 * kPwWaves) void pwgemm_kernel(const ConvGemmP p, int n_items) { pwgemm_body<KS, NT, AMP ? OPK_F16 : OPK_SPLIT>(p, n_items); }
+// ... with bfloat16 operands (ConvGemmP::amp == 2)
+template <int KS, int NT>
+__global__ __launch_bounds__(64 * kPwWaves) void pwgemm_bf16_kernel(const ConvGemmP p, int n_items) { pwgemm_body<KS, NT, OPK_BF16>(p, n_items); }
 #undef ESMI_PT
 #endif
 

@@ -30,6 +30,9 @@ int launch_convgemm(ConvGemmP p, hipStream_t st) {
     if (p.ids) {
         if (!p.table || (p.ld_table & 3) || !aligned16(p.table)) return ESMI_ERR_ARG;
     } else if (!p.A || (p.lda & 3) || (p.a_coff & 3) || !aligned16(p.A)) return ESMI_ERR_ARG;
+    // bf16-mixed (ConvGemmP::amp == 2): the weights are rounded as stored -- there is no bfloat16 blob -- and nothing is scaled
+    const bool bf16 = p.amp == 2;
+    if (bf16 && (!p.W || p.io_scale)) return ESMI_ERR_ARG;
     const bool full_row = p.ln_g || p.dot_out;
     if (p.c_out == 1 && p.mode == MODE_CONV && p.stride == 1 && !p.ids && !full_row && !p.res && !p.rowmask && p.out && !p.len) {
         const long n = (long)p.B * p.n_out;
@@ -39,7 +42,7 @@ int launch_convgemm(ConvGemmP p, hipStream_t st) {
     if (p.len) {
         // per-utterance lengths (HiFi-GAN stages of a length-aware call): the streaming kernel's tiles never span utterances, so the
         // limit is one scalar per wave; the LDS-staged kernels below tile flat rows across utterances and do not take it
-        if (full_row || p.ids || p.rowmask || p.io_scale || p.len_mul < 1 || p.len_add < 0 ||
+        if (bf16 || full_row || p.ids || p.rowmask || p.io_scale || p.len_mul < 1 || p.len_add < 0 ||
             p.c_out > 64 || (p.mode == MODE_CONV && (p.stride != 1 || p.n_in != p.n_out)))   // (c_out <= 64: what the generator limits)
             return ESMI_ERR_UNSUPPORTED;
         const int nt = p.c_out > 32 ? 2 : 1;
@@ -79,6 +82,7 @@ int launch_convgemm(ConvGemmP p, hipStream_t st) {
         // when the epilogue needs whole rows in one wave
         const int nh = full_row ? 1 : 2, n_items = (int)((rows + 31) / 32) * nh, want = (n_items + kPwWaves - 1) / kPwWaves;
         const dim3 grid((unsigned)(want < 256 ? want : 256));
+        if (bf16) return launch_pwgemm_bf16(p, full_row, grid, n_items, st);
 #define ESMI_PW_CASE(KS_, NT_, AMP_) ESMI_LAUNCH_LDS((pwgemm_kernel<KS_, NT_, AMP_>), grid, dim3(64 * kPwWaves), pwgemm_lds_bytes<KS_>(), st, p, n_items)
         const int variant = (p.c_in == 128 ? 0 : 4) + (full_row ? 2 : 0) + (p.amp ? 1 : 0);
         switch (variant) {
@@ -112,8 +116,9 @@ int launch_convgemm(ConvGemmP p, hipStream_t st) {
         const long wr = 32 * mt * NWV;
         const int nx = (int)((rows + wr - 1) / wr);
         dim3 g1((unsigned)((nx + 7) / 8 * 8 * ny));
-        const bool pre = p.Wp != nullptr && aligned16(p.Wp);
+        const bool pre = !bf16 && p.Wp != nullptr && aligned16(p.Wp);
         const int lds_bytes = wide ? convgemm_dma_bytes<8>(1, p.k, p.dil, pre) : convgemm_dma_bytes<4>(mt, p.k, p.dil, pre);
+        if (bf16) return launch_convgemm_dma_bf16(p, wide, mt, g1, lds_bytes, nx, ny, st);
 #define ESMI_DMA_CASE(NT_, MT_, AMP_, PRE_) \
     ESMI_LAUNCH_LDS((convgemm_dma_kernel<NT_, MT_, NWV, AMP_, PRE_>), g1, dim3(64 * NWV), lds_bytes, st, p, nx, ny)
         const int variant = (wide ? 8 : (mt == 2 ? 4 : 0)) + (p.amp ? 2 : 0) + (pre ? 1 : 0);
@@ -138,6 +143,7 @@ int launch_convgemm(ConvGemmP p, hipStream_t st) {
     const int tiles = p.B * convgemm_tiles_per_phase(p) * convgemm_row_stride(p);
     dim3 grid((tiles + 3) / 4, full_row ? 1 : (p.c_out + 32 * nt - 1) / (32 * nt));
     dim3 block(256);
+    if (bf16) return launch_convgemm_stream_bf16(p, nt, grid, st);
     if (!p.amp) {
         switch (nt) {
             case 1: ESMI_LAUNCH((convgemm_kernel<1, false>), grid, block, 0, st, p); break;

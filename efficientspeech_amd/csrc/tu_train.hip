@@ -12,7 +12,7 @@ extern "C" {
 // ------------------------------------------------------------------ training step (csrc/train_ops.h)
 namespace {
 int conv_desc_ok(const esmi_conv_desc* d, ConvDesc* o) {
-    if (d && d->precision != 0 && d->precision != 16 && d->precision != 32) return ESMI_ERR_ARG;
+    if (d && d->precision != 0 && d->precision != 16 && d->precision != 32 && d->precision != ESMI_PRECISION_BF16) return ESMI_ERR_ARG;
     if (!d || d->B <= 0 || d->n_in <= 0 || d->n_out <= 0 || d->c_in <= 0 || d->c_out <= 0 || d->k <= 0 || d->stride <= 0 || d->pad < 0 ||
         d->groups <= 0)
         return ESMI_ERR_ARG;
@@ -161,17 +161,19 @@ int measure_absmax(const ConvDesc& c, const float* dy, int* amax, hipStream_t st
     ESMI_LAUNCH(absmax_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, st, dy, len, amax);
     return launch_status();
 }
+// ConvGemmP::amp of a descriptor's GEMMs: 0 fp32-accurate, 1 binary16 operands, 2 bfloat16 operands
+inline int gemm_amp(const esmi_conv_desc* d) { return d->precision == 16 ? 1 : d->precision == ESMI_PRECISION_BF16 ? 2 : 0; }
 struct ConvLnArgs { const float *res, *g, *b; const unsigned char* rowmask; int relu_out; float *pre, *mean, *rstd; };
 // one of the two implicit-GEMM problems of a dense conv.  wg: the weight as the GEMM reads it; io_scale (data gradient): the slot max|dy| sits in
 int launch_conv_gemm(const ConvDesc& c, const GemmWeight& g, bool grad, const float* in, const float* wg, const float* bias, float* out,
-                     bool amp, const int* io_scale, int act, const ConvLnArgs* ln, hipStream_t st) {
+                     int amp, const int* io_scale, int act, const ConvLnArgs* ln, hipStream_t st) {
     ConvGemmP p = conv_defaults();
-    p.io_scale = reinterpret_cast<const float*>(io_scale);
+    p.io_scale = amp == 2 ? nullptr : reinterpret_cast<const float*>(io_scale);   // (bfloat16 has fp32's exponent range: nothing to scale)
     p.mode = (g.as_convT && !g.flipped) ? MODE_CONVT : MODE_CONV;
     p.k = c.k; p.stride = c.stride; p.pad = g.flipped ? c.k - 1 - c.pad : c.pad;
     p.B = c.B; p.n_in = grad ? c.n_out : c.n_in; p.n_out = grad ? c.n_in : c.n_out; p.c_in = g.cin; p.c_out = g.cout;
     p.A = in; p.lda = g.cin; p.W = wg; p.bias = bias; p.out = out; p.ldo = g.cout;
-    p.amp = amp ? 1 : 0;
+    p.amp = amp;
     p.act = act;
     p.pw_ok = 1;
     if (ln) {   // act(conv + bias) + res -> LayerNorm (+ ReLU, + row mask) in the GEMM's epilogue; the pre-norm tensor, mean, rstd kept
@@ -181,7 +183,7 @@ int launch_conv_gemm(const ConvDesc& c, const GemmWeight& g, bool grad, const fl
     }
     return launch_convgemm(p, st);
 }
-// one direction on its own: pack unless the step already did -> (data gradient) max|dy| -> GEMM.  ESMI_ERR_UNSUPPORTED when the GEMM
+// one direction on its own: pack unless the step already did -> (data gradient, not under bf16) max|dy| -> GEMM.  ESMI_ERR_UNSUPPORTED when the GEMM
 // does not take the shape or there is no room for the weight's copy.
 int conv_gemm(const esmi_conv_desc* d, const ConvDesc& c, bool grad, const float* in, const float* w, const float* bias, float* out,
               WeightCopy wc, hipStream_t st, const ConvLnArgs* ln = nullptr) {
@@ -192,10 +194,11 @@ int conv_gemm(const esmi_conv_desc* d, const ConvDesc& c, bool grad, const float
     if (ln && g.cout != 32 && g.cout != 64 && g.cout != 128) return ESMI_ERR_UNSUPPORTED;
     if (g.copy && !wc.packed)
         if (int rc = pack_weight(c, g, grad, w, wc.wt, st)) return rc;
-    int* amax = grad ? absmax_slot(wc.wt, c) : nullptr;
-    if (grad)
+    const int amp = gemm_amp(d);
+    int* amax = (grad && amp != 2) ? absmax_slot(wc.wt, c) : nullptr;
+    if (amax)
         if (int rc = measure_absmax(c, in, amax, st)) return rc;
-    return launch_conv_gemm(c, g, grad, in, g.copy ? wc.wt : w, bias, out, d->precision == 16, amax, grad ? 0 : d->act, ln, st);
+    return launch_conv_gemm(c, g, grad, in, g.copy ? wc.wt : w, bias, out, amp, amax, grad ? 0 : d->act, ln, st);
 }
 }  // namespace
 
@@ -315,12 +318,13 @@ int esmi_train_conv_bwd_f32(const esmi_conv_desc* d, const float* x, const float
     const GemmWeight g = gemm_weight(c, true);
     if (gemm_bytes > 0 && p.mfma && g.ok) {
         // dense shapes whose two gradients both run on the matrix pipe: tap-major weight copy (zeroes the absmax slot) -> weight gradient
-        // (leaves max|dy| in the slot) -> its reduction -> data-gradient GEMM scaled by it
-        int* amax = absmax_slot(wc.wt, c);
+        // (leaves max|dy| in the slot) -> its reduction -> data-gradient GEMM scaled by it (bf16: no max, no scale)
+        const int amp = gemm_amp(d);
+        int* amax = amp == 2 ? nullptr : absmax_slot(wc.wt, c);
         if (!wc.packed)
             if (int rc = pack_weight(c, g, true, w, wc.wt, S(stream))) return rc;
         if (int rc = conv_wgrad(c, p, x, dy, dw, dbias, part, amax, defer, S(stream))) return rc;
-        return launch_conv_gemm(c, g, true, dy, wc.wt, nullptr, dx, d->precision == 16, amax, 0, nullptr, S(stream));
+        return launch_conv_gemm(c, g, true, dy, wc.wt, nullptr, dx, amp, amax, 0, nullptr, S(stream));
     }
     if (c.c_out == 1 && c.k == 1 && c.stride == 1 && c.pad == 0 && c.groups == 1 && !c.transposed && c.n_in == c.n_out && p.chunk <= 64) {
         // a Linear down to one channel: the three gradients in one launch (train_ops.h train_lin1_bwd_kernel); its partial rows are

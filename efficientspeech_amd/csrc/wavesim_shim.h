@@ -173,6 +173,33 @@ __device__ __forceinline__ u32x4 round_f16x8(const f32x4& x0, const f32x4& x1) {
     }
     return o;
 }
+// two values rounded to bfloat16 (nearest even), a in the low half: v_cvt_pk_bf16_f32 on gfx950.  NaN stays NaN (quiet), +-inf stays
+// +-inf; a finite value above the largest bfloat16 rounds to inf, as torch.Tensor.bfloat16() has it.  No range note: bfloat16 has
+// fp32's exponent range
+__device__ __forceinline__ unsigned round_bf16_pair(float a, float b) {
+#ifdef ESMI_WAVESIM
+    auto rne = [](float x) -> unsigned {
+        const unsigned u = __builtin_bit_cast(unsigned, x);
+        if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x40u;   // NaN: keep it one (set the quiet bit)
+        return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+    };
+    return rne(a) | (rne(b) << 16);
+#else
+    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+    const bf16x2_t h = {(__bf16)a, (__bf16)b};
+    return __builtin_bit_cast(unsigned, h);
+#endif
+}
+// 8 consecutive k of one row rounded to bfloat16 (nearest even), in the k-slot order of round_f16x8: the single-piece operand of the
+// bf16-mixed training GEMMs (ESMI_PRECISION_BF16)
+__device__ __forceinline__ u32x4 round_bf16x8(const f32x4& x0, const f32x4& x1) {
+    u32x4 o;
+    o[0] = round_bf16_pair(x0[0], x0[1]);
+    o[1] = round_bf16_pair(x0[2], x0[3]);
+    o[2] = round_bf16_pair(x1[0], x1[1]);
+    o[3] = round_bf16_pair(x1[2], x1[3]);
+    return o;
+}
 __device__ __forceinline__ f32x16 mfma32_f16(const u32x4& a, const u32x4& b, f32x16 c) {
 #ifdef ESMI_WAVESIM
     return wavesim::mfma_32x32x16_f16(a, b, c);

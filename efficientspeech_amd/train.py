@@ -34,8 +34,8 @@ def _new(shape, like, dtype=torch.float32):
 @dataclasses.dataclass
 class _Step:
     """What a running `TrainStep` tells the operators; `TrainStep._fwd_bwd` turns the last three on as the step gets there."""
-    precision: int                  # 16: the reference's `--precision 16` -- the dense GEMMs (forward, data gradient) round their operands to
-    #                                 binary16 (one MFMA product instead of three)
+    precision: object               # 16: the reference's `--precision 16` -- the dense GEMMs (forward, data gradient) round their operands to
+    #                                 binary16 (one MFMA product instead of three); "bf16": `--precision bf16-mixed`, the same in bfloat16
     loss_seed: object               # what the backward is seeded with: False = 1, else the device scalar (the loss scale) -- the loss kernel
     #                                 writes its gradients already multiplied by it and `_Loss.backward` passes them on as they are
     packed_valid: bool = False      # once the step's pack launch has been enqueued: `param._esmi_packed` holds this step's GEMM copies
@@ -83,13 +83,27 @@ def _grad_buffer(param):
 
 
 # --------------------------------------------------------------------------- what _Conv, _LayerNorm and _ConvLN are made of
+_DESC_PRECISION = {16: 16, "bf16": _lib.PRECISION_BF16}     # `_Step.precision` -> esmi_conv_desc.precision (everything else: fp32-accurate)
+
+
+def normalize_precision(precision):
+    """32, 16 or "bf16" from what the reference's `--precision` takes for them: "bf16-mixed" (Lightning's spelling), "16-mixed",
+    "32-true", and the numbers as strings."""
+    names = {"32": 32, "32-true": 32, "16": 16, "16-mixed": 16, "bf16": "bf16", "bf16-mixed": "bf16"}
+    if isinstance(precision, str) and precision in names:
+        return names[precision]
+    if precision in (16, 32) and not isinstance(precision, bool):
+        return int(precision)
+    raise ValueError(f"precision must be 32, 16 or 'bf16' ('bf16-mixed'), got {precision!r}")
+
+
 def _conv_desc(lib, x, w0, w, n_out, stride, pad, groups, transposed, act):
     """-> (d, ws, nws): the `ConvDesc` of a convolution of x (B, n_in, Cin) by the Parameter `w0` (`w`: contiguous) and what its forward
     GEMM copies the weight into -- this step's packed copies (made by TrainStep's one pack launch) in `d`, else the workspace `ws`."""
     B, n_in, c_in = x.shape
     w3 = w if w.dim() == 3 else w.unsqueeze(-1)
     c_out, k = (w3.shape[1] if transposed else w3.shape[0]), w3.shape[2]
-    precision = 16 if (_STEP is not None and _STEP.precision == 16) else 0
+    precision = _DESC_PRECISION.get(_STEP.precision, 0) if _STEP is not None else 0
     d = _lib.ConvDesc(B, n_in, c_in, n_out, c_out, k, stride, pad, groups, 1 if transposed else 0, precision, act)
     packed = getattr(w0, "_esmi_packed", None) if (USE_MATRIX_PIPE and _STEP is not None and _STEP.packed_valid) else None
     if packed is not None:
@@ -649,7 +663,9 @@ class TrainStep:
         # (binary16 operands, fp32 accumulate, fp32 master weights) + torch.amp.GradScaler's dynamic loss scaling: the backward
         # is seeded with `scale`, a step whose gradients hold inf / nan is skipped and halves the scale, `growth_interval` clean
         # steps in a row double it.  `skipped` counts the skipped steps (they do not advance the optimizer's step count).
-        assert precision in (16, 32), precision
+        # precision "bf16" ("bf16-mixed") = autocast-class GEMMs with bfloat16 operands.  bfloat16 has fp32's exponent range, so there
+        # is no scaler: the backward is seeded with 1, no step is skipped, and everything else runs as at precision 32.
+        precision = normalize_precision(precision)
         self.precision = precision
         self.graph = bool(graph)
         dev = self.flat.data.device

@@ -34,7 +34,7 @@ extern "C" {
 
 #define ESMI_VERSION 501 /* 0.5.1: esmi_train_conv_ln_fwd_f32, then esmi_hifigan_generator_ragged_f32, then esmi_prosody_control and the three
                             *_ctl_f32 entry points, then esmi_hifigan_generator_prec_f32, then esmi_mel_decoder_prec_f32 and
-                            esmi_phoneme2mel_forward_prec_f32, then esmi_prosody_curves and the three *_curve_f32 entry points (additions; nothing else changed shape).  0.5.0 (round 5): esmi_mel_decoder_clock_probe;
+                            esmi_phoneme2mel_forward_prec_f32, then esmi_prosody_curves and the three *_curve_f32 entry points, then ESMI_PRECISION_BF16 as a value of esmi_conv_desc.precision (additions; nothing else changed shape).  0.5.0 (round 5): esmi_mel_decoder_clock_probe;
                             0.4.0: esmi_decoder_head.proj_w (the decoder's first stage at phoneme rate for every model size:
                           * esmi_decoder_head_f32).  0.3.0: training entry points changed shape (esmi_conv_desc: act / packed_fwd / packed_grad; LayerNorm with
                           * residual / row mask / activation arguments; esmi_train_loss_args.grad_seed; esmi_train_pack_weights_f32,
@@ -660,13 +660,22 @@ int esmi_mask_rows_f32(float* x, const uint8_t* mask, int64_t rows, int C, esmi_
  * ConvTranspose1d (Cin, Cout, k), Linear (Cout, Cin) = a conv with k = 1.  First correct version: one thread per output
  * element, fp32 FMA loops, no atomics (a step is bitwise reproducible); see csrc/train_ops.h.  The Python side
  * (efficientspeech_amd/train.py) composes them with torch.autograd as the tape. */
+#define ESMI_PRECISION_BF16 0xB16 /* esmi_conv_desc.precision: bf16-mixed (below) */
 typedef struct esmi_conv_desc {
     int B, n_in, c_in, n_out, c_out, k, stride, pad;
     int groups;       /* 1, or c_in == c_out == groups (depthwise, MelDecoder networks.py:275) */
     int transposed;   /* 1: nn.ConvTranspose1d (Fuse, networks.py:185), groups must be 1 */
     int precision;    /* 0 / 32: fp32-accurate contractions.  16: the reference's `--precision 16` (utils/tools.py:326-327, Lightning ->
                        * torch.autocast): the forward and data-gradient GEMMs round both operands to binary16 and run ONE MFMA product
-                       * per 16 channels (fp32 accumulate, fp32 tensors in memory, fp32 master weights); weight gradients stay fp32 */
+                       * per 16 channels (fp32 accumulate, fp32 tensors in memory, fp32 master weights); weight gradients stay fp32.
+                       * ESMI_PRECISION_BF16: the reference's `--precision bf16-mixed` (torch.autocast with bfloat16) -- the same GEMMs
+                       * round both operands to bfloat16 (nearest even: `x.bfloat16()`, `w.bfloat16()`, `dy.bfloat16()`; NaN stays NaN,
+                       * +-inf stays +-inf) and run ONE v_mfma_f32_32x32x16_bf16 per 16 channels, fp32 accumulate.  bfloat16 has fp32's
+                       * exponent range, so nothing is scaled: no 2^8 on the weights, no power-of-two operand scale on the data
+                       * gradient (no max|dy| pass), and the caller needs no loss scaler.  Everything precision 16 leaves alone
+                       * (weight and bias gradients, depthwise, one-channel convolutions, everything that is no GEMM) is left alone
+                       * here too, and libesmi_fp32mfma.so answers as it does for 16 (its exact-fp32 products).  Any other value:
+                       * ESMI_ERR_ARG, nothing launched */
     int act;          /* forward only: 0, or 1 ReLU / 2 GELU (erf) / 3 tanh applied to the result (in the GEMM's epilogue when the shape runs
                        * on the matrix pipe, else as a second launch); the backward entry points ignore it -- the caller applies
                        * esmi_train_act_bwd_f32 to dy first (ReLU / tanh from the saved OUTPUT) */
@@ -682,7 +691,8 @@ typedef struct esmi_conv_desc {
 size_t esmi_train_conv_workspace_bytes(const esmi_conv_desc* d);
 /* the GEMM copies of n weights in ONE launch (per 64): descs[i].packed_fwd / packed_grad (each may be NULL) <- weights[i] in the layout
  * the forward / data-gradient GEMM of descs[i] reads; also clears the operand-scale slot behind each data-gradient copy.  Only the
- * channel / tap / stride / padding / transposed fields of a descriptor matter here.  Call it once per step, before the forward. */
+ * channel / tap / stride / padding / transposed fields of a descriptor matter here -- `precision` does not: the copies are fp32 at every
+ * precision, and the binary16 / bfloat16 GEMMs round them as they stage them.  Call it once per step, before the forward. */
 int esmi_train_pack_weights_f32(const esmi_conv_desc* descs, const float* const* weights, int n, esmi_stream_t stream);
 int esmi_train_conv_fwd_f32(const esmi_conv_desc* d, const float* x, const float* w, const float* bias /* or NULL */, float* y,
                             void* workspace, size_t workspace_bytes, esmi_stream_t stream);

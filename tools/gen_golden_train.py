@@ -5,7 +5,7 @@ The reference's Phoneme2Mel (train=True) on the seeded synthetic weights and a s
 loss arithmetic (model.py:167-209: masked L1 on mel, masked MSE on pitch / energy / log(duration + 1), weights 10 / 2 / 2 / 1,
 model.py:216), torch autograd for the gradients and torch.optim.AdamW (model.py:279-283 with its lr / weight_decay defaults)
 for one update.  The fixture holds data only: inputs, the four losses, the total, every parameter's gradient, and the
-parameters after one optimizer step.   python tools/gen_golden_train.py
+parameters after one optimizer step.   python tools/gen_golden_train.py [--amp | --bf16]
 """
 import os
 import sys
@@ -94,12 +94,9 @@ def main():
         print(path, os.path.getsize(path), "bytes; losses", rec["losses"], "total", float(total), "params without grad:", nograd)
 
 
-def main_amp():
-    """The same step as the reference trains it by default: `--precision 16` (utils/tools.py:326-327) = Lightning's
-    torch.autocast(dtype=float16) around training_step + torch.amp.GradScaler around the optimizer (here on the CPU: the build
-    container has no GPU).  -> tests/golden/tiny_train_step_amp16.npz: losses, every gradient after GradScaler.unscale_, a sample
-    of the parameters after the scaled step, the scaler's scale."""
-    outdir = os.path.join(G.ROOT, "tests", "golden")
+def _amp_case():
+    """The tiny B = 2 step of the mixed-precision fixtures -> (net, sd, x, mel, rec): the reference network on the seeded weights, the
+    teacher-forced batch as tensors, and the fixture's input entries."""
     name, lens, T = "tiny", [13, 9], 13
     cfg = CONFIGS[name]
     net, sd = G.build_ref(cfg)
@@ -118,6 +115,23 @@ def main_amp():
     x = dict(phoneme=torch.from_numpy(ph), phoneme_mask=torch.from_numpy(m), pitch=torch.from_numpy(pitch),
              energy=torch.from_numpy(energy), duration=torch.from_numpy(dur).long(), mel_len=torch.from_numpy(mel_len),
              mel_mask=torch.from_numpy(mel_mask))
+    rec = dict(in_phoneme=ph, in_phoneme_mask=m, in_pitch=pitch, in_energy=energy, in_duration=dur, in_mel_len=mel_len, in_mel=mel,
+               in_mel_mask=mel_mask, weights_crc=np.array(G.sd_crc(sd), dtype=np.uint32))
+    return net, sd, x, torch.from_numpy(mel), rec
+
+
+# (file size: every gradient of at most 4,096 elements, and these six large ones)
+AMP_BIG = ("encoder.encoder.embed.weight", "encoder.encoder.attn_blocks.0.2.qkv.weight", "encoder.fuse.mlps.1.1.weight",
+           "encoder.duration_decoder.conv1.0.weight", "decoder.blocks.0.0.0.0.1.weight", "decoder.mel_linear.weight")
+
+
+def main_amp():
+    """The same step as the reference trains it by default: `--precision 16` (utils/tools.py:326-327) = Lightning's
+    torch.autocast(dtype=float16) around training_step + torch.amp.GradScaler around the optimizer (here on the CPU: the build
+    container has no GPU).  -> tests/golden/tiny_train_step_amp16.npz: losses, every gradient after GradScaler.unscale_, a sample
+    of the parameters after the scaled step, the scaler's scale."""
+    outdir = os.path.join(G.ROOT, "tests", "golden")
+    net, sd, x, mel, rec = _amp_case()
     params = [p for p in net.parameters() if p.requires_grad]
     opt = torch.optim.AdamW(params, lr=1e-3, weight_decay=1e-6)
     # GradScaler's default init_scale (65536) overflows binary16 in this step's backward: the reference skips five steps on this batch
@@ -126,17 +140,14 @@ def main_amp():
     opt.zero_grad()
     with torch.autocast("cpu", dtype=torch.float16):
         y_hat = net(x, train=True)
-        losses = reference_loss(y_hat, torch.from_numpy(mel), x)
+        losses = reference_loss(y_hat, mel, x)
         total = 10.0 * losses[0] + 2.0 * losses[1] + 2.0 * losses[2] + losses[3]
     scaler.scale(total).backward()
     scaler.unscale_(opt)
-    rec = dict(in_phoneme=ph, in_phoneme_mask=m, in_pitch=pitch, in_energy=energy, in_duration=dur, in_mel_len=mel_len, in_mel=mel,
-               in_mel_mask=mel_mask, losses=np.array([float(v) for v in losses], np.float64), total=np.array(float(total), np.float64),
-               weights_crc=np.array(G.sd_crc(sd), dtype=np.uint32), out_dtype=np.array(str(y_hat["mel"].dtype)))
-    big = ("encoder.encoder.embed.weight", "encoder.encoder.attn_blocks.0.2.qkv.weight", "encoder.fuse.mlps.1.1.weight",
-           "encoder.duration_decoder.conv1.0.weight", "decoder.blocks.0.0.0.0.1.weight", "decoder.mel_linear.weight")
+    rec.update(losses=np.array([float(v) for v in losses], np.float64), total=np.array(float(total), np.float64),
+               out_dtype=np.array(str(y_hat["mel"].dtype)))
     for k, p in net.named_parameters():
-        if p.requires_grad and p.grad is not None and (p.numel() <= 4096 or k in big):      # (file size: every small tensor, six large ones)
+        if p.requires_grad and p.grad is not None and (p.numel() <= 4096 or k in AMP_BIG):
             rec["grad." + k] = p.grad.float().numpy()
     scaler.step(opt)
     scaler.update()
@@ -149,8 +160,33 @@ def main_amp():
     print(path, os.path.getsize(path), "bytes; losses", rec["losses"], "total", float(total), "scale", float(scaler.get_scale()))
 
 
+def main_bf16():
+    """The same step under `--precision bf16-mixed` (README "Train": Lightning's torch.autocast(dtype=bfloat16) around
+    training_step; bfloat16 has fp32's exponent range, so Lightning uses no GradScaler and the backward is seeded with 1).
+    -> tests/golden/tiny_train_step_bf16.npz: losses, the total, the dtype of the mel output, the gradients main_amp keeps.  Data only."""
+    outdir = os.path.join(G.ROOT, "tests", "golden")
+    net, sd, x, mel, rec = _amp_case()
+    for p in net.parameters():
+        p.grad = None
+    with torch.autocast("cpu", dtype=torch.bfloat16):
+        y_hat = net(x, train=True)
+        losses = reference_loss(y_hat, mel, x)
+        total = 10.0 * losses[0] + 2.0 * losses[1] + 2.0 * losses[2] + losses[3]
+    total.backward()
+    rec.update(losses=np.array([float(v) for v in losses], np.float64), total=np.array(float(total), np.float64),
+               out_dtype=np.array(str(y_hat["mel"].dtype)))
+    for k, p in net.named_parameters():
+        if p.requires_grad and p.grad is not None and (p.numel() <= 4096 or k in AMP_BIG):
+            rec["grad." + k] = p.grad.float().numpy()
+    path = os.path.join(outdir, "tiny_train_step_bf16.npz")
+    np.savez_compressed(path, **rec)
+    print(path, os.path.getsize(path), "bytes; losses", rec["losses"], "total", float(total), "out dtype", y_hat["mel"].dtype)
+
+
 if __name__ == "__main__":
     if "--amp" in sys.argv:
         main_amp()
+    elif "--bf16" in sys.argv:
+        main_bf16()
     else:
         main()
