@@ -79,7 +79,28 @@ class HifiGanShape(C.Structure):
                 ("rb_kernels", C.c_int * HIFIGAN_MAX_KERNELS), ("rb_dilations", C.c_int * (HIFIGAN_MAX_KERNELS * 3))]
 
 
-PRECISION_BF16 = 0xB16      # ESMI_PRECISION_BF16 (include/esmi.h): esmi_conv_desc.precision of the bf16-mixed training GEMMs
+PRECISION_BF16 = 0xB16      # ESMI_PRECISION_BF16 (include/esmi.h): esmi_conv_desc.precision of the bf16-mixed training GEMMs, and the
+#                             `precision` argument of the inference entry points at bf16
+
+
+def normalize_precision(precision, what="precision", numeric_strings=True):
+    """32, 16 or "bf16" from what the reference's `--precision` takes for them: "bf16-mixed" (Lightning's spelling), "16-mixed",
+    "32-true", and the numbers as strings.  The one validator of the training step (`TrainStep(precision=)`) and of inference (the mel
+    decoder's and the vocoder's `precision`, the input-dict key `decoder_precision`): booleans and anything else are a ValueError.
+    `numeric_strings=False` (inference): "16" / "32" are refused too -- there the number itself has always been the spelling."""
+    names = {"32-true": 32, "16-mixed": 16, "bf16": "bf16", "bf16-mixed": "bf16"}
+    if numeric_strings:
+        names.update({"32": 32, "16": 16})
+    if isinstance(precision, str) and precision in names:
+        return names[precision]
+    if not isinstance(precision, (bool, str)) and precision in (16, 32):
+        return int(precision)
+    raise ValueError(f"{what} must be 32, 16 or 'bf16' ('bf16-mixed'), got {precision!r}")
+
+
+def precision_code(precision):
+    """a normalized precision (32, 16, "bf16") as the C entry points take it"""
+    return PRECISION_BF16 if precision == "bf16" else int(precision)
 
 
 class ConvDesc(C.Structure):

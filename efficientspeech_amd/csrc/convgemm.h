@@ -485,6 +485,9 @@ __global__ __launch_bounds__(256) void convgemm_len_kernel(const ConvGemmP p) { 
 // ... and with ConvGemmP::amp (the generator at precision 16)
 template <int NT>
 __global__ __launch_bounds__(256) void convgemm_len_amp_kernel(const ConvGemmP p) { convgemm_body<NT, true, true>(p); }
+// ... and with bfloat16 operands (ConvGemmP::amp == 2: the generator at bf16)
+template <int NT>
+__global__ __launch_bounds__(256) void convgemm_bf16_len_kernel(const ConvGemmP p) { convgemm_body<NT, OPK_BF16, true>(p); }
 
 
 // ---- a convolution down to ONE output channel (HiFi-GAN conv_post, hifigan/models.py:123-125: 8..32 channels -> 1, k = 7,

@@ -176,5 +176,10 @@ template <int DX2, int KD>
 int launch_mel_decoder_p16(const MelDecP& p, dim3 grid, hipStream_t st);
 template <int DX2, int KD>
 int set_dec_clock_p16(long long* slots);
+// ... and of the bf16 kernel (tu_dec_<dx2>_<k>_bf16.hip, ESMI_DEC_INSTANCE_BF16; split build only)
+template <int DX2, int KD>
+int launch_mel_decoder_bf16(const MelDecP& p, dim3 grid, hipStream_t st);
+template <int DX2, int KD>
+int set_dec_clock_bf16(long long* slots);
 
 }  // namespace esmi

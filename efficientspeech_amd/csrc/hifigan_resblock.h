@@ -423,8 +423,25 @@ __device__ __forceinline__ rb_u32x2 lrelu_round4(const f32x4& v, float slope) {
     return rb_u32x2{r[0], r[1]};
 }
 
-template <int C, int K>
-__global__ __launch_bounds__(64 * RbAmp<C>::kWaves, RbAmp<C>::kWps) void hifigan_resblock_amp_kernel(const ResblockP p) {
+// ... to bfloat16 (nearest even; no range to leave)
+__device__ __forceinline__ rb_u32x2 lrelu_round4_bf16(const f32x4& v, float slope) {
+    const f32x4 a = lrelu4(v, slope);
+    return rb_u32x2{round_bf16_pair(a[0], a[1]), round_bf16_pair(a[2], a[3])};
+}
+
+// ---- bf16 (include/esmi.h, "Inference at bf16"): the one-product kernels again with bfloat16 operands and nothing scaled.  BF = true in the
+// two bodies below: the activation plane holds nearest-even bfloat16; the weight operand is the nearest-even bfloat16 of (plane 0 + plane 1)
+// * 2^-8 of the same esmi_pack_resblock_f16 blob, formed in registers (bf16_of_f16_planes) when a fetched fragment is first used; the
+// accumulators hold products with W itself, so the epilogue's scale is 1.  LDS plane, window (rb_amp_rmax), waves and `len` handling are
+// those of precision 16.
+template <int C, int K, bool BF>
+__device__ __forceinline__ void hifigan_resblock_amp_body(const ResblockP& p) {
+    constexpr int NWP = BF ? 2 : 1;               // weight planes fetched per k-step
+    constexpr float WSI = BF ? 1.0f : kF16WScaleInv;
+    auto round4 = [&](const f32x4& v) __attribute__((always_inline)) {
+        if constexpr (BF) return lrelu_round4_bf16(v, p.slope);
+        else return lrelu_round4(v, p.slope);
+    };
     constexpr int RS = rb_row_bytes(C), MT = rb_mtiles(C), CG = (C < 32 ? C : 32) / 8;
     constexpr int STEPS = rb_ksteps(C, K), HALF = (K - 1) / 2, PD = kRbPd < STEPS ? kRbPd : STEPS;
     static_assert(STEPS >= PD, "prefetch distance reaches at most into the next conv");
@@ -446,10 +463,12 @@ __global__ __launch_bounds__(64 * RbAmp<C>::kWaves, RbAmp<C>::kWps) void hifigan
         *reinterpret_cast<rb_u32x2*>(lds + row * RS + ch * 2) = v;
     };
     // weight fragment (the blob's first plane) of flattened step index s (s >= STEPS: the next conv's first steps; past the last conv: nothing)
-    auto wfetch = [&](int ci, int s, u32x4& hi) __attribute__((always_inline)) {
+    auto wfetch = [&](int ci, int s, u32x4 (&hi)[NWP]) __attribute__((always_inline)) {
         if (s >= STEPS) { ++ci; s -= STEPS; }
-        if (ci < p.n_conv && (C >= 32 || i < C))     // rows past C are the zero padding of the M tile: those lanes keep their zeros
-            hi = *reinterpret_cast<const u32x4*>(p.conv[ci].wp + wlane + (long)s * 512);
+        if (ci < p.n_conv && (C >= 32 || i < C)) {   // rows past C are the zero padding of the M tile: those lanes keep their zeros
+#pragma unroll
+            for (int pl = 0; pl < NWP; ++pl) hi[pl] = *reinterpret_cast<const u32x4*>(p.conv[ci].wp + wlane + (long)s * 512 + 256 * pl);
+        }
     };
     auto xfetch = [&](int s, int dil, u32x4 (&x)[2]) __attribute__((always_inline)) {
         const int kidx = 16 * s + 8 * h;
@@ -465,12 +484,16 @@ __global__ __launch_bounds__(64 * RbAmp<C>::kWaves, RbAmp<C>::kWps) void hifigan
         }
     };
 
-    u32x4 wq[PD];
+    u32x4 wq[PD][NWP];
 #pragma unroll
-    for (int q = 0; q < PD; ++q) wq[q] = u32x4{0, 0, 0, 0};
+    for (int q = 0; q < PD; ++q)
+#pragma unroll
+        for (int pl = 0; pl < NWP; ++pl) wq[q][pl] = u32x4{0, 0, 0, 0};
     if (active) {
+        if constexpr (!(BF && C == 64)) {
 #pragma unroll
-        for (int q = 0; q < PD; ++q) wfetch(0, q, wq[q]);
+            for (int q = 0; q < PD; ++q) wfetch(0, q, wq[q]);
+        }
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
             const int row = row0 + 32 * tt, pos = t0 + row;
@@ -479,7 +502,7 @@ __global__ __launch_bounds__(64 * RbAmp<C>::kWaves, RbAmp<C>::kWps) void hifigan
 #pragma unroll
             for (int g = 0; g < CG; ++g) {
                 xres[tt][g] = inside[tt] ? ld4(src + 8 * g) : zero4();
-                put_plane(row, 32 * mt + 8 * g + 4 * h, lrelu_round4(xres[tt][g], p.slope));
+                put_plane(row, 32 * mt + 8 * g + 4 * h, round4(xres[tt][g]));
             }
         }
     }
@@ -496,14 +519,28 @@ __global__ __launch_bounds__(64 * RbAmp<C>::kWaves, RbAmp<C>::kWps) void hifigan
             xfetch(0, dil, x[0]);
 #pragma unroll
             for (int s = 0; s < STEPS; ++s) {
-                const u32x4 wh = wq[s % PD];
-                u32x4 nh = wh;
-                wfetch(ci, s + PD, nh);                            // in flight under PD steps of MFMAs (and the epilogue)
+                u32x4 wh, nh[NWP];
+                if constexpr (BF && C == 64) {   // 16 waves at 128 VGPRs: no room for two raw planes in flight across the MFMAs -- fetched where
+                                                 // they are used (four waves per SIMD cover the L2 round trip); `wq` is unused
+                    u32x4 raw[NWP] = {u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}};
+                    wfetch(ci, s, raw);
+                    wh = bf16_of_f16_planes(raw[0], raw[1]);
+                } else if constexpr (BF) {   // the slot's two planes -> the step's operand; the slot is then free for the fetch (lanes that do not
+                                             // fetch keep its zeros)
+                    wh = bf16_of_f16_planes(wq[s % PD][0], wq[s % PD][1]);
+                    wfetch(ci, s + PD, wq[s % PD]);
+                } else {
+                    wh = nh[0] = wq[s % PD][0];
+                    wfetch(ci, s + PD, nh);                        // in flight under PD steps of MFMAs (and the epilogue)
+                }
                 if (XB == 2 && s + 1 < STEPS) xfetch(s + 1, dil, x[(s + 1) % XB]);
                 sched_fence();
 #pragma unroll
-                for (int tt = 0; tt < 2; ++tt) acc[tt] = mfma32_f16(wh, x[s % XB][tt], acc[tt]);
-                wq[s % PD] = nh;
+                for (int tt = 0; tt < 2; ++tt) {
+                    if constexpr (BF) acc[tt] = mfma32_bf16(wh, x[s % XB][tt], acc[tt]);
+                    else acc[tt] = mfma32_f16(wh, x[s % XB][tt], acc[tt]);
+                }
+                if constexpr (!BF) wq[s % PD][0] = nh[0];
                 if (XB == 1 && s + 1 < STEPS) xfetch(s + 1, dil, x[0]);
             }
             // bias, residual, zero outside the sequence; the last conv's result goes straight out
@@ -519,7 +556,7 @@ __global__ __launch_bounds__(64 * RbAmp<C>::kWaves, RbAmp<C>::kWps) void hifigan
                     const f32x4 bv = ld4(bias + 8 * g);
                     f32x4 v;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaf(acc[tt][4 * g + e], kF16WScaleInv, bv[e]);
+                    for (int e = 0; e < 4; ++e) v[e] = fmaf(acc[tt][4 * g + e], WSI, bv[e]);
                     if (add_res) v = v + xres[tt][g];
                     if (!inside[tt]) v = zero4();
                     if (last) {
@@ -529,7 +566,7 @@ __global__ __launch_bounds__(64 * RbAmp<C>::kWaves, RbAmp<C>::kWps) void hifigan
                         }
                     } else {
                         if (add_res) xres[tt][g] = v;
-                        pl[tt][g] = lrelu_round4(v, p.slope);
+                        pl[tt][g] = round4(v);
                     }
                 }
             }
@@ -545,11 +582,25 @@ __global__ __launch_bounds__(64 * RbAmp<C>::kWaves, RbAmp<C>::kWps) void hifigan
         __syncthreads();       // the new plane is complete
     }
 }
-
-// C <= 16 on v_mfma_f32_16x16x32_f16 tiles, one product
 template <int C, int K>
-__global__ __launch_bounds__(64 * kRbWaves, kRbWps) void hifigan_resblock16_amp_kernel(const ResblockP p) {
+__global__ __launch_bounds__(64 * RbAmp<C>::kWaves, RbAmp<C>::kWps) void hifigan_resblock_amp_kernel(const ResblockP p) {
+    hifigan_resblock_amp_body<C, K, false>(p);
+}
+template <int C, int K>
+__global__ __launch_bounds__(64 * RbAmp<C>::kWaves, RbAmp<C>::kWps) void hifigan_resblock_bf16_kernel(const ResblockP p) {
+    hifigan_resblock_amp_body<C, K, true>(p);
+}
+
+// C <= 16 on v_mfma_f32_16x16x32_f16 / _bf16 tiles, one product
+template <int C, int K, bool BF>
+__device__ __forceinline__ void hifigan_resblock16_amp_body(const ResblockP& p) {
     static_assert(C == 8 || C == 16, "narrow-tile kernel");
+    constexpr int NWP = BF ? 2 : 1;               // weight planes fetched per k-step
+    constexpr float WSI = BF ? 1.0f : kF16WScaleInv;
+    auto round4 = [&](const f32x4& v) __attribute__((always_inline)) {
+        if constexpr (BF) return lrelu_round4_bf16(v, p.slope);
+        else return lrelu_round4(v, p.slope);
+    };
     constexpr int RS = rb_row_bytes(C), STEPS = rb_ksteps16(C, K), HALF = (K - 1) / 2;
     ESMI_DYN_LDS(lds_f);
     char* lds = reinterpret_cast<char*>(lds_f);
@@ -566,16 +617,20 @@ __global__ __launch_bounds__(64 * kRbWaves, kRbWps) void hifigan_resblock16_amp_
     auto put_plane = [&](int row, const rb_u32x2& v) __attribute__((always_inline)) {
         *reinterpret_cast<rb_u32x2*>(lds + row * RS + 8 * kb) = v;
     };
-    u32x4 wf[STEPS];
+    u32x4 wf[STEPS][NWP];
     auto wfetch = [&](int ci) __attribute__((always_inline)) {
         if (ci < p.n_conv && n < C) {              // rows past C are zero padding: those lanes keep their zeros
             const unsigned* q = p.conv[ci].wp + lane * 4;
 #pragma unroll
-            for (int s = 0; s < STEPS; ++s) wf[s] = *reinterpret_cast<const u32x4*>(q + s * 512);   // the blob's first plane
+            for (int s = 0; s < STEPS; ++s)
+#pragma unroll
+                for (int pl = 0; pl < NWP; ++pl) wf[s][pl] = *reinterpret_cast<const u32x4*>(q + s * 512 + 256 * pl);   // precision 16: the blob's first plane
         }
     };
 #pragma unroll
-    for (int s = 0; s < STEPS; ++s) wf[s] = u32x4{0, 0, 0, 0};
+    for (int s = 0; s < STEPS; ++s)
+#pragma unroll
+        for (int pl = 0; pl < NWP; ++pl) wf[s][pl] = u32x4{0, 0, 0, 0};
     if (active) {
         wfetch(0);
 #pragma unroll
@@ -583,7 +638,7 @@ __global__ __launch_bounds__(64 * kRbWaves, kRbWps) void hifigan_resblock16_amp_
             const int row = row0 + 16 * nt, pos = t0 + row;
             inside[nt] = pos >= 0 && pos < n_eff;
             xres[nt] = (inside[nt] && chan_ok) ? ld4(p.x + ((long)b * p.n + pos) * C + 4 * kb) : zero4();
-            if (chan_ok) put_plane(row, lrelu_round4(xres[nt], p.slope));
+            if (chan_ok) put_plane(row, round4(xres[nt]));
         }
     }
     __syncthreads();
@@ -608,8 +663,14 @@ __global__ __launch_bounds__(64 * kRbWaves, kRbWps) void hifigan_resblock16_amp_
                     r = r < 0 ? 0 : (r >= p.R ? p.R - 1 : r);
                     x[nt] = *reinterpret_cast<const u32x4*>(lds + opaque_i(r * RS + ch * 2));
                 }
+                if constexpr (BF) {
+                    const u32x4 wb = bf16_of_f16_planes(wf[s][0], wf[s][1]);
 #pragma unroll
-                for (int nt = 0; nt < 4; ++nt) acc[nt] = mfma16_f16(wf[s], x[nt], acc[nt]);
+                    for (int nt = 0; nt < 4; ++nt) acc[nt] = mfma16_bf16(wb, x[nt], acc[nt]);
+                } else {
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) acc[nt] = mfma16_f16(wf[s][0], x[nt], acc[nt]);
+                }
             }
             wfetch(ci + 1);                        // under the epilogue and the two barriers
             const f32x4 bv = chan_ok ? ld4(p.conv[ci].bias + 4 * kb) : zero4();
@@ -619,7 +680,7 @@ __global__ __launch_bounds__(64 * kRbWaves, kRbWps) void hifigan_resblock16_amp_
                 const int row = row0 + 16 * nt;
                 f32x4 v;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaf(acc[nt][e], kF16WScaleInv, bv[e]);
+                for (int e = 0; e < 4; ++e) v[e] = fmaf(acc[nt][e], WSI, bv[e]);
                 if (add_res) v = v + xres[nt];
                 if (!inside[nt]) v = zero4();
                 if (last) {
@@ -630,7 +691,7 @@ __global__ __launch_bounds__(64 * kRbWaves, kRbWps) void hifigan_resblock16_amp_
                     }
                 } else {
                     if (add_res) xres[nt] = v;
-                    pl[nt] = lrelu_round4(v, p.slope);
+                    pl[nt] = round4(v);
                 }
             }
         }
@@ -642,6 +703,14 @@ __global__ __launch_bounds__(64 * kRbWaves, kRbWps) void hifigan_resblock16_amp_
         }
         __syncthreads();       // the new plane is complete
     }
+}
+template <int C, int K>
+__global__ __launch_bounds__(64 * kRbWaves, kRbWps) void hifigan_resblock16_amp_kernel(const ResblockP p) {
+    hifigan_resblock16_amp_body<C, K, false>(p);
+}
+template <int C, int K>
+__global__ __launch_bounds__(64 * kRbWaves, kRbWps) void hifigan_resblock16_bf16_kernel(const ResblockP p) {
+    hifigan_resblock16_amp_body<C, K, true>(p);
 }
 
 }  // namespace esmi

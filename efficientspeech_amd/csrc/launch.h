@@ -84,6 +84,8 @@ inline ConvGemmP conv_transpose1d(int B, int n_in, int n_out, int c_in, int c_ou
 // tu_convgemm_bf16.hip: the three GEMM families with bfloat16 operands (ConvGemmP::amp == 2, the training step's bf16-mixed precision).
 // launch_convgemm decides the family, the tiling and the grid exactly as for the other precisions and hands them over
 int launch_convgemm_stream_bf16(const ConvGemmP& p, int nt, dim3 grid, hipStream_t st);
+// the length-limited streaming kernel (ConvGemmP::len) with bfloat16 operands: the generator's limited stages at bf16
+int launch_convgemm_len_bf16(const ConvGemmP& p, int nt, dim3 grid, hipStream_t st);
 #if ESMI_CHAIN_SPLIT
 int launch_pwgemm_bf16(const ConvGemmP& p, bool full_row, dim3 grid, int n_items, hipStream_t st);
 int launch_convgemm_dma_bf16(const ConvGemmP& p, bool wide, int mt, dim3 grid, int lds_bytes, int nx, int ny, hipStream_t st);
@@ -114,6 +116,8 @@ int launch_enc_merge_q256(const MergeQ256P& p, hipStream_t st);   // enc_merge25
 int launch_resblock(const ResblockP& p, int c, hipStream_t st);
 // tu_hifigan_amp.hip: the same block with one binary16 product per contraction (the generator at precision 16; p.R <= rb_amp_rmax(c))
 int launch_resblock_amp(const ResblockP& p, int c, hipStream_t st);
+// tu_hifigan_bf16.hip: the same with one bfloat16 product per contraction (the generator at bf16; same window)
+int launch_resblock_bf16(const ResblockP& p, int c, hipStream_t st);
 
 // Does enc_attn_ffn serve this block (the shapes it is instantiated for)?  Not beyond 128 positions: there the chain kernel runs one
 // latency chain per 32 rows against up to 256 keys, and the same ops as launches (LDS-staged attention + GEMMs) are faster (launches
@@ -148,8 +152,13 @@ int set_range_flag_dec_128_5_p16(int* flag);
 int set_range_flag_dec_128_3_p16(int* flag);
 int set_range_flag_dec_256_5_p16(int* flag);
 int set_range_flag_dec_256_3_p16(int* flag);
+int set_range_flag_dec_128_5_bf16(int* flag);
+int set_range_flag_dec_128_3_bf16(int* flag);
+int set_range_flag_dec_256_5_bf16(int* flag);
+int set_range_flag_dec_256_3_bf16(int* flag);
 int set_range_flag_hifigan(int* flag);
 int set_range_flag_hifigan_amp(int* flag);
+int set_range_flag_hifigan_bf16(int* flag);
 int set_range_flag_train(int* flag);
 // development (-DESMI_CHAIN_TRACE): every translation unit with chain kernels owns a copy of the trace pointer
 #ifdef ESMI_CHAIN_TRACE

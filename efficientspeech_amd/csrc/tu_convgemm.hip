@@ -42,12 +42,13 @@ int launch_convgemm(ConvGemmP p, hipStream_t st) {
     if (p.len) {
         // per-utterance lengths (HiFi-GAN stages of a length-aware call): the streaming kernel's tiles never span utterances, so the
         // limit is one scalar per wave; the LDS-staged kernels below tile flat rows across utterances and do not take it
-        if (bf16 || full_row || p.ids || p.rowmask || p.io_scale || p.len_mul < 1 || p.len_add < 0 ||
+        if (full_row || p.ids || p.rowmask || p.io_scale || p.len_mul < 1 || p.len_add < 0 ||
             p.c_out > 64 || (p.mode == MODE_CONV && (p.stride != 1 || p.n_in != p.n_out)))   // (c_out <= 64: what the generator limits)
             return ESMI_ERR_UNSUPPORTED;
         const int nt = p.c_out > 32 ? 2 : 1;
         const int tiles = p.B * convgemm_tiles_per_phase(p) * convgemm_row_stride(p);
         const dim3 grid((tiles + 3) / 4, (p.c_out + 32 * nt - 1) / (32 * nt)), block(256);
+        if (bf16) return launch_convgemm_len_bf16(p, nt, grid, st);
         if (p.amp) {
             if (nt == 1) { ESMI_LAUNCH((convgemm_len_amp_kernel<1>), grid, block, 0, st, p); }
             else { ESMI_LAUNCH((convgemm_len_amp_kernel<2>), grid, block, 0, st, p); }

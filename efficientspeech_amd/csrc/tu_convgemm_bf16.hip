@@ -1,5 +1,5 @@
 // esmi C-ABI, translation unit "tu_convgemm_bf16.hip": the implicit-GEMM families of convgemm.h / pwgemm.h with bfloat16 operands
-// (ConvGemmP::amp == 2: the training step's bf16-mixed precision, ESMI_PRECISION_BF16).  launch_convgemm (tu_convgemm.hip) picks the
+// (ConvGemmP::amp == 2: the training step's bf16-mixed precision and the generator at bf16, ESMI_PRECISION_BF16).  launch_convgemm (tu_convgemm.hip) picks the
 // family, the tiling and the grid; the launchers below only select the instantiation.  A unit of its own so that the cold build
 // compiles these instantiations next to the binary16 ones, not after them.
 // One of several translation units of libesmi.so (compiled in parallel by __graft_entry__.build(); the simulator build
@@ -20,6 +20,14 @@ int launch_convgemm_stream_bf16(const ConvGemmP& p, int nt, dim3 grid, hipStream
         case 8: ESMI_LAUNCH((convgemm_bf16_kernel<8>), grid, block, 0, st, p); break;
         default: return ESMI_ERR_UNSUPPORTED;
     }
+    return launch_status();
+}
+
+int launch_convgemm_len_bf16(const ConvGemmP& p, int nt, dim3 grid, hipStream_t st) {
+    const dim3 block(256);
+    if (nt == 1) { ESMI_LAUNCH((convgemm_bf16_len_kernel<1>), grid, block, 0, st, p); }
+    else if (nt == 2) { ESMI_LAUNCH((convgemm_bf16_len_kernel<2>), grid, block, 0, st, p); }
+    else return ESMI_ERR_UNSUPPORTED;
     return launch_status();
 }
 

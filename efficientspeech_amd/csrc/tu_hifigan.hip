@@ -100,7 +100,7 @@ HgMargins hg_margins(const esmi_hifigan_shape* s) {
     return g;
 }
 
-// amp (precision 16): the window of the one-product kernels -- half the LDS per row, and 16 waves at 64 channels (rb_amp_rmax)
+// amp (precision 16 and bf16): the window of the one-product kernels -- half the LDS per row, and 16 waves at 64 channels (rb_amp_rmax)
 bool resblock_fused_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, int rb, int c, int k, int n, bool amp, ResblockP* o) {
 #if !ESMI_CHAIN_SPLIT
     return false;   // the exact-fp32 build keeps the per-conv fp32-MFMA launches
@@ -203,19 +203,21 @@ bool hg_weights_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, i
 // stage, about a fifth; v1 its 256- and 128-channel stages, about two thirds -- on v1 most of the padded work is still done.
 // precision 0 / 32: the fp32-accurate split products.  16 (include/esmi.h): conv_pre, every ConvTranspose1d and every ResBlock convolution
 // carry ConvGemmP::amp, a one-launch ResBlock runs on hifigan_resblock_amp_kernel / hifigan_resblock16_amp_kernel; conv_post is unchanged.
+// ESMI_PRECISION_BF16: the same launches with ConvGemmP::amp = 2 (bfloat16 operands, nothing scaled) and the ResBlocks' bf16 kernels
+// (hifigan_resblock_bf16_kernel / hifigan_resblock16_bf16_kernel: same window, same packed weights).
 int hifigan_generator(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
                       const int32_t* mel_len, float* wav, int16_t* pcm, int precision, void* workspace, size_t workspace_bytes,
                       esmi_stream_t stream) {
-    if (precision != 0 && precision != 32 && precision != 16) return ESMI_ERR_ARG;
-    const int amp = precision == 16;
+    if (precision != 0 && precision != 32 && precision != 16 && precision != ESMI_PRECISION_BF16) return ESMI_ERR_ARG;
+    const int amp = precision == 16 ? 1 : (precision == ESMI_PRECISION_BF16 ? 2 : 0);   // ConvGemmP::amp of the per-convolution launches
     size_t buf;
     int rc = hg_plan(s, B, L, &buf);
     if (rc) return rc;
-    if (amp && !ESMI_CHAIN_SPLIT) return ESMI_ERR_UNSUPPORTED;   // the exact-fp32 build has no binary16 products
+    if (amp && !ESMI_CHAIN_SPLIT) return ESMI_ERR_UNSUPPORTED;   // the exact-fp32 build has no one-product path
     if (!w || !mel || (!wav && !pcm) || !workspace) return ESMI_ERR_ARG;
     if (workspace_bytes < 4 * buf) return ESMI_ERR_WORKSPACE;
     ResblockP fused[ESMI_HIFIGAN_MAX_RBCONV / 3];   // (hg_plan: n_up . n_kernels fit)
-    if (!hg_weights_ok(w, s, L, amp, fused)) return ESMI_ERR_ARG;
+    if (!hg_weights_ok(w, s, L, amp != 0, fused)) return ESMI_ERR_ARG;
     const HgMargins mg = hg_margins(s);
     hipStream_t st = S(stream);
     auto ws = [&](int q) { return reinterpret_cast<float*>(static_cast<char*>(workspace) + q * buf); };
@@ -242,7 +244,7 @@ int hifigan_generator(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s
             if (fp.n_conv) {   // the whole block on an LDS-resident window: y -> x (+)=
                 fp.x = y; fp.out = x; fp.B = B; fp.accum = j > 0; fp.slope = kSlope;
                 g.limit(&fp);
-                rc = amp ? launch_resblock_amp(fp, g.c, st) : launch_resblock(fp, g.c, st);
+                rc = amp == 2 ? launch_resblock_bf16(fp, g.c, st) : (amp ? launch_resblock_amp(fp, g.c, st) : launch_resblock(fp, g.c, st));
             } else {
                 rc = resblock_conv_by_conv(w, s, g, rb, y, x, r, t, amp, st);
             }

@@ -200,6 +200,35 @@ __device__ __forceinline__ u32x4 round_bf16x8(const f32x4& x0, const f32x4& x1) 
     o[3] = round_bf16_pair(x1[2], x1[3]);
     return o;
 }
+// the weight operand of the bf16 inference kernels that read the two-plane binary16 weight blobs (mel decoder, one-launch ResBlocks;
+// include/esmi.h): 8 weights as RNE bfloat16 of (plane0 + plane1) * 2^-8, formed in registers.  The planes are the nearest binary16 of
+// 2^8 W and of its residual: their sum is exact in fp32 (at most 22 significant bits), and so is the power-of-two scale
+__device__ __forceinline__ u32x4 bf16_of_f16_planes(const u32x4& p0, const u32x4& p1) {
+    u32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#ifdef ESMI_WAVESIM
+        const float a = f16_bits_to_f32(p0[j] & 0xFFFFu) + f16_bits_to_f32(p1[j] & 0xFFFFu);
+        const float b = f16_bits_to_f32(p0[j] >> 16) + f16_bits_to_f32(p1[j] >> 16);
+#else
+        typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+        const unsigned u0 = p0[j], u1 = p1[j];   // (scalars first: __builtin_bit_cast of a vector ELEMENT expression reads element 0 for every j)
+        const f16x2_t h0 = __builtin_bit_cast(f16x2_t, u0), h1 = __builtin_bit_cast(f16x2_t, u1);
+        const float a = (float)h0[0] + (float)h1[0], b = (float)h0[1] + (float)h1[1];
+#endif
+        o[j] = round_bf16_pair(a * kF16WScaleInv, b * kF16WScaleInv);
+    }
+    return o;
+}
+// v_mfma_f32_16x16x32_bf16 (gfx950): operand and result layout of mfma16_f16
+__device__ __forceinline__ f32x4 mfma16_bf16(const u32x4& a, const u32x4& b, f32x4 c) {
+#ifdef ESMI_WAVESIM
+    return wavesim::mfma_16x16x32_bf16(a, b, c);
+#else
+    typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+#endif
+}
 __device__ __forceinline__ f32x16 mfma32_f16(const u32x4& a, const u32x4& b, f32x16 c) {
 #ifdef ESMI_WAVESIM
     return wavesim::mfma_32x32x16_f16(a, b, c);

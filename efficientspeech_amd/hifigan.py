@@ -63,9 +63,8 @@ HIFIGAN_CONFIGS = {
 
 
 def _check_precision(precision):
-    if precision not in (16, 32):
-        raise ValueError(f"vocoder precision must be 32 or 16, got {precision!r}")
-    return int(precision)
+    """-> 32, 16 or "bf16" (`_lib.normalize_precision`: "bf16-mixed" and the reference's other named spellings are accepted)"""
+    return _lib.normalize_precision(precision, "vocoder precision", numeric_strings=False)
 
 
 def get_padding(kernel_size, dilation=1):
@@ -97,7 +96,7 @@ class Generator(_PackedModule):
 
     def __init__(self, h=None, precision=32):
         super().__init__()
-        self.precision = _check_precision(precision)   # forward's default: 32, or 16 (include/esmi.h: one binary16 product per contraction)
+        self.precision = _check_precision(precision)   # forward's default: 32, 16 (include/esmi.h: one binary16 product per contraction) or "bf16" (one bfloat16 product)
         if h is None:
             h = HifiGanConfig()
         elif isinstance(h, (str, os.PathLike, dict)) and not hasattr(h, "upsample_rates"):
@@ -187,7 +186,8 @@ class Generator(_PackedModule):
         """x: mel (B, num_mels, L) as the reference takes it -> wav (B, 1, L * hop).
 
         `precision`: 32 (fp32-accurate products) or 16 (every convolution but conv_post on binary16 operands with fp32 accumulation, as
-        the reference's `--precision 16` autocast vocodes: 2-4 PCM LSB rms away from 32, see include/esmi.h); None: `self.precision`.
+        the reference's `--precision 16` autocast vocodes: 2-4 PCM LSB rms away from 32, see include/esmi.h) or "bf16" ("bf16-mixed": the same
+        convolutions on bfloat16 operands, nothing scaled, no overflow at 65520); None: `self.precision`.
         Both read the same packed weights.
 
         `lengths`: int tensor (B,) on the device, the mel frames of each utterance (`Phoneme2Mel`'s `mel_len` as it is: no host
@@ -216,7 +216,7 @@ class Generator(_PackedModule):
         if precision == 32:
             lib.esmi_hifigan_generator_f32(C.byref(w), C.byref(s), _ptr(mel), B, L, _ptr(wav), _ptr(ws), nbytes, stream)
         else:
-            lib.esmi_hifigan_generator_prec_f32(C.byref(w), C.byref(s), _ptr(mel), B, L, None, _ptr(wav), None, precision, _ptr(ws), nbytes, stream)
+            lib.esmi_hifigan_generator_prec_f32(C.byref(w), C.byref(s), _ptr(mel), B, L, None, _ptr(wav), None, _lib.precision_code(precision), _ptr(ws), nbytes, stream)
         return wav
 
     def _forward_ragged(self, x, lengths, pcm16, precision=32):
@@ -238,7 +238,7 @@ class Generator(_PackedModule):
         if precision == 32:
             lib.esmi_hifigan_generator_ragged_f32(C.byref(w), C.byref(s), _ptr(mel), B, L, _ptr(lengths), *planes, _ptr(ws), nbytes, stream)
         else:
-            lib.esmi_hifigan_generator_prec_f32(C.byref(w), C.byref(s), _ptr(mel), B, L, _ptr(lengths), *planes, precision, _ptr(ws), nbytes, stream)
+            lib.esmi_hifigan_generator_prec_f32(C.byref(w), C.byref(s), _ptr(mel), B, L, _ptr(lengths), *planes, _lib.precision_code(precision), _ptr(ws), nbytes, stream)
         return out
 
 

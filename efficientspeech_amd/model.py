@@ -12,6 +12,7 @@ import os
 import torch
 from torch import nn
 
+from . import _lib
 from .config import CONFIGS, ESConfig, LJSPEECH_PITCH_STATS, LJSPEECH_ENERGY_STATS
 from .networks import PhonemeEncoder, MelDecoder, Phoneme2Mel
 
@@ -160,18 +161,19 @@ class EfficientSpeech(nn.Module):
         `pitch_control`, `energy_control`, `duration_control`: per-utterance prosody scales (a number, or a tensor of shape (B,) or ()),
         the same as the input-dict keys of those names (`networks._prosody_controls`: the prediction that is bucketized / rounded is
         multiplied inside the kernels; `duration_control=1.25` speaks 25 % slower).  An argument that is given replaces the batch's key.
-        `precision`: the vocoder's, 32 or 16 (hifigan.Generator.forward); None: the vocoder's own.
-        `decoder_precision`: the mel decoder's, 32 or 16 -- the input-dict key of that name (`Phoneme2Mel._launch`; the argument replaces
+        `precision`: the vocoder's, 32, 16 or "bf16" (hifigan.Generator.forward); None: the vocoder's own.
+        `decoder_precision`: the mel decoder's, 32, 16 or "bf16" -- the input-dict key of that name (`Phoneme2Mel._launch`; the argument replaces
         the batch's key); None: the decoder's own `precision` attribute.  The encoder side is fp32-accurate either way, so `wav_len` and
         `duration` do not depend on it.  `precision=16, decoder_precision=16` is the reference's `--precision 16` for both the decoder
-        and the vocoder."""
-        if precision is not None and precision not in (16, 32):
-            raise ValueError(f"vocoder precision must be 32 or 16, got {precision!r}")
+        and the vocoder; `precision="bf16", decoder_precision="bf16"` is `--precision bf16-mixed`, the arithmetic a
+        `TrainStep(precision="bf16")` checkpoint was trained at."""
+        if precision is not None:
+            precision = _lib.normalize_precision(precision, "vocoder precision", numeric_strings=False)
         if self.hifigan is None:
             raise RuntimeError("synthesize() needs a vocoder: attach one (hifigan=Generator(...) / get_hifigan(...)); "
                                "predict_step returns the mel when there is none")
-        if decoder_precision is not None and (isinstance(decoder_precision, bool) or decoder_precision not in (16, 32)):
-            raise ValueError(f"decoder precision must be 32 or 16, got {decoder_precision!r}")
+        if decoder_precision is not None:
+            decoder_precision = _lib.normalize_precision(decoder_precision, "decoder precision", numeric_strings=False)
         controls = {"pitch_control": pitch_control, "energy_control": energy_control, "duration_control": duration_control,
                     "decoder_precision": decoder_precision}
         if any(v is not None for v in controls.values()):

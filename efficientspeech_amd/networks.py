@@ -632,18 +632,16 @@ class FeatureUpsampler(nn.Module):
 
 
 def _decoder_precision(precision, default=32):
-    """The mel decoder's precision argument (32, or 16: include/esmi.h, esmi_mel_decoder_prec_f32) validated on the host; None -> `default`."""
-    if precision is None:
-        precision = default
-    if isinstance(precision, bool) or precision not in (16, 32):
-        raise ValueError(f"decoder precision must be 32 or 16, got {precision!r}")
-    return int(precision)
+    """The mel decoder's precision argument (include/esmi.h, esmi_mel_decoder_prec_f32) validated on the host -> 32, 16 or "bf16"
+    (`_lib.normalize_precision`: "bf16-mixed" and the reference's other named spellings are accepted); None -> `default`."""
+    return _lib.normalize_precision(default if precision is None else precision, "decoder precision", numeric_strings=False)
 
 
 class MelDecoder(_PackedModule):
-    """Mel spectrogram decoder (networks.py:261-304), one fused HIP kernel per call: esmi_mel_decoder_prec_f32, at either precision.
+    """Mel spectrogram decoder (networks.py:261-304), one fused HIP kernel per call: esmi_mel_decoder_prec_f32, at any of its precisions.
     `precision` (a plain attribute, not in the state_dict; default 32): 16 runs every contraction of the kernel as ONE binary16
-    product with fp32 accumulation (include/esmi.h) -- the same packed weights, the same launch geometry.  It is the default of
+    product with fp32 accumulation, "bf16" ("bf16-mixed") as ONE bfloat16 product with nothing scaled (include/esmi.h) -- the same
+    packed weights, the same launch geometry.  It is the default of
     `forward` and of the inference forward of `Phoneme2Mel`; `Phoneme2Mel.forward(x, train=True)` runs the decoder at 32 regardless."""
 
     def __init__(self, dim, kernel_size=5, n_mel_channels=80, n_blocks=2, block_depth=2):
@@ -667,7 +665,7 @@ class MelDecoder(_PackedModule):
         self.timing = None      # bench.py sets this to a list to collect (start, end) HIP events per timed launch
         self.timing_every = 1   # ... on every n-th launch only (an event pair costs ~10 us of pipeline drain per step)
         self._launches = 0
-        self.precision = 32     # forward's default: 32, or 16 (one binary16 product per contraction)
+        self.precision = 32     # forward's default: 32, 16 (one binary16 product per contraction) or "bf16" (one bfloat16 product)
 
     def _shape(self):
         return _lib.DecoderShape(self.dim_x4, self.dim_x2, self.kernel_size, self.n_blocks, self.block_depth,
@@ -712,7 +710,7 @@ class MelDecoder(_PackedModule):
             return self._forward(features, precision)
 
     def _forward(self, features, precision=None):
-        """features (B,L,4*dim) -> mel (B,L,n_mel).  (Direct mode: rows exactly as given.)  precision: 32 or 16; None: `self.precision`."""
+        """features (B,L,4*dim) -> mel (B,L,n_mel).  (Direct mode: rows exactly as given.)  precision: 32, 16 or "bf16"; None: `self.precision`."""
         precision = _decoder_precision(precision, self.precision)
         x = _f32(features)
         lib, stream = _runtime(x)
@@ -722,7 +720,7 @@ class MelDecoder(_PackedModule):
             shape = self._shape()
             ws, ws_bytes = self._workspace(lib, shape, B, L, x.device)
             lib.esmi_mel_decoder_prec_f32(_ptr(self._packed(lib, stream)), C.byref(shape), _ptr(x), None, None, None, None, L, 0,
-                                          B, 0, L, _ptr(mel), _ptr(ws), ws_bytes, precision, stream)
+                                          B, 0, L, _ptr(mel), _ptr(ws), ws_bytes, _lib.precision_code(precision), stream)
         return mel
 
     @staticmethod
@@ -764,7 +762,8 @@ class MelDecoder(_PackedModule):
                 ev[0].record()
             ws, ws_bytes = self._workspace(lib, shape, B, L_out, feat.device)
             lib.esmi_mel_decoder_prec_f32(_ptr(blob), C.byref(shape), _ptr(feat), _ptr(h0), _ptr(cum), _ptr(mel_len), _ptr(lmax_dev),
-                                          int(lmax_host), int(apply_mask), B, T, L_out, _ptr(mel), _ptr(ws), ws_bytes, precision, stream)
+                                          int(lmax_host), int(apply_mask), B, T, L_out, _ptr(mel), _ptr(ws), ws_bytes,
+                                          _lib.precision_code(precision), stream)
             if ev is not None:
                 ev[1].record()
                 self.timing.append(ev)
@@ -988,7 +987,7 @@ class Phoneme2Mel(nn.Module):
         call returned (a multi-GPU caller MAX-reduces `state.lmax` in between).  -> the call's `_Request` with mel, mel_len,
         duration (B,T,1), lmax (device scalar or None).  Every stage is one call of esmi_phoneme2mel_forward_curve_f32 (the control struct
         or NULL, the precision): the older entry points are that call with NULL and / or 32 (include/esmi.h).
-        Inference extension keys of x: `duration_forced`, `max_mel_len` (`max_mel_len_exact`), `decoder_precision` (16 or 32, validated on
+        Inference extension keys of x: `duration_forced`, `max_mel_len` (`max_mel_len_exact`), `decoder_precision` (16, 32 or "bf16", validated on
         the host: the mel decoder's arithmetic for this call, overriding `self.decoder.precision`; the encoder side is untouched by it, so
         mel_len and the durations are the same bits either way -- include/esmi.h), and the per-utterance prosody controls
         `pitch_control`, `energy_control`, `duration_control` (a number, a (B,) / () tensor or a (B, T) per-phoneme curve each; numbers are validated on the host,
@@ -1031,7 +1030,7 @@ class Phoneme2Mel(nn.Module):
         dec, ctl_p = self.decoder, None if st.ctl is None else C.byref(st.ctl)
 
         def forward(stage_):                   # (stage 1 ignores the precision, stage 2 the controls)
-            lib.esmi_phoneme2mel_forward_curve_f32(C.byref(a), ctl_p, st.precision, stage_, stream)
+            lib.esmi_phoneme2mel_forward_curve_f32(C.byref(a), ctl_p, _lib.precision_code(st.precision), stage_, stream)
         timed = False
         if stage != 1 and dec.timing is not None:                     # bench.py: HIP events around the decoder launch only
             dec._launches += 1

@@ -86,15 +86,7 @@ def _grad_buffer(param):
 _DESC_PRECISION = {16: 16, "bf16": _lib.PRECISION_BF16}     # `_Step.precision` -> esmi_conv_desc.precision (everything else: fp32-accurate)
 
 
-def normalize_precision(precision):
-    """32, 16 or "bf16" from what the reference's `--precision` takes for them: "bf16-mixed" (Lightning's spelling), "16-mixed",
-    "32-true", and the numbers as strings."""
-    names = {"32": 32, "32-true": 32, "16": 16, "16-mixed": 16, "bf16": "bf16", "bf16-mixed": "bf16"}
-    if isinstance(precision, str) and precision in names:
-        return names[precision]
-    if precision in (16, 32) and not isinstance(precision, bool):
-        return int(precision)
-    raise ValueError(f"precision must be 32, 16 or 'bf16' ('bf16-mixed'), got {precision!r}")
+normalize_precision = _lib.normalize_precision     # (shared with inference: its home is _lib)
 
 
 def _conv_desc(lib, x, w0, w, n_out, stride, pad, groups, transposed, act):

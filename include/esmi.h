@@ -34,7 +34,7 @@ extern "C" {
 
 #define ESMI_VERSION 501 /* 0.5.1: esmi_train_conv_ln_fwd_f32, then esmi_hifigan_generator_ragged_f32, then esmi_prosody_control and the three
                             *_ctl_f32 entry points, then esmi_hifigan_generator_prec_f32, then esmi_mel_decoder_prec_f32 and
-                            esmi_phoneme2mel_forward_prec_f32, then esmi_prosody_curves and the three *_curve_f32 entry points, then ESMI_PRECISION_BF16 as a value of esmi_conv_desc.precision (additions; nothing else changed shape).  0.5.0 (round 5): esmi_mel_decoder_clock_probe;
+                            esmi_phoneme2mel_forward_prec_f32, then esmi_prosody_curves and the three *_curve_f32 entry points, then ESMI_PRECISION_BF16 as a value of esmi_conv_desc.precision, then as a value of the inference entry points' `precision` (additions; nothing else changed shape).  0.5.0 (round 5): esmi_mel_decoder_clock_probe;
                             0.4.0: esmi_decoder_head.proj_w (the decoder's first stage at phoneme rate for every model size:
                           * esmi_decoder_head_f32).  0.3.0: training entry points changed shape (esmi_conv_desc: act / packed_fwd / packed_grad; LayerNorm with
                           * residual / row mask / activation arguments; esmi_train_loss_args.grad_seed; esmi_train_pack_weights_f32,
@@ -548,7 +548,8 @@ int esmi_phoneme2mel_forward_ctl_f32(const esmi_forward_args* a, const esmi_pros
  * binary16-operand implementation: 7e-4 .. 2e-3 rms, 3e-3 .. 2e-2 L-inf on mels of magnitude 4 .. 15 (tiny / small / base).
  * Activations beyond the binary16 range (|a| >= 65520) become +-inf, as under torch autocast; libesmi_checked.so range-checks every value
  * it rounds.
- * precision 0 / 32: exactly esmi_mel_decoder_f32 (the same kernel, the same bits); 16: as above; anything else: ESMI_ERR_ARG.
+ * precision 0 / 32: exactly esmi_mel_decoder_f32 (the same kernel, the same bits); 16: as above; ESMI_PRECISION_BF16: "Inference at bf16"
+ * below; anything else: ESMI_ERR_ARG.
  * libesmi_fp32mfma.so has no binary16 products: precision 16 is ESMI_ERR_UNSUPPORTED there.  Nothing is launched by a refused call. */
 int esmi_mel_decoder_prec_f32(const float* blob, const esmi_decoder_shape* s, const float* x, const float* h0, const int32_t* cum,
                               const int32_t* mel_len, const int32_t* lmax_dev, int lmax_host, int apply_mask, int B, int T, int L_out,
@@ -643,11 +644,40 @@ int esmi_hifigan_generator_ragged_f32(const esmi_hifigan_weights* w, const esmi_
  * implementation: 2e-4 .. 5e-4 L-inf, 6e-5 .. 1.2e-4 rms on waveforms of rms 0.06 .. 0.18 for v1 / v2 / v3 (2-4 PCM LSB rms).
  *
  * mel_len == NULL: the plain call (pcm must be NULL); else the length-aware one.  precision 0 / 32: exactly
- * esmi_hifigan_generator_f32 / _ragged_f32; 16: as defined above; anything else: ESMI_ERR_ARG, nothing launched.
+ * esmi_hifigan_generator_f32 / _ragged_f32; 16: as defined above; ESMI_PRECISION_BF16: "Inference at bf16" below; anything else:
+ * ESMI_ERR_ARG, nothing launched.
  * libesmi_fp32mfma.so has no binary16 products: precision 16 is ESMI_ERR_UNSUPPORTED there, nothing launched.  Workspace as above. */
 int esmi_hifigan_generator_prec_f32(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
                                     const int32_t* mel_len, float* wav, int16_t* pcm, int precision,
                                     void* workspace, size_t workspace_bytes, esmi_stream_t stream);
+
+/* Inference at bf16 (opt-in): precision = ESMI_PRECISION_BF16 (0xB16, defined below) in esmi_mel_decoder_prec_f32,
+ * esmi_phoneme2mel_forward_prec_f32, esmi_phoneme2mel_forward_curve_f32 and esmi_hifigan_generator_prec_f32 -- the reference's
+ * `--precision bf16-mixed` applied to synthesis, and the arithmetic a checkpoint trained with esmi_conv_desc.precision =
+ * ESMI_PRECISION_BF16 was trained at.  EVERY contraction that precision 16 runs as one binary16 product runs as ONE bfloat16 product with
+ * fp32 accumulation (v_mfma_f32_32x32x16_bf16 / v_mfma_f32_16x16x32_bf16: the cycles of the f16 forms).  Decoder: the pointwise
+ * convolutions, the mel Linear, and `proj` when the kernel runs it.  Vocoder: every convolution but conv_post -- conv_pre, every
+ * ConvTranspose1d, every ResBlock convolution, one launch or conv by conv.
+ *   - both operands are rounded to bfloat16, round to nearest even; the activation is rounded where precision 16 rounds it (the depthwise
+ *     output, the last LayerNorm's rows, the fp32 input rows of `proj`; in the vocoder after the input-side leaky_relu(a_scale * x));
+ *   - NOTHING is scaled: no 2^8 on the weight operand, no 2^-8 in the epilogue;
+ *   - everything that is fp32 at precision 16 stays fp32 (depthwise taps, biases, tanh, every LayerNorm, the skip tensor, the h0 gather, the
+ *     carried rows; the ResBlock residual stream, the sum over a stage's ResBlocks, conv_post, the tensors in memory); phases, grid, LDS
+ *     layout, workspace and the chunk walk are those of precision 16; the length-aware generator call keeps its guarantees;
+ *   - the weight operand of the per-convolution launches (conv_pre, ConvTranspose1d, conv-by-conv ResBlocks): RNE bfloat16 of the fp32
+ *     weight, rounded as it is read;
+ *   - the weight operand of the fused kernels (mel decoder, one-launch ResBlocks), whose weights exist only as two binary16 planes of
+ *     2^8 * W: RNE bfloat16 of (plane0 + plane1) * 2^-8, formed in registers when the wave loads its weight slice.  The sum of the planes
+ *     is exact in fp32 and carries W to 22 bits, so this equals bfloat16(W) except where W lies within 2^-22 |W| of a bfloat16 rounding
+ *     boundary: about one weight in 2^13, by one bfloat16 ulp.  No new pack format, no second copy: one blob serves three precisions.
+ * bfloat16 has fp32's exponent range: there is no overflow hazard at |a| >= 65520, no range-checked twin (libesmi_checked.so runs bf16
+ * with nothing to check) and no weight guard.  The encoder side is not touched: mel_len, the durations and cum are bit for bit those of
+ * precision 32.  Expect the error of any bfloat16-operand implementation, 2^3 times precision 16's (three fewer significand bits).
+ * Measured against precision 32 (profiles/r15_inference_bf16.md): mel 4.7e-3 .. 7.1e-3 rms, 3.1e-2 .. 4.5e-2 L-inf on mels of rms 1.0,
+ * max 5.2 (tiny / small / base); waveform 5.0e-4 .. 6.4e-4 rms, 3.1e-3 .. 4.5e-3 L-inf on waveforms of rms 0.06 .. 0.12 (v1 / v2): 15-21
+ * PCM LSB rms.
+ * libesmi_fp32mfma.so has no one-product path: ESMI_PRECISION_BF16 is ESMI_ERR_UNSUPPORTED there, as 16 is.  Any value other than 0, 32, 16
+ * and ESMI_PRECISION_BF16 is ESMI_ERR_ARG; nothing is launched by a refused call. */
 
 /* x.masked_fill(mask[:, :, None], 0) on (rows, C) fp32 -- used by the module-level API when the
  * decoder is called stand-alone.                                                              */
@@ -660,7 +690,7 @@ int esmi_mask_rows_f32(float* x, const uint8_t* mask, int64_t rows, int C, esmi_
  * ConvTranspose1d (Cin, Cout, k), Linear (Cout, Cin) = a conv with k = 1.  First correct version: one thread per output
  * element, fp32 FMA loops, no atomics (a step is bitwise reproducible); see csrc/train_ops.h.  The Python side
  * (efficientspeech_amd/train.py) composes them with torch.autograd as the tape. */
-#define ESMI_PRECISION_BF16 0xB16 /* esmi_conv_desc.precision: bf16-mixed (below) */
+#define ESMI_PRECISION_BF16 0xB16 /* esmi_conv_desc.precision: bf16-mixed (below); the inference entry points' `precision`: bf16 (above) */
 typedef struct esmi_conv_desc {
     int B, n_in, c_in, n_out, c_out, k, stride, pad;
     int groups;       /* 1, or c_in == c_out == groups (depthwise, MelDecoder networks.py:275) */

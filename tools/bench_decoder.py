@@ -3,7 +3,10 @@
    python tools/bench_decoder.py [--config tiny] [--libs a.so b.so ...]
 --precision 16 (esmi_mel_decoder_prec_f32: one binary16 product per contraction): times precision 32 and 16 of the same call in alternating
 legs 32 / 16 / 32 / 16 in one process, and prints per-leg medians, the spread of the two precision-32 legs (the noise a ratio has to
-beat), the ratio and the difference of the two mels."""
+beat), the ratio and the difference of the two mels.
+--precision bf16 (ESMI_PRECISION_BF16: one bfloat16 product per contraction): legs 32 / 16 / bf16 / 32; prints the ratios bf16 / 32 and
+bf16 / 16, the spread of the two precision-32 legs, whether the bf16 leg beats BOTH of them by more than that spread, and the
+difference between the two mels of each pair of precisions."""
 import argparse, ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -15,8 +18,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="tiny"); ap.add_argument("--batch", type=int, default=256)
 ap.add_argument("--phonemes", type=int, default=128); ap.add_argument("--dur", type=int, default=6)
 ap.add_argument("--zeros", action="store_true", help="zero activations (DVFS probe: same instruction stream, less switching power)"); ap.add_argument("--iters", type=int, default=30); ap.add_argument("--h0", action="store_true", help="phoneme-rate first stage supplied (what the full forward does for tiny, T <= 128)"); ap.add_argument("--burst", type=int, default=20, help="launches per timed burst (back-to-back, one event pair)"); ap.add_argument("--libs", nargs="*", default=[_lib.LIB_PATH])
-ap.add_argument("--precision", type=int, default=32, choices=(32, 16))
+ap.add_argument("--precision", default="32", choices=("32", "16", "bf16"))
 a = ap.parse_args()
+a.precision = a.precision if a.precision == "bf16" else int(a.precision)
 cfg = CONFIGS[a.config]
 B, T, L = a.batch, a.phonemes, a.phonemes * a.dur
 flops = {"tiny": 189_440, "small": 973_824, "base": 1_505_792}[a.config]
@@ -33,7 +37,7 @@ for path in a.libs:
     if a.zeros:
         feat.zero_()
         if h0 is not None: h0.zero_()
-    if a.precision == 16:
+    if a.precision in (16, "bf16"):
         def leg(pr):
             ts = []
             for _ in range(a.iters):
@@ -45,9 +49,23 @@ for path in a.libs:
                 torch.cuda.synchronize(); ts.append(s.elapsed_time(e) / a.burst)
             return float(np.median(ts)) * 1e3, m
         for _ in range(3):
-            for pr in (32, 16):
+            for pr in (32, 16, a.precision):
                 dec._fused(feat, cum, mel_len, None, L, True, L, h0=h0, precision=pr)
         torch.cuda.synchronize()
+        if a.precision == "bf16":
+            legs = [(pr,) + leg(pr) for pr in (32, 16, "bf16", 32)]      # alternating: the bf16 leg sits between the two precision-32 legs
+            (_, ta, m32), (_, t16, m16), (_, tb, mb), (_, tc, _m) = legs
+            noise = abs(ta - tc)
+            rms = lambda t: float(t.double().pow(2).mean().sqrt())       # noqa: E731
+            print(f"{os.path.basename(path)} {a.config} B={B} T={T} D={a.dur} h0={bool(a.h0)}: legs us " + "  ".join(f"p{pr} {t:.1f}" for pr, t, _ in legs))
+            print(f"  precision 32 {(ta + tc) / 2:8.1f} us (two legs, spread {noise:.1f} us = {noise / ((ta + tc) / 2) * 100:.2f} %)   16 {t16:8.1f} us   bf16 {tb:8.1f} us   "
+                  f"bf16 / 32 = {tb / ((ta + tc) / 2):.3f}   bf16 / 16 = {tb / t16:.3f}   16 / 32 = {t16 / ((ta + tc) / 2):.3f}")
+            print(f"  gate (bf16 faster than both precision-32 legs by more than their spread): {'PASS' if min(ta, tc) - tb > noise else 'FAIL'}")
+            for na, ma, nb, mb_ in (("bf16", mb, "32", m32), ("16", m16, "32", m32), ("bf16", mb, "16", m16)):
+                d = ma.double() - mb_.double()
+                print(f"  mel{na} - mel{nb}: L-inf {float(d.abs().max()):.2e} rms {rms(d):.2e}")
+            print(f"  mel32 rms {rms(m32):.3f} max {float(m32.abs().max()):.2f}   finite={bool(torch.isfinite(mb).all())}", flush=True)
+            continue
         legs = [(pr,) + leg(pr) for pr in (32, 16, 32, 16)]      # alternating: both precisions see the same clocks and neighbours
         t32, t16 = [t for pr, t, _ in legs if pr == 32], [t for pr, t, _ in legs if pr == 16]
         m32, m16 = legs[0][2].double(), legs[1][2].double()
