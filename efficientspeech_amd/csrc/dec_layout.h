@@ -12,6 +12,9 @@
 #if ESMI_DEC_SPLIT != 0 && ESMI_DEC_SPLIT != 2
 #error "ESMI_DEC_SPLIT must be 0 (fp32 MFMA) or 2 (split f16x2)"
 #endif
+#if (ESMI_DEC_SPLIT == 2) != (ESMI_CHAIN_SPLIT != 0)   // one build, one answer to "are the one-product paths there?" (launch.h precision_mode_built)
+#error "ESMI_DEC_SPLIT and ESMI_CHAIN_SPLIT go together: both split (2, 1) or both exact fp32 (0, 0)"
+#endif
 
 namespace esmi {
 
@@ -163,23 +166,13 @@ struct DecWalk {
     __host__ __device__ int keep() const { return skew ? kDecRows - sh : kDecRows - halo; }
 };
 
-// One translation unit per instantiation (tu_dec_<dx2>_<k>.hip: the kernel is by far the slowest thing to compile) defines these two
-// for its (DX2, KD) by explicit instantiation -- ESMI_DEC_INSTANCE, mel_decoder.h, where the definitions are.  Declarations only here:
-// tu_decoder.hip takes their addresses for its table of instantiations and must not see the definitions (it includes this header, never
-// mel_decoder.h), or it would instantiate the kernels itself.
-template <int DX2, int KD>
+// One translation unit per instantiation (tu_dec_<dx2>_<k>[_p16 | _bf16].hip: the kernel is by far the slowest thing to compile) defines
+// these two for its (DX2, KD, PM) by explicit instantiation -- ESMI_DEC_INSTANCE, mel_decoder.h, where the definitions are.  Declarations
+// only here: tu_decoder.hip takes their addresses for its table of instantiations and must not see the definitions (it includes this
+// header, never mel_decoder.h), or it would instantiate the kernels itself.
+template <int DX2, int KD, PrecisionMode PM>
 int launch_mel_decoder(const MelDecP& p, dim3 grid, hipStream_t st);
-template <int DX2, int KD>
+template <int DX2, int KD, PrecisionMode PM>
 int set_dec_clock(long long* slots);
-// ... and the same pair of the precision-16 kernel (tu_dec_<dx2>_<k>_p16.hip, ESMI_DEC_INSTANCE_P16; split build only)
-template <int DX2, int KD>
-int launch_mel_decoder_p16(const MelDecP& p, dim3 grid, hipStream_t st);
-template <int DX2, int KD>
-int set_dec_clock_p16(long long* slots);
-// ... and of the bf16 kernel (tu_dec_<dx2>_<k>_bf16.hip, ESMI_DEC_INSTANCE_BF16; split build only)
-template <int DX2, int KD>
-int launch_mel_decoder_bf16(const MelDecP& p, dim3 grid, hipStream_t st);
-template <int DX2, int KD>
-int set_dec_clock_bf16(long long* slots);
 
 }  // namespace esmi

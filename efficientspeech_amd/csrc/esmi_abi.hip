@@ -5,6 +5,7 @@
 #include "dec_layout.h"   // the decoder's build knob (esmi_build_config) and host-side helpers
 
 using namespace esmi;
+namespace esmi { RangeSetter* g_range_setters = nullptr; }   // every unit's ESMI_TU_RANGE_SETTER node (launch.h)
 ESMI_TU_RANGE_SETTER(abi)
 
 namespace {
@@ -849,28 +850,21 @@ int esmi_phoneme2mel_forward_curve_f32(const esmi_forward_args* a, const esmi_pr
     if (!a) return ESMI_ERR_ARG;
     // the precision argument of every form of this call is judged here, before the encoder side is enqueued
     if (stage == 1) precision = 32;   // (the encoder side has one arithmetic: stage 1 ignores the argument)
-    if (precision != 0 && precision != 32 && precision != 16 && precision != ESMI_PRECISION_BF16) return ESMI_ERR_ARG;
-#if ESMI_DEC_SPLIT != 2
-    if (precision == 16 || precision == ESMI_PRECISION_BF16) return ESMI_ERR_UNSUPPORTED;   // no one-product path in this build: refused before the encoder side is enqueued
-#endif
+    PrecisionMode mode;
+    if (int rc = precision_mode(precision, &mode)) return rc;
+    if (!precision_mode_built(mode)) return ESMI_ERR_UNSUPPORTED;   // no one-product path in this build: refused before the encoder side is enqueued
     if (stage != 2 && ctl_conflict(ctl, nullptr, nullptr, a->dur_forced)) return ESMI_ERR_ARG;   // (a forced duration is final)
     if (!a->range_flag) return forward_impl(a, ctl, precision, stage, stream);
 #if ESMI_RANGE_CHECK
     // validation mode: clear the word, point every translation unit's kernels at it, run, wait, read it back
     hipError_t e = hipMemsetAsync(a->range_flag, 0, sizeof(int32_t), S(stream));
     if (e != hipSuccess) return (int)e;
-    int (*const setters[])(int*) = {set_range_flag_abi, set_range_flag_convgemm, set_range_flag_attention, set_range_flag_enc_merge,
-                                    set_range_flag_enc_block, set_range_flag_enc_attn_ffn, set_range_flag_enc_fuse_va, set_range_flag_enc_va16, set_range_flag_enc_va64, set_range_flag_enc_pred128, set_range_flag_enc_block16,
-                                    set_range_flag_decoder, set_range_flag_dec_128_5, set_range_flag_dec_128_3, set_range_flag_dec_256_5,
-                                    set_range_flag_dec_256_3, set_range_flag_dec_128_5_p16, set_range_flag_dec_128_3_p16, set_range_flag_dec_256_5_p16,
-                                    set_range_flag_dec_256_3_p16, set_range_flag_dec_128_5_bf16, set_range_flag_dec_128_3_bf16, set_range_flag_dec_256_5_bf16,
-                                    set_range_flag_dec_256_3_bf16, set_range_flag_hifigan, set_range_flag_hifigan_amp, set_range_flag_hifigan_bf16, set_range_flag_train, set_range_flag_convgemm_bf16};
-    for (auto set : setters)
-        if (int rc = set(reinterpret_cast<int*>(a->range_flag))) return rc;
+    for (const RangeSetter* u = g_range_setters; u; u = u->next)
+        if (int rc = u->set(reinterpret_cast<int*>(a->range_flag))) return rc;
     int rc = forward_impl(a, ctl, precision, stage, stream);
     int32_t flag = 0;
     if (!rc) rc = read_device_flag(a->range_flag, S(stream), &flag);
-    for (auto set : setters) set(nullptr);
+    for (const RangeSetter* u = g_range_setters; u; u = u->next) u->set(nullptr);
     return rc ? rc : (flag ? ESMI_ERR_RANGE : ESMI_OK);
 #else
     return ESMI_ERR_UNSUPPORTED;   // this library was built without the range check (libesmi_checked.so has it)

@@ -12,6 +12,13 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 struct bf16x3 { u32x4 hi, mid, lo; };
 struct f16x2p { u32x4 h1, h2; };
+// The arithmetic of a contraction, one vocabulary from the C entry points (`int precision`, include/esmi.h; launch.h precision_mode) to
+// the kernel launch.  The values are ConvGemmP::amp's:
+//  PM_SPLIT  the default: fp32-accurate split products on the f16 matrix pipe (fp32 MFMAs in the exact-fp32 build);
+//  PM_F16    precision 16: one binary16 product per contraction;
+//  PM_BF16   ESMI_PRECISION_BF16: one bfloat16 product per contraction, nothing scaled.
+enum PrecisionMode { PM_SPLIT = 0, PM_F16 = 1, PM_BF16 = 2 };
+constexpr int kPrecisionModes = 3;
 constexpr float kF16WScale = 256.0f, kF16WScaleInv = 1.0f / 256.0f;
 __host__ __device__ inline unsigned f32_to_f16_bits(float f, bool rtz) {     // software conversion (packers, simulator)
     const unsigned u = __builtin_bit_cast(unsigned, f), sign = (u >> 16) & 0x8000u, a = u & 0x7FFFFFFFu;

@@ -28,6 +28,21 @@ inline int launch_status() {
 }
 inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
+// The `precision` of the C entry points and of esmi_conv_desc (include/esmi.h: 0 / 32, 16, ESMI_PRECISION_BF16) as the mode every
+// launcher below speaks (PrecisionMode, esmi_types.h); ESMI_ERR_ARG for anything else.
+inline int precision_mode(int precision, PrecisionMode* mode) {
+    switch (precision) {
+        case 0:
+        case 32: *mode = PM_SPLIT; return ESMI_OK;
+        case 16: *mode = PM_F16; return ESMI_OK;
+        case ESMI_PRECISION_BF16: *mode = PM_BF16; return ESMI_OK;
+    }
+    return ESMI_ERR_ARG;
+}
+// Does this build have the mode's kernels?  The exact-fp32 library (ESMI_CHAIN_SPLIT = 0 and ESMI_DEC_SPLIT = 0, one knob in two
+// spellings: dec_layout.h) has no one-product path; an entry point answers ESMI_ERR_UNSUPPORTED there.
+constexpr bool precision_mode_built(PrecisionMode mode) { return mode == PM_SPLIT || ESMI_CHAIN_SPLIT; }
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a PER-DEVICE setting: remember per (instantiation, device ordinal) that
 // it was made (once: keeps the call out of hipGraph captures).  `done` is one static table per call site.
 constexpr int kMaxDevices = 64;
@@ -112,12 +127,71 @@ int launch_enc_pred128(const Pred128P& p, int dim, hipStream_t st);   // enc_pre
 int launch_enc_fuse128(const FuseVaP& p, int dim, int kernel, hipStream_t st);   // enc_fuse128.h: the Fuse stage of the same models
 int launch_enc_post_attn128(const PostAttn128P& p, hipStream_t st);   // enc_ffn128.h: proj + LN1 + MixFFN + LN2, C = 128, two heads, expansion 2, N <= 256
 int launch_enc_merge_q256(const MergeQ256P& p, hipStream_t st);   // enc_merge256.h: merge conv k = 3 stride 2, 128 -> 256, + the folded query GEMM, N <= 128
-// tu_hifigan.hip (which also holds the generator's host side: esmi_hifigan_*)
-int launch_resblock(const ResblockP& p, int c, hipStream_t st);
-// tu_hifigan_amp.hip: the same block with one binary16 product per contraction (the generator at precision 16; p.R <= rb_amp_rmax(c))
-int launch_resblock_amp(const ResblockP& p, int c, hipStream_t st);
-// tu_hifigan_bf16.hip: the same with one bfloat16 product per contraction (the generator at bf16; same window)
-int launch_resblock_bf16(const ResblockP& p, int c, hipStream_t st);
+
+// ---- One HiFi-GAN ResBlock in one launch (hifigan_resblock.h) when its packed weights are there and (channels, kernel size) has an
+// instantiation; the generator's resblock_fused_ok (tu_hifigan.hip) decides and sizes the window, else the block runs conv by conv.
+// The (c, k) ladder, once for the three modes.  What the one-product kernels do differently: one operand plane in LDS instead of two
+// (rb_amp_lds_bytes), 16 waves at 64 channels (rb_amp_waves), and a window of at most rb_amp_rmax(c) rows.
+template <PrecisionMode PM, int C, int K>
+int launch_resblock_ck(const ResblockP& p, hipStream_t st) {
+    constexpr bool kOne = PM != PM_SPLIT;
+    const size_t lds = kOne ? rb_amp_lds_bytes(C, p.R) : rb_lds_bytes(C, p.R);
+    const dim3 grid((unsigned)(p.B * p.tiles_per_b)), block(64 * (kOne ? rb_amp_waves(C) : kRbWaves));
+    if (kOne && p.R > rb_amp_rmax(C)) return ESMI_ERR_ARG;   // (rows past the waves' items would never be computed)
+    if constexpr (C <= 16) {   // narrow MFMA tiles (16 channels x 16 positions): LDS <= 32 KB, no limit to raise
+        if constexpr (PM == PM_SPLIT) {
+            ESMI_LAUNCH((hifigan_resblock16_kernel<C, K>), grid, block, lds, st, p);
+        } else if constexpr (PM == PM_F16) {
+            ESMI_LAUNCH((hifigan_resblock16_amp_kernel<C, K>), grid, block, lds, st, p);
+        } else {
+            ESMI_LAUNCH((hifigan_resblock16_bf16_kernel<C, K>), grid, block, lds, st, p);
+        }
+    } else {
+        static AttrOnce once;
+#define ESMI_RB_LAUNCH(kern)                                                                                       \
+    do {                                                                                                           \
+        if (lds > 48 * 1024)                                                                                       \
+            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(kern), once)) return rc;                    \
+        ESMI_LAUNCH(kern, grid, block, lds, st, p);                                                                \
+    } while (0)
+        if constexpr (PM == PM_SPLIT) {
+            ESMI_RB_LAUNCH((hifigan_resblock_kernel<C, K>));
+        } else if constexpr (PM == PM_F16) {
+            ESMI_RB_LAUNCH((hifigan_resblock_amp_kernel<C, K>));
+        } else {
+            ESMI_RB_LAUNCH((hifigan_resblock_bf16_kernel<C, K>));
+        }
+#undef ESMI_RB_LAUNCH
+    }
+    return launch_status();
+}
+template <PrecisionMode PM, int C>
+int launch_resblock_c(const ResblockP& p, hipStream_t st) {
+    switch (p.k) {
+        case 3: return launch_resblock_ck<PM, C, 3>(p, st);
+        case 7: return launch_resblock_ck<PM, C, 7>(p, st);
+        case 11: return launch_resblock_ck<PM, C, 11>(p, st);
+    }
+    return ESMI_ERR_UNSUPPORTED;
+}
+template <PrecisionMode PM>
+int launch_resblock(const ResblockP& p, int c, hipStream_t st) {
+    if constexpr (precision_mode_built(PM)) {
+        switch (c) {
+            case 8: return launch_resblock_c<PM, 8>(p, st);
+            case 16: return launch_resblock_c<PM, 16>(p, st);
+            case 32: return launch_resblock_c<PM, 32>(p, st);
+            case 64: return launch_resblock_c<PM, 64>(p, st);
+        }
+    }
+    return ESMI_ERR_UNSUPPORTED;
+}
+// Each mode's twelve kernels compile in a unit of their own, side by side (ESMI_RESBLOCK_INSTANCE): tu_hifigan.hip, which also holds the
+// generator's host side (esmi_hifigan_*), tu_hifigan_amp.hip and tu_hifigan_bf16.hip.  No other unit instantiates the ladder:
+extern template int launch_resblock<PM_SPLIT>(const ResblockP&, int, hipStream_t);
+extern template int launch_resblock<PM_F16>(const ResblockP&, int, hipStream_t);
+extern template int launch_resblock<PM_BF16>(const ResblockP&, int, hipStream_t);
+#define ESMI_RESBLOCK_INSTANCE(PM) namespace esmi { template int launch_resblock<PM>(const ResblockP&, int, hipStream_t); }
 
 // Does enc_attn_ffn serve this block (the shapes it is instantiated for)?  Not beyond 128 positions: there the chain kernel runs one
 // latency chain per 32 rows against up to 256 keys, and the same ops as launches (LDS-staged attention + GEMMs) are faster (launches
@@ -129,48 +203,27 @@ inline bool enc_attn_ffn_supported(int C, int N, int expansion) {
 }
 
 // ---- activation-range check (esmi_dev.h, the ESMI_RANGE_CHECK build): every translation unit owns a copy of the device-side flag
-// pointer and defines its setter with ESMI_TU_RANGE_SETTER(<unit>); the validation mode of esmi_phoneme2mel_forward_f32 (esmi_abi.hip)
-// calls them all.
-int set_range_flag_abi(int* flag);
-int set_range_flag_convgemm(int* flag);
-int set_range_flag_convgemm_bf16(int* flag);
-int set_range_flag_attention(int* flag);
-int set_range_flag_enc_merge(int* flag);
-int set_range_flag_enc_block(int* flag);
-int set_range_flag_enc_attn_ffn(int* flag);
-int set_range_flag_enc_fuse_va(int* flag);
-int set_range_flag_enc_va16(int* flag);
-int set_range_flag_enc_va64(int* flag);
-int set_range_flag_enc_pred128(int* flag);
-int set_range_flag_enc_block16(int* flag);
-int set_range_flag_decoder(int* flag);
-int set_range_flag_dec_128_5(int* flag);
-int set_range_flag_dec_128_3(int* flag);
-int set_range_flag_dec_256_5(int* flag);
-int set_range_flag_dec_256_3(int* flag);
-int set_range_flag_dec_128_5_p16(int* flag);
-int set_range_flag_dec_128_3_p16(int* flag);
-int set_range_flag_dec_256_5_p16(int* flag);
-int set_range_flag_dec_256_3_p16(int* flag);
-int set_range_flag_dec_128_5_bf16(int* flag);
-int set_range_flag_dec_128_3_bf16(int* flag);
-int set_range_flag_dec_256_5_bf16(int* flag);
-int set_range_flag_dec_256_3_bf16(int* flag);
-int set_range_flag_hifigan(int* flag);
-int set_range_flag_hifigan_amp(int* flag);
-int set_range_flag_hifigan_bf16(int* flag);
-int set_range_flag_train(int* flag);
+// pointer.  ESMI_TU_RANGE_SETTER(<unit>) links the unit's setter into g_range_setters while the library loads (the head is constant-
+// initialised, so the order in which the units' nodes are constructed does not matter); the validation mode of
+// esmi_phoneme2mel_forward_curve_f32 (esmi_abi.hip) walks the list.  A unit with kernels that leaves the macro out is not range-checked.
+struct RangeSetter;
+extern RangeSetter* g_range_setters;   // esmi_abi.hip
+struct RangeSetter {
+    const char* unit;
+    int (*set)(int* flag);
+    RangeSetter* next;
+    RangeSetter(const char* unit_, int (*set_)(int*)) : unit(unit_), set(set_), next(g_range_setters) { g_range_setters = this; }
+};
+#if !ESMI_RANGE_CHECK
+inline int store_range_flag_pointer(int*) { return ESMI_OK; }   // (the unchecked builds have no flag to point at)
+#endif
+#define ESMI_TU_RANGE_SETTER(tu) namespace esmi { namespace { RangeSetter range_setter_##tu(#tu, store_range_flag_pointer); } }
 // development (-DESMI_CHAIN_TRACE): every translation unit with chain kernels owns a copy of the trace pointer
 #ifdef ESMI_CHAIN_TRACE
 #define ESMI_TU_CHAIN_TRACE_SETTER(tu) extern "C" void esmi_dev_set_chain_trace_##tu(long long* ptr) { \
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_chain_trace_dev), &ptr, sizeof(ptr)); }
 #else
 #define ESMI_TU_CHAIN_TRACE_SETTER(tu)
-#endif
-#if ESMI_RANGE_CHECK
-#define ESMI_TU_RANGE_SETTER(tu) namespace esmi { int set_range_flag_##tu(int* flag) { return store_range_flag_pointer(flag); } }
-#else
-#define ESMI_TU_RANGE_SETTER(tu) namespace esmi { int set_range_flag_##tu(int*) { return ESMI_OK; } }
 #endif
 
 }  // namespace esmi

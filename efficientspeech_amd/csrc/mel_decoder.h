@@ -172,7 +172,8 @@ __device__ __forceinline__ void dec_zero_acc(f32x16 (&acc)[MT][NTW]) {
 //                where the wave loads its slice (bf16_of_f16_planes); the accumulators then hold products with W itself.
 // Phases, barriers, LDS layout, grid and the chunk walk are those of the default kernel; every difference is an `if constexpr` on
 // P16 / BF / ONE below.
-enum DecPrecisionMode { DEC_PM_SPLIT = 0, DEC_PM_F16 = 1, DEC_PM_BF16 = 2 };
+using DecPrecisionMode = PrecisionMode;   // (esmi_types.h; the kernel body's names for its three values:)
+constexpr PrecisionMode DEC_PM_SPLIT = PM_SPLIT, DEC_PM_F16 = PM_F16, DEC_PM_BF16 = PM_BF16;
 template <int DX2, int KD, int NW, bool HALF16 = false>
 __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void mel_decoder_kernel(const MelDecP p) {
     constexpr int PM = HALF16 ? DEC_PM_F16 : DEC_PM_SPLIT;
@@ -185,60 +186,35 @@ __global__ __launch_bounds__(64 * NW, (DX2 <= 128 ? kDecWps128 : NW / 4)) void m
 #include "mel_decoder_body.h"
 }
 
-// ---- one instantiation: the launcher and the clock probe's setter of (DX2, KD), declared in dec_layout.h.  Each tu_dec_<dx2>_<k>.hip
-// is ESMI_DEC_INSTANCE(dx2, k) and nothing else: this kernel dominates the library's compile time, so the four build side by side.
-template <int DX2, int KD>
+// ---- one instantiation: the launcher and the clock probe's setter of (DX2, KD, PM), declared in dec_layout.h.  Each
+// tu_dec_<dx2>_<k>[_p16 | _bf16].hip is ESMI_DEC_INSTANCE(dx2, k, mode) and nothing else: this kernel dominates the library's compile
+// time, so the twelve build side by side.  A one-product mode in the exact-fp32 build has no kernel: its unit is then host code alone
+// that answers ESMI_ERR_UNSUPPORTED, and tu_decoder.hip's table holds NULL for it.
+template <int DX2, int KD, PrecisionMode PM>
 int set_dec_clock(long long* slots) { return store_dec_clock_pointer(slots); }
 
-template <int DX2, int KD>
+template <int DX2, int KD, PrecisionMode PM>
 int launch_mel_decoder(const MelDecP& p, dim3 grid, hipStream_t st) {
-    constexpr int NW = 8;   // waves per window (16 for dx2 = 256 measured 30 % slower: HISTORY.md 3.1)
-    const int lds = (dec_lds_floats<DX2>(KD) + p.carry_lds_layers * (KD / 2) * DX2) * (int)sizeof(float);
-    ESMI_LAUNCH_LDS((mel_decoder_kernel<DX2, KD, NW>), grid, dim3(64 * NW), lds, st, p);
-    return launch_status();
-}
-
-// ... and of the precision-16 kernel of (DX2, KD): tu_dec_<dx2>_<k>_p16.hip (split build only; an empty unit otherwise)
-template <int DX2, int KD>
-int set_dec_clock_p16(long long* slots) { return store_dec_clock_pointer(slots); }
-
-template <int DX2, int KD>
-int launch_mel_decoder_p16(const MelDecP& p, dim3 grid, hipStream_t st) {
-    constexpr int NW = 8;
-    const int lds = (dec_lds_floats<DX2>(KD) + p.carry_lds_layers * (KD / 2) * DX2) * (int)sizeof(float);
-    ESMI_LAUNCH_LDS((mel_decoder_kernel<DX2, KD, NW, true>), grid, dim3(64 * NW), lds, st, p);
-    return launch_status();
-}
-
-// ... and of the bf16 kernel: tu_dec_<dx2>_<k>_bf16.hip (split build only; an empty unit otherwise)
-template <int DX2, int KD>
-int set_dec_clock_bf16(long long* slots) { return store_dec_clock_pointer(slots); }
-
-template <int DX2, int KD>
-int launch_mel_decoder_bf16(const MelDecP& p, dim3 grid, hipStream_t st) {
-    constexpr int NW = 8;
-    const int lds = (dec_lds_floats<DX2>(KD) + p.carry_lds_layers * (KD / 2) * DX2) * (int)sizeof(float);
-    ESMI_LAUNCH_LDS((mel_decoder_bf16_kernel<DX2, KD, NW>), grid, dim3(64 * NW), lds, st, p);
-    return launch_status();
+    if constexpr (precision_mode_built(PM)) {
+        constexpr int NW = 8;   // waves per window (16 for dx2 = 256 measured 30 % slower: HISTORY.md 3.1)
+        const int lds = (dec_lds_floats<DX2>(KD) + p.carry_lds_layers * (KD / 2) * DX2) * (int)sizeof(float);
+        if constexpr (PM == PM_SPLIT) {
+            ESMI_LAUNCH_LDS((mel_decoder_kernel<DX2, KD, NW>), grid, dim3(64 * NW), lds, st, p);
+        } else if constexpr (PM == PM_F16) {
+            ESMI_LAUNCH_LDS((mel_decoder_kernel<DX2, KD, NW, true>), grid, dim3(64 * NW), lds, st, p);
+        } else {
+            ESMI_LAUNCH_LDS((mel_decoder_bf16_kernel<DX2, KD, NW>), grid, dim3(64 * NW), lds, st, p);
+        }
+        return launch_status();
+    }
+    return ESMI_ERR_UNSUPPORTED;
 }
 
 }  // namespace esmi
 
-#define ESMI_DEC_INSTANCE_BF16(DX2, KD)                                                               \
+#define ESMI_DEC_INSTANCE(DX2, KD, PM)                                                                \
+    ESMI_TU_RANGE_SETTER(dec_##DX2##_##KD##_##PM)                                                     \
     namespace esmi {                                                                                  \
-    template int set_dec_clock_bf16<DX2, KD>(long long*);                                             \
-    template int launch_mel_decoder_bf16<DX2, KD>(const MelDecP&, dim3, hipStream_t);                 \
-    }
-
-#define ESMI_DEC_INSTANCE_P16(DX2, KD)                                                                \
-    namespace esmi {                                                                                  \
-    template int set_dec_clock_p16<DX2, KD>(long long*);                                              \
-    template int launch_mel_decoder_p16<DX2, KD>(const MelDecP&, dim3, hipStream_t);                  \
-    }
-
-#define ESMI_DEC_INSTANCE(DX2, KD)                                                                    \
-    ESMI_TU_RANGE_SETTER(dec_##DX2##_##KD)                                                            \
-    namespace esmi {                                                                                  \
-    template int set_dec_clock<DX2, KD>(long long*);                                                  \
-    template int launch_mel_decoder<DX2, KD>(const MelDecP&, dim3, hipStream_t);                      \
+    template int set_dec_clock<DX2, KD, PM>(long long*);                                              \
+    template int launch_mel_decoder<DX2, KD, PM>(const MelDecP&, dim3, hipStream_t);                  \
     }

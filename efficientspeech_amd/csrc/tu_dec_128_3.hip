@@ -2,4 +2,4 @@
 #include "launch.h"
 #include "mel_decoder.h"
 
-ESMI_DEC_INSTANCE(128, 3)
+ESMI_DEC_INSTANCE(128, 3, PM_SPLIT)

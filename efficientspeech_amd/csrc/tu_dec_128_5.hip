@@ -2,4 +2,4 @@
 #include "launch.h"
 #include "mel_decoder.h"
 
-ESMI_DEC_INSTANCE(128, 5)
+ESMI_DEC_INSTANCE(128, 5, PM_SPLIT)

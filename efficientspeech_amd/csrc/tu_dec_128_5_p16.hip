@@ -1,11 +1,5 @@
-// esmi C-ABI, translation unit "tu_dec_128_5_p16.hip": mel_decoder_kernel<128, 5, NW, true> -- the precision-16 form (include/esmi.h) -- and its
-// launcher (mel_decoder.h, ESMI_DEC_INSTANCE_P16).  The exact-fp32 build has no binary16 products: no kernel in this unit there.
+// esmi C-ABI, translation unit "tu_dec_128_5_p16.hip": mel_decoder_kernel<128, 5, NW, true>, the precision-16 form (include/esmi.h), and its launcher (mel_decoder.h, ESMI_DEC_INSTANCE)
 #include "launch.h"
-#include "dec_layout.h"
-
-ESMI_TU_RANGE_SETTER(dec_128_5_p16)
-#if ESMI_DEC_SPLIT == 2
 #include "mel_decoder.h"
 
-ESMI_DEC_INSTANCE_P16(128, 5)
-#endif
+ESMI_DEC_INSTANCE(128, 5, PM_F16)

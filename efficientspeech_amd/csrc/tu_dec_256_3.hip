@@ -2,4 +2,4 @@
 #include "launch.h"
 #include "mel_decoder.h"
 
-ESMI_DEC_INSTANCE(256, 3)
+ESMI_DEC_INSTANCE(256, 3, PM_SPLIT)

@@ -1,11 +1,5 @@
-// esmi C-ABI, translation unit "tu_dec_256_3_p16.hip": mel_decoder_kernel<256, 3, NW, true> -- the precision-16 form (include/esmi.h) -- and its
-// launcher (mel_decoder.h, ESMI_DEC_INSTANCE_P16).  The exact-fp32 build has no binary16 products: no kernel in this unit there.
+// esmi C-ABI, translation unit "tu_dec_256_3_p16.hip": mel_decoder_kernel<256, 3, NW, true>, the precision-16 form (include/esmi.h), and its launcher (mel_decoder.h, ESMI_DEC_INSTANCE)
 #include "launch.h"
-#include "dec_layout.h"
-
-ESMI_TU_RANGE_SETTER(dec_256_3_p16)
-#if ESMI_DEC_SPLIT == 2
 #include "mel_decoder.h"
 
-ESMI_DEC_INSTANCE_P16(256, 3)
-#endif
+ESMI_DEC_INSTANCE(256, 3, PM_F16)

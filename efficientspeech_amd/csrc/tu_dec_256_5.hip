@@ -2,4 +2,4 @@
 #include "launch.h"
 #include "mel_decoder.h"
 
-ESMI_DEC_INSTANCE(256, 5)
+ESMI_DEC_INSTANCE(256, 5, PM_SPLIT)

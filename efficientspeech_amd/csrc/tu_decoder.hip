@@ -1,5 +1,5 @@
 // esmi C-ABI, translation unit "tu_decoder.hip": the mel decoder: blob packer and mel_decoder_kernel launches (dec_layout.h; the kernel
-// itself, mel_decoder.h, is compiled by the tu_dec_<dx2>_<k>.hip units)
+// itself, mel_decoder.h, is compiled by the tu_dec_<dx2>_<k>[_p16 | _bf16].hip units, one per shape and precision mode)
 // One of several translation units of libesmi.so (compiled in parallel by __graft_entry__.build(); the simulator build
 // tools/wavesim/build.sh compiles the same files with the host compiler).  Internal launchers are declared in launch.h.
 #include "launch.h"
@@ -65,28 +65,22 @@ int dec_pack(const esmi_decoder_weights* w, const esmi_decoder_shape* s, float* 
     return launch_status();
 }
 
-// the (dx2, kernel) instantiations: launcher and clock-probe setter (defined in tu_dec_<dx2>_<k>.hip), those of the precision-16 kernel
-// (tu_dec_<dx2>_<k>_p16.hip) and of the bf16 kernel (tu_dec_<dx2>_<k>_bf16.hip) -- NULL in the exact-fp32 build, which has no one-product
-// path --, blob size and packer
+// the (dx2, kernel) instantiations: per mode the launcher and the clock-probe setter (defined in tu_dec_<dx2>_<k>[_p16 | _bf16].hip; NULL
+// where the build has no such kernel: the exact-fp32 build has no one-product path), blob size and packer
 struct DecInst {
     int dx2, kd;
-    int (*launch)(const MelDecP&, dim3, hipStream_t);
-    int (*set_clock)(long long*);
-    int (*launch16)(const MelDecP&, dim3, hipStream_t);
-    int (*set_clock16)(long long*);
-    int (*launch_bf16)(const MelDecP&, dim3, hipStream_t);
-    int (*set_clock_bf16)(long long*);
+    int (*launch[kPrecisionModes])(const MelDecP&, dim3, hipStream_t);
+    int (*set_clock[kPrecisionModes])(long long*);
     long (*blob_floats)(int d4, int n_blocks, int block_depth);
     int (*pack)(const esmi_decoder_weights*, const esmi_decoder_shape*, float*, hipStream_t);
 };
 template <int DX2, int KD>
 constexpr DecInst dec_inst_of() {
-#if ESMI_DEC_SPLIT == 2
-    return {DX2, KD, launch_mel_decoder<DX2, KD>, set_dec_clock<DX2, KD>, launch_mel_decoder_p16<DX2, KD>, set_dec_clock_p16<DX2, KD>,
-            launch_mel_decoder_bf16<DX2, KD>, set_dec_clock_bf16<DX2, KD>, DecLay<DX2, KD>::floats, dec_pack<DX2, KD>};
-#else
-    return {DX2, KD, launch_mel_decoder<DX2, KD>, set_dec_clock<DX2, KD>, nullptr, nullptr, nullptr, nullptr, DecLay<DX2, KD>::floats, dec_pack<DX2, KD>};
-#endif
+    constexpr bool f16 = precision_mode_built(PM_F16), bf16 = precision_mode_built(PM_BF16);
+    return {DX2, KD,
+            {launch_mel_decoder<DX2, KD, PM_SPLIT>, f16 ? launch_mel_decoder<DX2, KD, PM_F16> : nullptr, bf16 ? launch_mel_decoder<DX2, KD, PM_BF16> : nullptr},
+            {set_dec_clock<DX2, KD, PM_SPLIT>, f16 ? set_dec_clock<DX2, KD, PM_F16> : nullptr, bf16 ? set_dec_clock<DX2, KD, PM_BF16> : nullptr},
+            DecLay<DX2, KD>::floats, dec_pack<DX2, KD>};
 }
 const DecInst kDecInst[] = {dec_inst_of<128, 5>(), dec_inst_of<128, 3>(), dec_inst_of<256, 5>(), dec_inst_of<256, 3>()};
 const DecInst* dec_inst(const esmi_decoder_shape* s) {   // (after dec_check: the shape is one of the table's)
@@ -102,13 +96,10 @@ extern "C" {
 // measurement aid (include/esmi.h): arm / disarm the clock probe of every decoder instantiation (one device global per unit)
 int esmi_mel_decoder_clock_probe(int64_t* dev_slots) {
     long long* s = reinterpret_cast<long long*>(dev_slots);
-    for (const DecInst& d : kDecInst) {
-        if (int rc = d.set_clock(s)) return rc;
-        if (d.set_clock16)
-            if (int rc = d.set_clock16(s)) return rc;
-        if (d.set_clock_bf16)
-            if (int rc = d.set_clock_bf16(s)) return rc;
-    }
+    for (const DecInst& d : kDecInst)
+        for (auto set_clock : d.set_clock)
+            if (set_clock)
+                if (int rc = set_clock(s)) return rc;
     return ESMI_OK;
 }
 
@@ -182,7 +173,8 @@ int esmi_mel_decoder_prec_f32(const float* blob, const esmi_decoder_shape* s, co
                               int L_out, float* mel, void* workspace, size_t workspace_bytes, int precision, esmi_stream_t stream) {
     // precision (include/esmi.h): 0 / 32 the fp32-accurate kernel; 16 one binary16 product per contraction; ESMI_PRECISION_BF16 one
     // bfloat16 product; anything else is refused before anything else
-    if (precision != 0 && precision != 32 && precision != 16 && precision != ESMI_PRECISION_BF16) return ESMI_ERR_ARG;
+    PrecisionMode mode;
+    if (int rc = precision_mode(precision, &mode)) return rc;
     int rc = dec_check(s);
     if (rc) return rc;
     if (!blob || (!x && !h0) || !mel || B <= 0 || L_out <= 0 || !aligned16(blob) || (x && !aligned16(x))) return ESMI_ERR_ARG;
@@ -193,7 +185,7 @@ int esmi_mel_decoder_prec_f32(const float* blob, const esmi_decoder_shape* s, co
     MelDecP p;
     p.blob = blob;
     const DecInst* inst = dec_inst(s);
-    if ((precision == 16 && !inst->launch16) || (precision == ESMI_PRECISION_BF16 && !inst->launch_bf16)) return ESMI_ERR_UNSUPPORTED;   // (checked before the first launch: nothing is enqueued)
+    if (!inst->launch[mode]) return ESMI_ERR_UNSUPPORTED;   // (checked before the first launch: nothing is enqueued)
     if (inst->blob_floats(s->d4, s->n_blocks, s->block_depth) > kDecBlobMaxFloats) return ESMI_ERR_UNSUPPORTED;
     p.d4 = s->d4; p.n_blocks = s->n_blocks; p.block_depth = s->block_depth; p.n_mel = s->n_mel;
     p.x = x; p.h0 = h0; p.cum = cum; p.mel_len = mel_len; p.lmax_dev = lmax_dev; p.lmax_host = lmax_host;
@@ -224,8 +216,7 @@ int esmi_mel_decoder_prec_f32(const float* blob, const esmi_decoder_shape* s, co
         p.n_seg = (L_out + p.seg_len - 1) / p.seg_len;
     }
     dim3 grid((unsigned)(p.n_seg * ((B + 7) / 8) * 8)), block(kDecThreads);
-    if (precision == ESMI_PRECISION_BF16) return inst->launch_bf16(p, grid, st);
-    return precision == 16 ? inst->launch16(p, grid, st) : inst->launch(p, grid, st);
+    return inst->launch[mode](p, grid, st);
 }
 
 int esmi_mel_decoder_f32(const float* blob, const esmi_decoder_shape* s, const float* x, const float* h0,

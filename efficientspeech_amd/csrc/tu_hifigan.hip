@@ -7,44 +7,7 @@
 using namespace esmi;
 ESMI_TU_RANGE_SETTER(hifigan)
 
-namespace esmi {
-
-// One ResBlock in one launch (hifigan_resblock.h) when its packed weights are there and (channels, kernel size) has an
-// instantiation; `false` from resblock_fused_ok -> the caller runs the block conv by conv.
-template <int C, int K>
-int launch_resblock_ck(const ResblockP& p, hipStream_t st) {
-    const size_t lds = rb_lds_bytes(C, p.R);
-    const dim3 grid((unsigned)(p.B * p.tiles_per_b)), block(64 * kRbWaves);
-    if constexpr (C <= 16) {   // narrow MFMA tiles (16 channels x 16 positions): LDS <= 32 KB, no limit to raise
-        ESMI_LAUNCH((hifigan_resblock16_kernel<C, K>), grid, block, lds, st, p);
-    } else {
-        static AttrOnce once;
-        if (lds > 48 * 1024)
-            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(hifigan_resblock_kernel<C, K>), once)) return rc;
-        ESMI_LAUNCH((hifigan_resblock_kernel<C, K>), grid, block, lds, st, p);
-    }
-    return launch_status();
-}
-template <int C>
-int launch_resblock_c(const ResblockP& p, hipStream_t st) {
-    switch (p.k) {
-        case 3: return launch_resblock_ck<C, 3>(p, st);
-        case 7: return launch_resblock_ck<C, 7>(p, st);
-        case 11: return launch_resblock_ck<C, 11>(p, st);
-    }
-    return ESMI_ERR_UNSUPPORTED;
-}
-int launch_resblock(const ResblockP& p, int c, hipStream_t st) {
-    switch (c) {
-        case 8: return launch_resblock_c<8>(p, st);
-        case 16: return launch_resblock_c<16>(p, st);
-        case 32: return launch_resblock_c<32>(p, st);
-        case 64: return launch_resblock_c<64>(p, st);
-    }
-    return ESMI_ERR_UNSUPPORTED;
-}
-
-}  // namespace esmi
+ESMI_RESBLOCK_INSTANCE(PM_SPLIT)   // the fp32-accurate ResBlock kernels (launch.h has the ladder)
 
 // ------------------------------------------------------------------ the generator's host side
 namespace {
@@ -100,8 +63,8 @@ HgMargins hg_margins(const esmi_hifigan_shape* s) {
     return g;
 }
 
-// amp (precision 16 and bf16): the window of the one-product kernels -- half the LDS per row, and 16 waves at 64 channels (rb_amp_rmax)
-bool resblock_fused_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, int rb, int c, int k, int n, bool amp, ResblockP* o) {
+// mode: precision 16 and bf16 have the window of the one-product kernels -- half the LDS per row, and 16 waves at 64 channels (rb_amp_rmax)
+bool resblock_fused_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, int rb, int c, int k, int n, PrecisionMode mode, ResblockP* o) {
 #if !ESMI_CHAIN_SPLIT
     return false;   // the exact-fp32 build keeps the per-conv fp32-MFMA launches
 #endif
@@ -120,7 +83,7 @@ bool resblock_fused_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* 
         }
     }
     // 8 waves = 8 (row pair, 32-channel tile) items; LDS <= 80 KB: two workgroups per CU
-    const int r_max = amp ? rb_amp_rmax(c) : (c == 64 ? 256 : 512);
+    const int r_max = mode != PM_SPLIT ? rb_amp_rmax(c) : (c == 64 ? 256 : 512);
     int R = ((n + 2 * halo + 63) / 64) * 64;
     R = R < r_max ? R : r_max;
     if (R - 2 * halo < 32 && R - 2 * halo < n) return false;
@@ -144,11 +107,11 @@ struct HgStage {
 
 // ResBlock rb of stage g one launch per convolution: x (+)= block(y), j = rb % n_kernels > 0 accumulates; r, t: the block's own state
 int resblock_conv_by_conv(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const HgStage& g, int rb, const float* y, float* x,
-                          float* r, float* t, int amp, hipStream_t st) {
+                          float* r, float* t, PrecisionMode mode, hipStream_t st) {
     const int j = rb % s->n_kernels, k = s->rb_kernels[j], nconv = s->resblock == 1 ? 3 : 2, c = g.c;
     auto conv = [&](int dil, const float* in, const float* wt, const float* bias, float* out) {   // out = conv(leaky_relu(in))
         ConvGemmP p = conv1d(g.B, g.n, c, c, k, dil, in, c, {wt, nullptr}, bias, out, c);
-        p.act_in = 1; p.act_in_slope = kSlope; p.amp = amp;
+        p.act_in = 1; p.act_in_slope = kSlope; p.amp = mode;
         g.limit(&p);
         return p;
     };
@@ -179,14 +142,14 @@ int resblock_conv_by_conv(const esmi_hifigan_weights* w, const esmi_hifigan_shap
 // Every weight the call is going to read, looked at before the first launch: conv_pre, conv_post and the ConvTranspose1d's their fp32
 // tensor and bias; a ResBlock that runs as one launch (fp[rb].n_conv > 0 then, and fp[rb] holds its parameters) its packed weights
 // and biases (resblock_fused_ok has looked), any other its fp32 tensors and biases.
-bool hg_weights_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, int L, bool amp, ResblockP* fp) {
+bool hg_weights_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, int L, PrecisionMode mode, ResblockP* fp) {
     bool ok = w->pre_w && w->pre_b && w->post_w && w->post_b;
     int n = L, c = s->initial_channel;
     for (int i = 0, rb = 0; i < s->n_up; ++i) {
         ok = ok && w->up_w[i] && w->up_b[i];
         n *= s->up_rates[i]; c /= 2;
         for (int j = 0; j < s->n_kernels; ++j, ++rb) {
-            if (resblock_fused_ok(w, s, rb, c, s->rb_kernels[j], n, amp, &fp[rb])) continue;
+            if (resblock_fused_ok(w, s, rb, c, s->rb_kernels[j], n, mode, &fp[rb])) continue;
             fp[rb].n_conv = 0;
             for (int m = rb * 3; m < rb * 3 + (s->resblock == 1 ? 3 : 2); ++m)
                 ok = ok && w->rb_w1[m] && w->rb_b1[m] && (s->resblock == 2 || (w->rb_w2[m] && w->rb_b2[m]));
@@ -208,24 +171,26 @@ bool hg_weights_ok(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, i
 int hifigan_generator(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s, const float* mel, int B, int L,
                       const int32_t* mel_len, float* wav, int16_t* pcm, int precision, void* workspace, size_t workspace_bytes,
                       esmi_stream_t stream) {
-    if (precision != 0 && precision != 32 && precision != 16 && precision != ESMI_PRECISION_BF16) return ESMI_ERR_ARG;
-    const int amp = precision == 16 ? 1 : (precision == ESMI_PRECISION_BF16 ? 2 : 0);   // ConvGemmP::amp of the per-convolution launches
+    PrecisionMode mode;   // which ResBlock kernels, and ConvGemmP::amp of the per-convolution launches
+    if (int rc = precision_mode(precision, &mode)) return rc;
     size_t buf;
     int rc = hg_plan(s, B, L, &buf);
     if (rc) return rc;
-    if (amp && !ESMI_CHAIN_SPLIT) return ESMI_ERR_UNSUPPORTED;   // the exact-fp32 build has no one-product path
+    if (!precision_mode_built(mode)) return ESMI_ERR_UNSUPPORTED;   // the exact-fp32 build has no one-product path
     if (!w || !mel || (!wav && !pcm) || !workspace) return ESMI_ERR_ARG;
     if (workspace_bytes < 4 * buf) return ESMI_ERR_WORKSPACE;
     ResblockP fused[ESMI_HIFIGAN_MAX_RBCONV / 3];   // (hg_plan: n_up . n_kernels fit)
-    if (!hg_weights_ok(w, s, L, amp != 0, fused)) return ESMI_ERR_ARG;
+    if (!hg_weights_ok(w, s, L, mode, fused)) return ESMI_ERR_ARG;
     const HgMargins mg = hg_margins(s);
+    static constexpr decltype(&launch_resblock<PM_SPLIT>) kLaunchResblock[kPrecisionModes] = {launch_resblock<PM_SPLIT>, launch_resblock<PM_F16>,
+                                                                                              launch_resblock<PM_BF16>};
     hipStream_t st = S(stream);
     auto ws = [&](int q) { return reinterpret_cast<float*>(static_cast<char*>(workspace) + q * buf); };
     float *x = ws(0), *y = ws(1), *r = ws(2), *t = ws(3);   // x: stage input / sum over the ResBlocks; y: upsampled; r, t: ResBlock state
     HgStage g = {B, L, s->initial_channel, nullptr, 0, 0, 0};
     // conv_pre, models.py:112: Conv1d(n_mel, C0, 7, padding 3)
     ConvGemmP p = conv1d(B, L, s->n_mel, g.c, 7, 1, mel, s->n_mel, {w->pre_w, nullptr}, w->pre_b, x, g.c);
-    p.amp = amp;
+    p.amp = mode;
     if ((rc = launch_convgemm(p, st))) return rc;
     float in_scale = 1.0f;           // the mean over the ResBlocks of the previous stage, folded into the next input activation
     for (int i = 0; i < s->n_up; ++i) {
@@ -235,7 +200,7 @@ int hifigan_generator(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s
         g = HgStage{B, in.n * u, in.c / 2, lim ? mel_len : nullptr, L, mg.mul[i], mg.add[i]};
         // x = ups[i](leaky_relu(x, 0.1)), models.py:114-115: ConvTranspose1d(c, c/2, k, u, padding (k-u)//2)
         p = conv_transpose1d(B, in.n, g.n, in.c, g.c, k, u, (k - u) / 2, x, in.c, {w->up_w[i], nullptr}, w->up_b[i], y, g.c);
-        p.act_in = 1; p.act_in_slope = kSlope; p.a_scale = in_scale; p.amp = amp;
+        p.act_in = 1; p.act_in_slope = kSlope; p.a_scale = in_scale; p.amp = mode;
         g.limit(&p);
         if ((rc = launch_convgemm(p, st))) return rc;
         for (int j = 0; j < s->n_kernels; ++j) {   // xs += resblocks[i*num_kernels + j](x), models.py:116-121
@@ -244,9 +209,9 @@ int hifigan_generator(const esmi_hifigan_weights* w, const esmi_hifigan_shape* s
             if (fp.n_conv) {   // the whole block on an LDS-resident window: y -> x (+)=
                 fp.x = y; fp.out = x; fp.B = B; fp.accum = j > 0; fp.slope = kSlope;
                 g.limit(&fp);
-                rc = amp == 2 ? launch_resblock_bf16(fp, g.c, st) : (amp ? launch_resblock_amp(fp, g.c, st) : launch_resblock(fp, g.c, st));
+                rc = kLaunchResblock[mode](fp, g.c, st);
             } else {
-                rc = resblock_conv_by_conv(w, s, g, rb, y, x, r, t, amp, st);
+                rc = resblock_conv_by_conv(w, s, g, rb, y, x, r, t, mode, st);
             }
             if (rc) return rc;
         }

@@ -1,51 +1,11 @@
 // esmi C-ABI, translation unit "tu_hifigan_amp.hip": the one-launch ResBlock kernels of the HiFi-GAN generator at precision 16
 // (hifigan_resblock.h: one binary16 product per contraction).  A unit of its own: its twelve instantiations compile beside
-// tu_hifigan.hip's instead of behind them.  The generator's host side (tu_hifigan.hip) decides when they run.
+// tu_hifigan.hip's instead of behind them (launch.h has the ladder they hang on; the exact-fp32 build has none of them).  The generator's
+// host side (tu_hifigan.hip) decides when they run.
 // One of several translation units of libesmi.so (compiled in parallel by __graft_entry__.build(); the simulator build
 // tools/wavesim/build.sh compiles the same files with the host compiler).  Internal launchers are declared in launch.h.
 #include "launch.h"
 
 using namespace esmi;
 ESMI_TU_RANGE_SETTER(hifigan_amp)
-
-namespace esmi {
-
-#if ESMI_CHAIN_SPLIT
-template <int C, int K>
-int launch_resblock_amp_ck(const ResblockP& p, hipStream_t st) {
-    const size_t lds = rb_amp_lds_bytes(C, p.R);
-    const dim3 grid((unsigned)(p.B * p.tiles_per_b));
-    if (p.R > rb_amp_rmax(C)) return ESMI_ERR_ARG;   // (rows past the waves' items would never be computed)
-    if constexpr (C <= 16) {   // narrow MFMA tiles (16 channels x 16 positions): LDS <= 16 KB
-        ESMI_LAUNCH((hifigan_resblock16_amp_kernel<C, K>), grid, dim3(64 * kRbWaves), lds, st, p);
-    } else {
-        static AttrOnce once;
-        if (lds > 48 * 1024)
-            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(hifigan_resblock_amp_kernel<C, K>), once)) return rc;
-        ESMI_LAUNCH((hifigan_resblock_amp_kernel<C, K>), grid, dim3(64 * rb_amp_waves(C)), lds, st, p);
-    }
-    return launch_status();
-}
-template <int C>
-int launch_resblock_amp_c(const ResblockP& p, hipStream_t st) {
-    switch (p.k) {
-        case 3: return launch_resblock_amp_ck<C, 3>(p, st);
-        case 7: return launch_resblock_amp_ck<C, 7>(p, st);
-        case 11: return launch_resblock_amp_ck<C, 11>(p, st);
-    }
-    return ESMI_ERR_UNSUPPORTED;
-}
-int launch_resblock_amp(const ResblockP& p, int c, hipStream_t st) {
-    switch (c) {
-        case 8: return launch_resblock_amp_c<8>(p, st);
-        case 16: return launch_resblock_amp_c<16>(p, st);
-        case 32: return launch_resblock_amp_c<32>(p, st);
-        case 64: return launch_resblock_amp_c<64>(p, st);
-    }
-    return ESMI_ERR_UNSUPPORTED;
-}
-#else
-int launch_resblock_amp(const ResblockP&, int, hipStream_t) { return ESMI_ERR_UNSUPPORTED; }   // the exact-fp32 build has no precision 16
-#endif
-
-}  // namespace esmi
+ESMI_RESBLOCK_INSTANCE(PM_F16)

@@ -12,7 +12,8 @@ extern "C" {
 // ------------------------------------------------------------------ training step (csrc/train_ops.h)
 namespace {
 int conv_desc_ok(const esmi_conv_desc* d, ConvDesc* o) {
-    if (d && d->precision != 0 && d->precision != 16 && d->precision != 32 && d->precision != ESMI_PRECISION_BF16) return ESMI_ERR_ARG;
+    PrecisionMode mode;
+    if (d && precision_mode(d->precision, &mode)) return ESMI_ERR_ARG;
     if (!d || d->B <= 0 || d->n_in <= 0 || d->n_out <= 0 || d->c_in <= 0 || d->c_out <= 0 || d->k <= 0 || d->stride <= 0 || d->pad < 0 ||
         d->groups <= 0)
         return ESMI_ERR_ARG;
@@ -161,14 +162,18 @@ int measure_absmax(const ConvDesc& c, const float* dy, int* amax, hipStream_t st
     ESMI_LAUNCH(absmax_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, st, dy, len, amax);
     return launch_status();
 }
-// ConvGemmP::amp of a descriptor's GEMMs: 0 fp32-accurate, 1 binary16 operands, 2 bfloat16 operands
-inline int gemm_amp(const esmi_conv_desc* d) { return d->precision == 16 ? 1 : d->precision == ESMI_PRECISION_BF16 ? 2 : 0; }
+// the mode of a descriptor's GEMMs, ConvGemmP::amp (conv_desc_ok has refused a precision that has none)
+inline PrecisionMode gemm_mode(const esmi_conv_desc* d) {
+    PrecisionMode mode = PM_SPLIT;
+    (void)precision_mode(d->precision, &mode);
+    return mode;
+}
 struct ConvLnArgs { const float *res, *g, *b; const unsigned char* rowmask; int relu_out; float *pre, *mean, *rstd; };
 // one of the two implicit-GEMM problems of a dense conv.  wg: the weight as the GEMM reads it; io_scale (data gradient): the slot max|dy| sits in
 int launch_conv_gemm(const ConvDesc& c, const GemmWeight& g, bool grad, const float* in, const float* wg, const float* bias, float* out,
-                     int amp, const int* io_scale, int act, const ConvLnArgs* ln, hipStream_t st) {
+                     PrecisionMode amp, const int* io_scale, int act, const ConvLnArgs* ln, hipStream_t st) {
     ConvGemmP p = conv_defaults();
-    p.io_scale = amp == 2 ? nullptr : reinterpret_cast<const float*>(io_scale);   // (bfloat16 has fp32's exponent range: nothing to scale)
+    p.io_scale = amp == PM_BF16 ? nullptr : reinterpret_cast<const float*>(io_scale);   // (bfloat16 has fp32's exponent range: nothing to scale)
     p.mode = (g.as_convT && !g.flipped) ? MODE_CONVT : MODE_CONV;
     p.k = c.k; p.stride = c.stride; p.pad = g.flipped ? c.k - 1 - c.pad : c.pad;
     p.B = c.B; p.n_in = grad ? c.n_out : c.n_in; p.n_out = grad ? c.n_in : c.n_out; p.c_in = g.cin; p.c_out = g.cout;
@@ -194,8 +199,8 @@ int conv_gemm(const esmi_conv_desc* d, const ConvDesc& c, bool grad, const float
     if (ln && g.cout != 32 && g.cout != 64 && g.cout != 128) return ESMI_ERR_UNSUPPORTED;
     if (g.copy && !wc.packed)
         if (int rc = pack_weight(c, g, grad, w, wc.wt, st)) return rc;
-    const int amp = gemm_amp(d);
-    int* amax = (grad && amp != 2) ? absmax_slot(wc.wt, c) : nullptr;
+    const PrecisionMode amp = gemm_mode(d);
+    int* amax = (grad && amp != PM_BF16) ? absmax_slot(wc.wt, c) : nullptr;
     if (amax)
         if (int rc = measure_absmax(c, in, amax, st)) return rc;
     return launch_conv_gemm(c, g, grad, in, g.copy ? wc.wt : w, bias, out, amp, amax, grad ? 0 : d->act, ln, st);
@@ -319,8 +324,8 @@ int esmi_train_conv_bwd_f32(const esmi_conv_desc* d, const float* x, const float
     if (gemm_bytes > 0 && p.mfma && g.ok) {
         // dense shapes whose two gradients both run on the matrix pipe: tap-major weight copy (zeroes the absmax slot) -> weight gradient
         // (leaves max|dy| in the slot) -> its reduction -> data-gradient GEMM scaled by it (bf16: no max, no scale)
-        const int amp = gemm_amp(d);
-        int* amax = amp == 2 ? nullptr : absmax_slot(wc.wt, c);
+        const PrecisionMode amp = gemm_mode(d);
+        int* amax = amp == PM_BF16 ? nullptr : absmax_slot(wc.wt, c);
         if (!wc.packed)
             if (int rc = pack_weight(c, g, true, w, wc.wt, S(stream))) return rc;
         if (int rc = conv_wgrad(c, p, x, dy, dw, dbias, part, amax, defer, S(stream))) return rc;
