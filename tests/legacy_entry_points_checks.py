@@ -5,7 +5,7 @@
     esmi_variance_adaptor_f32 / _ctl_f32                      -> esmi_variance_adaptor_curve_f32
 
 The Python modules only call the general forms, so nothing else runs the older ones.  (The mel decoder pair is
-decoder_precision16_checks.check_entry_points_at_32.)  tests/test_legacy_entry_points.py runs the checks through the wave simulator and
+precision_checks.check_entry_points.)  tests/test_legacy_entry_points.py runs the checks through the wave simulator and
 on the device.  Tiny ES at prosody_control_checks.SHAPE (B = 3, T = 17, lengths (17, 9, 1)); every output buffer is filled with NaN
 (its bit pattern in the int32 ones) before each call, and every comparison is `array_equal` on all of them: a NaN left anywhere fails it."""
 import ctypes as C

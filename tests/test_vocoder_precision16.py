@@ -1,7 +1,7 @@
 """The HiFi-GAN generator at precision 16: esmi_hifigan_generator_prec_f32, Generator(h, precision) / Generator.forward(..., precision),
-get_hifigan(..., precision), EfficientSpeech.synthesize(..., precision).  The checks and the fp64 yardstick live in
-tests/vocoder_precision16_checks.py; the GPU tier runs them on the device, the CPU tier through the wave simulator (the same kernel
-sources compiled for the host).
+get_hifigan(..., precision), EfficientSpeech.synthesize(..., precision).  The checks, the operand rule `R16` and the fp64 yardstick live
+in tests/precision_checks.py, which tests/test_inference_bf16.py runs with the bf16 rule.  A test marked `gpu` gets the device from the
+`device` fixture, the others "cpu" with the wave simulator bound (the same kernel sources compiled for the host).
 
 To re-record the launch table after an intended change of the launches: `python -m tests.test_vocoder_precision16` prints it.
 """
@@ -14,90 +14,73 @@ import textwrap
 
 import pytest
 
-from tests import vocoder_precision16_checks as V
-from tests.simlib import use_sim
+from tests import precision_checks as V
+from tests.precision_checks import R16, device, yard   # noqa: F401 (fixtures)
 
-DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "efficientspeech_amd", "libesmi.so")
 TOOLS = ["/opt/rocm/lib/llvm/bin/clang-offload-bundler", "/opt/rocm/lib/llvm/bin/llvm-readelf"]
 
 
-@pytest.fixture(scope="module")
-def yard():
-    """the fp64 yardsticks the accuracy tests share (computed on first use), released when this module's tests are done"""
-    y = V.Yardsticks()
-    yield y
-    y.clear()
-
-
-# ---------------------------------------------------------------------------------------------------------------- test 0 (CPU, no kernels)
 @pytest.mark.parametrize("config", ["v1", "v2", "v3"])
 def test_fp64_mirror_matches_the_reference_fixtures(config, yard):
     """the yardstick's exact mode against the committed reference waveforms: < 2e-6 L-inf"""
-    V.check_mirror_matches_fixture(yard, config)
+    V.check_mirror_matches_fixture(yard, R16, config)
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU tier
 @pytest.mark.gpu
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "convs"])
 @pytest.mark.parametrize("config", ["v1", "v2", "v3"])
-def test_precision16_error_is_the_binary16_operand_error(config, fused, yard):
-    """Test 1 on the three fixture shapes.  v2 covers all twelve (C, K) one-product ResBlock1 instantiations; v3 ResBlock2 with n_conv = 2
-    and its k = 5 blocks conv by conv; v1 the 256- / 128-channel stages on convgemm_dma_kernel<..., true, ...>.
-    (The ratios are printed with -s; the simulator's are in profiles/r10_vocoder_precision16.md, the device's are not recorded yet.)"""
-    V.check_accuracy(yard, config, DEV, fused)
+def test_precision16_error_is_the_binary16_operand_error(config, fused, yard, device):
+    """the three fixture shapes.  v2 covers all twelve (C, K) one-product ResBlock1 instantiations; v3 ResBlock2 with n_conv = 2 and its
+    k = 5 blocks conv by conv; v1 the 256- / 128-channel stages on convgemm_dma_kernel<..., true, ...>."""
+    V.check_vocoder_accuracy(yard, R16, config, device, fused)
 
 
 @pytest.mark.gpu
-def test_precision16_ragged_keeps_its_contract():
-    """Test 2: v2, B = 4, L = 64, lengths [64, 33, 9, 0], one launch per ResBlock and conv by conv."""
-    V.check_ragged_contract("v2", 4, 64, [64, 33, 9, 0], DEV)
+def test_precision16_ragged_keeps_its_contract(device):
+    """v2, B = 4, L = 64, lengths [64, 33, 9, 0], one launch per ResBlock and conv by conv"""
+    V.check_ragged_contract(R16, "v2", 4, 64, [64, 33, 9, 0], device)
 
 
 @pytest.mark.gpu
-def test_precision_0_and_32_are_the_existing_entry_points():
-    """Test 3 on the device: v2, B = 2, L = 24 (two windows in the first stage of the default path), lengths [24, 5]."""
-    V.check_default_untouched("v2", 2, 24, [24, 5], DEV)
+def test_precision_0_and_32_are_the_existing_entry_points(device):
+    """v2, B = 2, L = 24 (two windows in the first stage of the default path), lengths [24, 5]"""
+    V.check_default_untouched(R16, "v2", 2, 24, [24, 5], device)
 
 
 @pytest.mark.gpu
-def test_precision16_through_synthesize_and_the_scheduler():
-    V.check_wrappers(DEV)
+def test_precision16_through_synthesize_and_the_scheduler(device):
+    V.check_vocoder_wrappers(device)
 
 
 # ---------------------------------------------------------------------------------------------------------------- CPU tier (simulator)
-def test_simulated_precision16_accuracy_v2_two_windows(yard):
-    """Test 1, v2 with one launch per ResBlock at B = 1, L = 50: the one-product kernels take windows of up to 512 rows at every channel
-    count (16 waves at C = 64), so the first stage's k = 11 block (halo 60) has TL = 392 output rows per window and 8 L = 400 positions
-    are the smallest length with two windows per utterance there."""
-    with use_sim():
-        V.check_accuracy(yard, "v2", "cpu", True, 1, 50)
+def test_simulated_precision16_accuracy_v2_two_windows(yard, device):
+    """v2 with one launch per ResBlock at B = 1, L = 50: the one-product kernels take windows of up to 512 rows at every channel count
+    (16 waves at C = 64), so the first stage's k = 11 block (halo 60) has TL = 392 output rows per window and 8 L = 400 positions are
+    the smallest length with two windows per utterance there."""
+    V.check_vocoder_accuracy(yard, R16, "v2", device, True, 1, 50)
 
 
-def test_simulated_precision16_accuracy_reduced_generator_conv_by_conv(yard):
-    """Test 1, the reduced generator of tests/test_vocoder_dispatch.py one launch per convolution, B = 2, L = 6."""
-    with use_sim():
-        V.check_accuracy(yard, "reduced1", "cpu", False, 2, 6)
+def test_simulated_precision16_accuracy_reduced_generator_conv_by_conv(yard, device):
+    """the reduced generator of tests/test_vocoder_dispatch.py one launch per convolution, B = 2, L = 6"""
+    V.check_vocoder_accuracy(yard, R16, "reduced1", device, False, 2, 6)
 
 
-def test_simulated_precision16_ragged_keeps_its_contract():
-    """Test 2 on the reduced generator, lengths [6, 2], both modes (the C call alone: the module's forward is in the accuracy tests)."""
-    with use_sim():
-        V.check_ragged_contract("reduced1", 2, 6, [6, 2], "cpu", module=False)
+def test_simulated_precision16_ragged_keeps_its_contract(device):
+    """the reduced generator, lengths [6, 2], both modes (the C call alone: the module's forward is in the accuracy tests)"""
+    V.check_ragged_contract(R16, "reduced1", 2, 6, [6, 2], device, module=False)
 
 
-def test_simulated_precision_0_and_32_are_the_existing_entry_points():
-    """Test 3 on a small generator (32 -> 16 / 8 channels; one launch per ResBlock), B = 2, L = 6, lengths [6, 2]: six calls compared
-    with each other."""
-    with use_sim():
-        V.check_default_untouched("small", 2, 6, [6, 2], "cpu")
+def test_simulated_precision_0_and_32_are_the_existing_entry_points(device):
+    """a small generator (32 -> 16 / 8 channels; one launch per ResBlock), B = 2, L = 6, lengths [6, 2]"""
+    V.check_default_untouched(R16, "small", 2, 6, [6, 2], device)
 
 
-def test_precision_refusals():
-    """Test 5: ValueError from Python; ESMI_ERR_ARG from the C call for precision 8 and for a PCM plane without lengths, nothing launched."""
-    with use_sim():
-        V.check_refusals("cpu")
+def test_precision_refusals(device):
+    """ValueError from Python; ESMI_ERR_ARG from the C call for precision 8 and for a PCM plane without lengths, nothing launched"""
+    V.check_vocoder_refusals(device)
 
 
 # (ResBlock type, fuse_resblocks, length-aware) -> the launch records of the reduced generator at precision 16, in order

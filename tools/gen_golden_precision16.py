@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Record the precision-16 outputs that tests/test_inference_bf16.py pins bit for bit (tests/golden/precision16_parent_bits.npz).
    python tools/gen_golden_precision16.py sim|gpu [out.npz]
-Run it on the commit whose bits are to be kept: `sim` runs tests/inference_bf16_checks.precision16_cases on that commit's wave-simulator
+Run it on the commit whose bits are to be kept: `sim` runs tests/precision_checks.precision16_cases on that commit's wave-simulator
 build, `gpu` on its libesmi.so (or the library ESMI_LIB names) on the device.  The tier's arrays are merged into the file, the other
-tier's are kept.  The cases use the precision-16 entry points only, so the module runs on a commit that has no bf16 inference."""
+tier's are kept."""
 import os
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,7 +12,7 @@ import numpy as np
 
 tier = sys.argv[1]
 out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "tests", "golden", "precision16_parent_bits.npz")
-from tests import inference_bf16_checks as V
+from tests import precision_checks as V
 if tier == "sim":
     from tests.simlib import use_sim
     with use_sim():
