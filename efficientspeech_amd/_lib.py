@@ -13,14 +13,36 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ESMI_LIB") or os.path.join(_HERE, "libesmi.so")   # ESMI_LIB: another build of the same ABI
+
+# ---- include/esmi.h's integer #defines, as far as Python needs them.  This is their ONE home on this side: every other module takes
+# them from here, and `MIRRORED` (below the last of them) is what tests/test_abi_exports.py compares with the header.
 MAX_DEPTH = 4
 MAX_DEC_LAYERS = 16
+HIFIGAN_MAX_UP, HIFIGAN_MAX_KERNELS, HIFIGAN_MAX_RBCONV = 8, 8, 96
+PRECISION_BF16 = 0xB16      # esmi_conv_desc.precision of the bf16-mixed training GEMMs, and the `precision` argument of the inference
+#                             entry points at bf16
+ESMI_OK, ERR_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_RANGE = 0, -1, -2, -3, -4
+# launch-plan bits: passed per call, the library keeps no state
+FUSE_MERGE_QKV, FUSE_ATTN_FFN, FUSE_VARIANCE, FUSE_SPLIT2, FUSE_BLOCK, FUSE_CHAIN16, FUSE_ALL = 1, 2, 4, 8, 16, 32, 63
+# the training step's buffers: the queue of deferred reductions, the loss kernel's scratch, the optimizer's two device blocks
+REDUCE_QUEUE_ITEMS = 48
+TRAIN_LOSS_SCRATCH_FLOATS = 1536
+TRAIN_ADAMW_HYPER_FLOATS, TRAIN_SCALER_FLOATS = 8, 8
+# ... and the slots of those two blocks (esmi_train_adamw_graph_f32's hyper_dev and scaler_state)
+HYPER_LR, HYPER_DECAY, HYPER_STEP_SIZE, HYPER_BC2_SQRT, HYPER_SKIP, HYPER_GRAD_SCALE = range(6)
+SCALER_SCALE, SCALER_GROWTH_FACTOR, SCALER_BACKOFF_FACTOR, SCALER_GROWTH_INTERVAL, SCALER_CLEAN_STEPS, SCALER_SKIPPED = range(6)
 
-ESMI_OK = 0
-_ERRS = {-1: "ESMI_ERR_ARG (null pointer / bad size / misaligned)",
-         -2: "ESMI_ERR_UNSUPPORTED (shape outside what the kernels are built for)",
-         -3: "ESMI_ERR_WORKSPACE (workspace too small)",
-         -4: "ESMI_ERR_RANGE (an activation left the binary16 range of the split contractions)"}
+_NAMES = ("MAX_DEPTH MAX_DEC_LAYERS HIFIGAN_MAX_UP HIFIGAN_MAX_KERNELS HIFIGAN_MAX_RBCONV PRECISION_BF16 ERR_ARG ERR_UNSUPPORTED "
+          "ERR_WORKSPACE ERR_RANGE FUSE_MERGE_QKV FUSE_ATTN_FFN FUSE_VARIANCE FUSE_SPLIT2 FUSE_BLOCK FUSE_CHAIN16 FUSE_ALL "
+          "REDUCE_QUEUE_ITEMS TRAIN_LOSS_SCRATCH_FLOATS TRAIN_ADAMW_HYPER_FLOATS TRAIN_SCALER_FLOATS HYPER_LR HYPER_DECAY HYPER_STEP_SIZE "
+          "HYPER_BC2_SQRT HYPER_SKIP HYPER_GRAD_SCALE SCALER_SCALE SCALER_GROWTH_FACTOR SCALER_BACKOFF_FACTOR SCALER_GROWTH_INTERVAL "
+          "SCALER_CLEAN_STEPS SCALER_SKIPPED")
+MIRRORED = {"ESMI_OK": ESMI_OK, **{"ESMI_" + n: globals()[n] for n in _NAMES.split()}}      # header name -> the value held here
+
+_ERRS = {ERR_ARG: "ESMI_ERR_ARG (null pointer / bad size / misaligned)",
+         ERR_UNSUPPORTED: "ESMI_ERR_UNSUPPORTED (shape outside what the kernels are built for)",
+         ERR_WORKSPACE: "ESMI_ERR_WORKSPACE (workspace too small)",
+         ERR_RANGE: "ESMI_ERR_RANGE (an activation left the binary16 range of the split contractions)"}
 
 fp = C.c_void_p  # device pointers travel as integers
 
@@ -63,9 +85,6 @@ class DecoderShape(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("d4", "dx2", "kernel", "n_blocks", "block_depth", "n_mel")]
 
 
-HIFIGAN_MAX_UP, HIFIGAN_MAX_KERNELS, HIFIGAN_MAX_RBCONV = 8, 8, 96
-
-
 class HifiGanWeights(C.Structure):
     _fields_ = [("pre_w", fp), ("pre_b", fp), ("up_w", fp * HIFIGAN_MAX_UP), ("up_b", fp * HIFIGAN_MAX_UP),
                 ("rb_w1", fp * HIFIGAN_MAX_RBCONV), ("rb_b1", fp * HIFIGAN_MAX_RBCONV), ("rb_w2", fp * HIFIGAN_MAX_RBCONV),
@@ -77,10 +96,6 @@ class HifiGanShape(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n_mel", "initial_channel", "n_up", "n_kernels", "resblock")] + \
                [("up_rates", C.c_int * HIFIGAN_MAX_UP), ("up_kernels", C.c_int * HIFIGAN_MAX_UP),
                 ("rb_kernels", C.c_int * HIFIGAN_MAX_KERNELS), ("rb_dilations", C.c_int * (HIFIGAN_MAX_KERNELS * 3))]
-
-
-PRECISION_BF16 = 0xB16      # ESMI_PRECISION_BF16 (include/esmi.h): esmi_conv_desc.precision of the bf16-mixed training GEMMs, and the
-#                             `precision` argument of the inference entry points at bf16
 
 
 def normalize_precision(precision, what="precision", numeric_strings=True):
@@ -115,7 +130,7 @@ class ReduceItem(C.Structure):
 
 class ReduceQueue(C.Structure):
     """esmi_reduce_queue (include/esmi.h): the queued second stages of a training step's chunked reductions."""
-    _fields_ = [("count", C.c_int32), ("items", ReduceItem * 48)]
+    _fields_ = [("count", C.c_int32), ("items", ReduceItem * REDUCE_QUEUE_ITEMS)]
 
 
 class TrainLossArgs(C.Structure):
@@ -146,10 +161,6 @@ class ForwardArgs(C.Structure):
                 ("duration_pred", fp), ("mel_len", fp), ("mel", fp), ("L_out", C.c_int), ("lmax_host", C.c_int), ("lmax_dev", fp),
                 ("pitch_pred", fp), ("energy_pred", fp), ("pitch_idx", fp), ("energy_idx", fp), ("dur", fp), ("cum", fp),
                 ("arena", fp), ("arena_bytes", C.c_size_t), ("range_flag", fp)]
-
-
-# launch-plan bits (include/esmi.h ESMI_FUSE_*): passed per call, the library keeps no state
-FUSE_MERGE_QKV, FUSE_ATTN_FFN, FUSE_VARIANCE, FUSE_SPLIT2, FUSE_BLOCK, FUSE_CHAIN16, FUSE_ALL = 1, 2, 4, 8, 16, 32, 63
 
 
 _tls = threading.local()
@@ -323,9 +334,9 @@ class Unsupported(RuntimeError):
 
 def _make_check(name):
     def check(rc, func, args):
-        if rc == -2:
+        if rc == ERR_UNSUPPORTED:
             raise Unsupported(f"{name}: shape not supported")
-        if rc == -4:
+        if rc == ERR_RANGE:
             raise ActivationRange(f"{name}: an activation is outside the binary16 range (|a| >= 65504) of the fp32-accurate split "
                                   "contractions; run this checkpoint on libesmi_fp32mfma.so (ESMI_LIB=...), which has no range limit")
         if rc != ESMI_OK:

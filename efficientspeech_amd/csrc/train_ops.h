@@ -1402,7 +1402,8 @@ static __global__ void train_adamw_kernel(float* __restrict__ p, const float* __
 
 // the same with the step count and the learning rate read from device memory, so that a captured hipGraph of the whole
 // training step replays correctly -- and so that `precision=16`'s dynamic loss scaling needs no host round trip:
-//   hyper  = {lr (caller), 1 - lr wd, lr / bc1, sqrt(bc2), skip flag, gradient scale}  (all but [0] written by train_bump_step_kernel)
+//   hyper  = {lr (caller), 1 - lr wd, lr / bc1, sqrt(bc2), skip flag, gradient scale}  (all but the first written by train_bump_step_kernel;
+//            the slots' names: ESMI_HYPER_* and ESMI_SCALER_* in include/esmi.h)
 //   scaler = NULL, or torch.amp.GradScaler's state {scale, growth_factor, backoff_factor, growth_interval, clean steps in a row,
 //            skipped steps}: an inf / nan in the (scaled) gradients -- `grad_absmax` holds max|g| with nan ordered as inf -- skips the
 //            update (the step counter does not advance), multiplies the scale by backoff_factor; growth_interval clean steps in a
@@ -1413,38 +1414,41 @@ static __global__ void train_bump_step_kernel(int* __restrict__ step, float* __r
     bool skip = false;
     float gscale = 1.0f;
     if (scaler) {
-        const float amax = grad_absmax[0], scale = scaler[0];
+        const float amax = grad_absmax[0], scale = scaler[ESMI_SCALER_SCALE];
         if (!(amax <= 3.4028234663852886e38f)) {       // inf or nan
             skip = true;
-            scaler[0] = scale * scaler[2];
-            scaler[4] = 0.0f;
-            scaler[5] += 1.0f;
+            scaler[ESMI_SCALER_SCALE] = scale * scaler[ESMI_SCALER_BACKOFF_FACTOR];
+            scaler[ESMI_SCALER_CLEAN_STEPS] = 0.0f;
+            scaler[ESMI_SCALER_SKIPPED] += 1.0f;
         } else {
             gscale = 1.0f / scale;
-            float good = scaler[4] + 1.0f;
-            if (good >= scaler[3]) { scaler[0] = scale * scaler[1]; good = 0.0f; }
-            scaler[4] = good;
+            float good = scaler[ESMI_SCALER_CLEAN_STEPS] + 1.0f;
+            if (good >= scaler[ESMI_SCALER_GROWTH_INTERVAL]) {
+                scaler[ESMI_SCALER_SCALE] = scale * scaler[ESMI_SCALER_GROWTH_FACTOR];
+                good = 0.0f;
+            }
+            scaler[ESMI_SCALER_CLEAN_STEPS] = good;
         }
     }
-    hyper[4] = skip ? 1.0f : 0.0f;
-    hyper[5] = gscale;
+    hyper[ESMI_HYPER_SKIP] = skip ? 1.0f : 0.0f;
+    hyper[ESMI_HYPER_GRAD_SCALE] = gscale;
     if (skip) return;
     const int t = step[0] + 1;
     step[0] = t;
-    const double lr = (double)hyper[0];
+    const double lr = (double)hyper[ESMI_HYPER_LR];
     const double bc1 = -expm1((double)t * log(beta1)), bc2 = -expm1((double)t * log(beta2));
-    hyper[1] = (float)(1.0 - lr * wd);
-    hyper[2] = (float)(lr / bc1);
-    hyper[3] = (float)sqrt(bc2);
+    hyper[ESMI_HYPER_DECAY] = (float)(1.0 - lr * wd);
+    hyper[ESMI_HYPER_STEP_SIZE] = (float)(lr / bc1);
+    hyper[ESMI_HYPER_BC2_SQRT] = (float)sqrt(bc2);
 }
 static __global__ void train_adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                        long n, AdamWScalars h, const float* __restrict__ hyper) {
     const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= n || hyper[4] != 0.0f) return;
-    h.decay = hyper[1];
-    h.step_size = hyper[2];
-    h.bc2_sqrt = hyper[3];
-    h.gscale = hyper[5];
+    if (q >= n || hyper[ESMI_HYPER_SKIP] != 0.0f) return;
+    h.decay = hyper[ESMI_HYPER_DECAY];
+    h.step_size = hyper[ESMI_HYPER_STEP_SIZE];
+    h.bc2_sqrt = hyper[ESMI_HYPER_BC2_SQRT];
+    h.gscale = hyper[ESMI_HYPER_GRAD_SCALE];
     adamw_update(p, g, m, v, q, h);
 }
 

@@ -251,6 +251,29 @@ class _PackedModule(nn.Module):
         return super()._apply(fn, *args, **kwargs)
 
 
+class PackedCopies:
+    """Every packed copy the inference path keeps under the module tree `net`: each module's `_PackCache` attributes, whatever
+    their names (the decoder has two), and the one-call forward's argument block.  `invalidate()` drops them all, so that the
+    next eval forward re-packs from the current parameters -- for a caller that writes the weights behind torch's version
+    counters, as the training step's optimizer kernel does."""
+
+    def __init__(self, net):
+        self.net, self._n = net, -1
+
+    def invalidate(self):
+        if self._n != sum(1 for _ in self.net.modules()):
+            # collected once (and again only if the module tree changed): the training step calls this every step, graph replays
+            # included, and walking every module's __dict__ was pure host time in a loop that is host-dispatch bound
+            mods = list(self.net.modules())
+            self._n = len(mods)
+            self._owners = [m for m in mods if hasattr(m, "_launch")]      # the one-call forward's argument block (lazily created)
+            self._caches = [v for m in mods for v in m.__dict__.values() if isinstance(v, _PackCache)]
+        for v in self._caches:
+            v.invalidate()
+        for m in self._owners:
+            m._fwd_ident = None
+
+
 def _pack_conv(lib, stream, w, transposed=False):
     """(Cout,Cin,k) [or ConvTranspose (Cin,Cout,k)] -> tap-major (k,Cout,Cin) on device."""
     w = _f32(w)

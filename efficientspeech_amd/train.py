@@ -425,7 +425,7 @@ class _Loss(torch.autograd.Function):
         T = pitch_pred.shape[1]
         out = _new((5,), mel_pred)
         grads = [torch.empty_like(t) for t in (mel_pred, pitch_pred, energy_pred, dur_pred)]
-        scratch = _new((1536,), mel_pred)          # ESMI_TRAIN_LOSS_SCRATCH_FLOATS; held until the call has been enqueued
+        scratch = _new((_lib.TRAIN_LOSS_SCRATCH_FLOATS,), mel_pred)      # held until the call has been enqueued
         seed = _STEP.loss_seed if _STEP is not None else None      # None: unknown here (scaled in backward); False: 1; else the device scalar
         a = _lib.TrainLossArgs(_ptr(mel_pred), _ptr(mel), _ptr(pitch_pred), _ptr(pitch), _ptr(energy_pred), _ptr(energy),
                                _ptr(dur_pred), _ptr(dur), _ptr(mel_mask), _ptr(ph_mask), B, T, L, nm, _ptr(out),
@@ -633,6 +633,113 @@ class FlatParams:
         self.grad.zero_()
 
 
+# torch.amp.GradScaler.state_dict()'s keys (Lightning stores it next to the optimizer) and the slots of the scaler block that hold them
+_SCALER_KEYS = (("scale", _lib.SCALER_SCALE), ("growth_factor", _lib.SCALER_GROWTH_FACTOR), ("backoff_factor", _lib.SCALER_BACKOFF_FACTOR),
+                ("growth_interval", _lib.SCALER_GROWTH_INTERVAL), ("_growth_tracker", _lib.SCALER_CLEAN_STEPS))
+
+
+class AdamWState:
+    """What AdamW and the loss scaler keep besides the moments (`FlatParams.m`, `.v`), and the optimizer launch that reads it.
+
+    Where the scalars live is decided here, once: `on_device` (graph replay, precision 16) keeps the step counter as one int32 and
+    the hyper block (`_lib.HYPER_*`: the caller's slot is the learning rate, the rest is the launch's own) in device memory, so that
+    the step never waits for the host; otherwise the counter is a Python int and the scalars travel as arguments.  Either way there
+    is ONE counter, and `t` reads and writes it: on the device a read is one device -> host copy and a write one `fill_`.
+
+    Precision 16 adds torch.amp.GradScaler on the device: the scaler block (`_lib.SCALER_*`) and the slot that max|g| is reduced
+    into.  Without them (`scaler is None`) the backward is seeded with the constant 1 and no step is skipped."""
+
+    def __init__(self, dev, precision=32, graph=False, lr=1e-3, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5,
+                 growth_interval=2000):
+        self.on_device = bool(graph) or precision == 16
+        self.scaler = self.absmax = self.hyper = None
+        self._count = 0                             # the step counter: this int, or (on_device) one int32 in device memory
+        if self.on_device:
+            self._count = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.hyper = torch.full((_lib.TRAIN_ADAMW_HYPER_FLOATS,), lr, dtype=torch.float32, device=dev)
+            self._lr = self.hyper[_lib.HYPER_LR:_lib.HYPER_LR + 1]
+        if precision == 16:
+            block = [0.0] * _lib.TRAIN_SCALER_FLOATS              # (clean steps in a row and skipped steps start at 0)
+            block[_lib.SCALER_SCALE], block[_lib.SCALER_GROWTH_FACTOR] = init_scale, growth_factor
+            block[_lib.SCALER_BACKOFF_FACTOR], block[_lib.SCALER_GROWTH_INTERVAL] = backoff_factor, growth_interval
+            self.scaler = torch.tensor(block, dtype=torch.float32, device=dev)
+            self.absmax = torch.zeros(1, dtype=torch.float32, device=dev)
+        # what the backward is seeded with (GradScaler.scale(loss).backward()): the device-side scale, else the constant one
+        self.loss_seed = (torch.ones(1, dtype=torch.float32, device=dev) if self.scaler is None
+                          else self.scaler[_lib.SCALER_SCALE:_lib.SCALER_SCALE + 1])
+
+    @property
+    def t(self):
+        return int(self._count.item()) if self.on_device else self._count
+
+    @t.setter
+    def t(self, v):
+        if self.on_device:
+            self._count.fill_(int(v))
+        else:
+            self._count = int(v)
+
+    # read-outs of the scaler block (each is one small device -> host copy; the step itself never reads them)
+    @property
+    def scale(self):
+        return 1.0 if self.scaler is None else float(self.scaler[_lib.SCALER_SCALE].item())
+
+    @property
+    def skipped(self):
+        return 0 if self.scaler is None else int(self.scaler[_lib.SCALER_SKIPPED].item())
+
+    def _need_scaler(self, what):
+        if self.scaler is None:
+            raise AttributeError(f"no {what}: this step has no loss scaler (only precision 16 has one)")
+        return self.scaler
+
+    @property
+    def growth_interval(self):
+        return int(self._need_scaler("growth_interval")[_lib.SCALER_GROWTH_INTERVAL].item())
+
+    @growth_interval.setter
+    def growth_interval(self, n):
+        self._need_scaler("growth_interval")[_lib.SCALER_GROWTH_INTERVAL] = float(n)
+
+    def scaler_state_dict(self):
+        """torch.amp.GradScaler.state_dict() of the scaler block; None without one."""
+        if self.scaler is None:
+            return None
+        block = self.scaler.cpu().tolist()
+        sd = {key: block[slot] for key, slot in _SCALER_KEYS}
+        sd.update(growth_interval=int(sd["growth_interval"]), _growth_tracker=int(sd["_growth_tracker"]))
+        return sd
+
+    def load_scaler_state_dict(self, sd):
+        """... and back; without a scaler block a checkpoint's entry is ignored."""
+        if self.scaler is not None and sd is not None:
+            for key, slot in _SCALER_KEYS:
+                self.scaler[slot] = float(sd[key])
+
+    def set_lr(self, lr):
+        """This step's learning rate, for the launch that reads it from device memory (outside a captured graph: before the replay)."""
+        if self.on_device:
+            self._lr.fill_(lr)
+
+    def launch(self, flat, lr, betas, eps, weight_decay):
+        """One AdamW update of `flat` by its (already exchanged) gradients."""
+        f = flat
+        lib, st = _rt(f.data)
+        if self.scaler is not None:
+            # GradScaler.step + .update on the device: max|g| of the (still scaled) gradients -- absmax's integer max orders inf and
+            # nan above every finite magnitude -- decides inside the optimizer launch whether the update runs (on g / scale) or is
+            # skipped with the scale backed off; nothing is read back.
+            lib.esmi_absmax_f32(_ptr(f.grad), f.grad.numel(), _ptr(self.absmax), st)
+        if self.on_device:                          # (the launch counts: a skipped step does not advance the counter)
+            absmax, scaler = (None, None) if self.scaler is None else (_ptr(self.absmax), _ptr(self.scaler))
+            lib.esmi_train_adamw_graph_f32(_ptr(f.data), _ptr(f.grad), _ptr(f.m), _ptr(f.v), f.data.numel(), _ptr(self.hyper),
+                                           betas[0], betas[1], eps, weight_decay, _ptr(self._count), absmax, scaler, st)
+        else:
+            self._count += 1
+            lib.esmi_train_adamw_f32(_ptr(f.data), _ptr(f.grad), _ptr(f.m), _ptr(f.v), f.data.numel(), lr, betas[0], betas[1], eps,
+                                     weight_decay, self._count, 1.0, st)
+
+
 class TrainStep:
     """One optimizer step of the reference's training loop (model.py:212-226 + :279-283) on one GPU of a data-parallel job.
 
@@ -650,7 +757,7 @@ class TrainStep:
         self.net, self.flat = net, FlatParams(net)
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         self.group, self.world = group, world_size
-        self._t = 0
+        self.epoch = 0                              # what `state_dict()` records; `fit` and `load_state_dict` set it
         # precision 16 = what Lightning's `precision=16` does around the reference's step (train.py:66-70): autocast-class GEMMs
         # (binary16 operands, fp32 accumulate, fp32 master weights) + torch.amp.GradScaler's dynamic loss scaling: the backward
         # is seeded with `scale`, a step whose gradients hold inf / nan is skipped and halves the scale, `growth_interval` clean
@@ -660,46 +767,17 @@ class TrainStep:
         precision = normalize_precision(precision)
         self.precision = precision
         self.graph = bool(graph)
-        dev = self.flat.data.device
-        if precision == 16:
-            # the scaler's state and the optimizer's step count live in device memory: the step never waits for the host.
-            # {scale, growth_factor, backoff_factor, growth_interval, clean steps in a row, skipped steps, -, -}
-            self._scaler = torch.tensor([init_scale, growth_factor, backoff_factor, growth_interval, 0, 0, 0, 0], dtype=torch.float32, device=dev)
-            self._absmax = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._opt = AdamWState(self.flat.data.device, precision, self.graph, lr, init_scale, growth_factor, backoff_factor, growth_interval)
         self._graphs = {}
-        self._one = torch.ones(1, dtype=torch.float32, device=dev)
         self._build_pack_list()
-        self._on_device = self.graph or precision == 16     # the optimizer reads step count and learning rate from device memory
-        if self._on_device:
-            self._step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-            self._lr_dev = torch.full((8,), lr, dtype=torch.float32, device=dev)   # ESMI_TRAIN_ADAMW_HYPER_FLOATS: [0] = lr
+        self._packed = networks.PackedCopies(net)   # what the inference path keeps of the weights this step's optimizer overwrites
 
-    # precision 16: read-outs of the device-side state (each is one small device -> host copy; the step itself never reads them)
-    @property
-    def scale(self):
-        return float(self._scaler[0].item()) if self.precision == 16 else 1.0
-
-    @property
-    def skipped(self):
-        return int(self._scaler[5].item()) if self.precision == 16 else 0
-
-    @property
-    def growth_interval(self):
-        return int(self._scaler[3].item())
-
-    @growth_interval.setter
-    def growth_interval(self, n):
-        self._scaler[3] = float(n)
-
-    @property
-    def t(self):
-        return int(self._step_dev.item()) if self.precision == 16 else self._t
-
-    @t.setter
-    def t(self, v):
-        self._t = int(v)
-        if self.precision == 16 and hasattr(self, "_step_dev"):
-            self._step_dev.fill_(int(v))
+    # the optimizer's step count and the loss scaler's read-outs: `AdamWState`'s (under graph replay and at precision 16 each read is
+    # one small device -> host copy; the step itself never reads them)
+    t = property(lambda self: self._opt.t, lambda self, v: setattr(self._opt, "t", v))
+    scale = property(lambda self: self._opt.scale)
+    skipped = property(lambda self: self._opt.skipped)
+    growth_interval = property(lambda self: self._opt.growth_interval, lambda self, n: setattr(self._opt, "growth_interval", n))
 
     # ---- checkpoint / resume (what Lightning's ModelCheckpoint keeps: weights, hyper-parameters, the optimizer's state_dict)
     def hyper_parameters(self):
@@ -719,7 +797,7 @@ class TrainStep:
         f = self.flat
         index = {id(p): j for j, p in enumerate(self.net.parameters())}
         state = {}
-        t_now = self.t                          # (precision 16: a device read -- once, not per parameter)
+        t_now = self.t                          # (possibly a device read -- once, not per parameter)
         for p, sl in zip(f.params, f.slices):
             if t_now > 0:
                 state[index[id(p)]] = {"step": torch.tensor(float(t_now)), "exp_avg": f.m[sl].view(p.shape).clone(),
@@ -738,11 +816,10 @@ class TrainStep:
         `hifigan.` before saving."""
         ck = {"state_dict": {"phoneme2mel." + k: v.detach().clone() for k, v in self.net.state_dict().items()},
               "hyper_parameters": self.hyper_parameters(), "optimizer_states": [self.optimizer_state_dict()],
-              "global_step": self.t, "epoch": int(getattr(self, "epoch", 0))}
-        if self.precision == 16:                   # torch.amp.GradScaler.state_dict()'s keys (Lightning stores it next to the optimizer)
-            sc = self._scaler.cpu().tolist()
-            ck["scaler"] = {"scale": sc[0], "growth_factor": sc[1], "backoff_factor": sc[2], "growth_interval": int(sc[3]),
-                            "_growth_tracker": int(sc[4])}
+              "global_step": self.t, "epoch": int(self.epoch)}
+        scaler = self._opt.scaler_state_dict()
+        if scaler is not None:
+            ck["scaler"] = scaler
         return ck
 
     def load_state_dict(self, ckpt):
@@ -780,32 +857,10 @@ class TrainStep:
         # the BASE learning rate: under a scheduler torch stores it as `initial_lr` and keeps the scheduled value in `lr` (0 at the
         # first step of the reference's LambdaLR warm-up) -- `fit` derives every step's rate from the base one
         self.lr, self.wd, self.betas, self.eps = g.get("initial_lr", g["lr"]), g["weight_decay"], tuple(g["betas"]), g["eps"]
-        if self.graph and self.precision != 16:
-            self._step_dev.fill_(self.t)
-        if self.precision == 16 and "scaler" in ckpt:
-            sc = ckpt["scaler"]
-            self._scaler[:5] = torch.tensor([sc["scale"], sc["growth_factor"], sc["backoff_factor"], sc["growth_interval"],
-                                             sc["_growth_tracker"]], dtype=torch.float32)
-        self._invalidate_packed()
+        self._opt.load_scaler_state_dict(ckpt.get("scaler"))
+        self._packed.invalidate()
         self.epoch = int(ckpt.get("epoch", 0))
         return self.epoch
-
-    def _invalidate_packed(self):
-        """The optimizer kernel wrote the weights behind torch's version counters: drop EVERY packed copy the inference path
-        keeps (each module's `_PackCache` attributes, whatever their names -- the decoder has two -- and the one-call
-        forward's argument block) so that the next eval forward re-packs from the updated parameters."""
-        caches = getattr(self, "_pack_caches", None)
-        if caches is None or self._pack_caches_n != sum(1 for _ in self.net.modules()):
-            # collected once (and again only if the module tree changed): this runs every step, graph replays included, and walking
-            # every module's __dict__ was pure host time in a loop that is host-dispatch bound
-            mods = list(self.net.modules())
-            self._pack_caches_n = len(mods)
-            self._pack_owners = [m for m in mods if hasattr(m, "_launch")]      # the one-call forward keeps an argument block (lazily created)
-            caches = self._pack_caches = [v for m in mods for v in m.__dict__.values() if isinstance(v, networks._PackCache)]
-        for v in caches:
-            v.invalidate()
-        for m in self._pack_owners:
-            m._fwd_ident = None
 
     def _build_pack_list(self):
         """Persistent GEMM copies (forward layout, data-gradient layout) of every dense convolution / Linear weight, re-made by ONE
@@ -835,16 +890,15 @@ class TrainStep:
         f = self.flat
         f.zero_grad()
         rq = (_lib.ReduceQueue(), [])
-        amp = self.precision == 16
         lib0, st0 = _rt(f.data)
-        with _step_context(self.precision, self._scaler[:1] if amp else False) as now:
+        seed = self._opt.loss_seed                 # one device float: the loss scale, or the constant 1 where there is no scaler
+        with _step_context(self.precision, seed if self._opt.scaler is not None else False) as now:
             if USE_MATRIX_PIPE and self._pack_n:   # every operator of this step reads these copies of the current weights
                 lib0.esmi_train_pack_weights_f32(self._pack_descs, self._pack_w, self._pack_n, st0)
                 now.packed_valid = True
             parts, total = training_loss(self.net, x, y)
             # one backward on a zeroed buffer: operators write parameter gradients in place and queue their reductions' second stages
             now.direct_grads, now.reduce_queue = True, rq
-            seed = self._scaler[0] if amp else self._one     # GradScaler.scale(loss).backward(): the seed is the device-side scale
             total.backward(gradient=seed.reshape(total.shape))
         lib0.esmi_train_reduce_flush_f32(C.byref(rq[0]), st0)      # every queued parameter-gradient reduction in one launch
         rq[1].clear()
@@ -858,20 +912,7 @@ class TrainStep:
             import torch.distributed as dist
             dist.all_reduce(f.grad, op=dist.ReduceOp.SUM, group=self.group)
             f.grad.div_(self.world)                # DDP averages (train.py:66-70 runs Lightning's default DDP strategy)
-        lib, st = _rt(f.data)
-        amp = self.precision == 16
-        if amp:
-            # GradScaler.step + .update on the device: max|g| of the (still scaled) gradients -- absmax's integer max orders inf and
-            # nan above every finite magnitude -- decides inside the optimizer launch whether the update runs (on g / scale) or is
-            # skipped with the scale backed off; nothing is read back.
-            lib.esmi_absmax_f32(_ptr(f.grad), f.grad.numel(), _ptr(self._absmax), st)
-        if self._on_device:
-            absmax, scaler = (_ptr(self._absmax), _ptr(self._scaler)) if amp else (None, None)
-            lib.esmi_train_adamw_graph_f32(_ptr(f.data), _ptr(f.grad), _ptr(f.m), _ptr(f.v), f.data.numel(), _ptr(self._lr_dev),
-                                           self.betas[0], self.betas[1], self.eps, self.wd, _ptr(self._step_dev), absmax, scaler, st)
-        else:
-            lib.esmi_train_adamw_f32(_ptr(f.data), _ptr(f.grad), _ptr(f.m), _ptr(f.v), f.data.numel(), lr, self.betas[0],
-                                     self.betas[1], self.eps, self.wd, self.t, 1.0, st)
+        self._opt.launch(f, lr, self.betas, self.eps, self.wd)
 
     def _body(self, x, y, lr):
         losses = self._fwd_bwd(x, y)
@@ -882,14 +923,11 @@ class TrainStep:
         """One training step.  graph=True: a hipGraph per batch SHAPE replays the step (inputs are copied into its static buffers) --
         the whole step on one GPU; data-parallel, everything up to the gradient all-reduce (the collective and the optimizer launch
         follow eagerly)."""
-        if self.precision != 16:
-            self._t += 1                           # (precision 16 counts on the device: a skipped step does not advance it)
         lr = self.lr if lr is None else lr
-        if self._on_device:
-            self._lr_dev[:1].fill_(lr)
+        self._opt.set_lr(lr)
         if not self.graph:
             out = self._body(x, y, lr)
-            self._invalidate_packed()
+            self._packed.invalidate()
             return out
         whole = self.world == 1                    # the collective stays outside a graph
         key = tuple((k, tuple(v.shape)) for k, v in sorted({**x, **{"y." + k: v for k, v in y.items()}}.items()) if torch.is_tensor(v))
@@ -906,7 +944,7 @@ class TrainStep:
             with torch.cuda.graph(g):
                 static_out = self._body(sx, sy, lr) if whole else self._fwd_bwd(sx, sy)
             self._graphs[key] = (g, sx, sy, static_out)
-            self._invalidate_packed()
+            self._packed.invalidate()
             return out.clone()                     # (the capture itself does not execute: this batch's step ran eagerly above)
         g, sx, sy, static_out = ent
         for k, v in x.items():
@@ -917,7 +955,7 @@ class TrainStep:
         g.replay()
         if not whole:
             self._optimize(lr)
-        self._invalidate_packed()
+        self._packed.invalidate()
         return static_out.clone()
 
 

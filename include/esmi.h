@@ -822,7 +822,7 @@ int esmi_train_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n
                          double weight_decay, int step, double grad_scale /* gradients are g * grad_scale: 1 / loss scale under
                          precision 16 (torch.amp.GradScaler's unscale_), else 1 */, esmi_stream_t stream);
 /* the same update with its bookkeeping in device memory -- for a captured hipGraph of the whole step, and for `precision=16` without a
- * host round trip: hyper_dev = ESMI_TRAIN_ADAMW_HYPER_FLOATS floats ([0] = learning rate, written by the caller before a replay;
+ * host round trip: hyper_dev = ESMI_TRAIN_ADAMW_HYPER_FLOATS floats ([ESMI_HYPER_LR] = learning rate, written by the caller before a replay;
  * the rest is scratch of this call: the bias corrections of the current step, evaluated in double precision by one device thread,
  * the skip flag and the gradient scale), step_dev = the step counter (1 int32, advanced by this call before the update).
  * grad_absmax + scaler_state (both NULL, or both given): torch.amp.GradScaler on the device -- grad_absmax = max|g| of the (scaled)
@@ -831,6 +831,20 @@ int esmi_train_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n
  * the scale off; otherwise the update runs on g / scale and the growth counter advances */
 #define ESMI_TRAIN_ADAMW_HYPER_FLOATS 8
 #define ESMI_TRAIN_SCALER_FLOATS 8
+/* the slots of hyper_dev ... */
+#define ESMI_HYPER_LR 0         /* learning rate: the caller's, read by this call */
+#define ESMI_HYPER_DECAY 1      /* 1 - lr * weight_decay */
+#define ESMI_HYPER_STEP_SIZE 2  /* lr / (1 - beta1^step) */
+#define ESMI_HYPER_BC2_SQRT 3   /* sqrt(1 - beta2^step) */
+#define ESMI_HYPER_SKIP 4       /* != 0: the gradients overflowed, this update does not run */
+#define ESMI_HYPER_GRAD_SCALE 5 /* 1 / loss scale (1 without a scaler) */
+/* ... and of scaler_state */
+#define ESMI_SCALER_SCALE 0
+#define ESMI_SCALER_GROWTH_FACTOR 1
+#define ESMI_SCALER_BACKOFF_FACTOR 2
+#define ESMI_SCALER_GROWTH_INTERVAL 3
+#define ESMI_SCALER_CLEAN_STEPS 4 /* clean steps in a row since the scale last changed */
+#define ESMI_SCALER_SKIPPED 5     /* skipped steps, ever */
 int esmi_train_adamw_graph_f32(float* p, const float* g, float* m, float* v, int64_t n, float* hyper_dev, double beta1, double beta2,
                                double eps, double weight_decay, int32_t* step_dev, const float* grad_absmax /* or NULL */,
                                float* scaler_state /* or NULL */, esmi_stream_t stream);

@@ -27,6 +27,32 @@ def test_header_lists_expected_entry_points():
     assert sorted(_lib.EXPORTS) == header_functions()
 
 
+def header_constants():
+    """Every `#define ESMI_<NAME> <integer>` of the header: decimal, hex, or a parenthesised negative."""
+    src = open(os.path.join(ROOT, "include", "esmi.h")).read()
+    found = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(ESMI_[A-Z0-9_]+)[ \t]+(\(-\d+\)|0[xX][0-9a-fA-F]+|\d+)[ \t]*(?:/\*.*|//.*)?$", src, flags=re.M)
+    assert len({n for n, _ in found}) == len(found)          # (defined once each)
+    return {n: int(v.strip("()"), 0) for n, v in found}
+
+
+def test_python_mirrors_the_headers_constants():
+    """`_lib.MIRRORED` is the one place where Python repeats include/esmi.h's integer constants (limits, error codes, plan bits, the
+    training step's buffer sizes, the slots of the optimizer's two device blocks): each has the header's value."""
+    from efficientspeech_amd import _lib
+    header = header_constants()
+    assert header["ESMI_VERSION"] == 501 and header["ESMI_ERR_RANGE"] == -4 and header["ESMI_PRECISION_BF16"] == 0xB16   # all three spellings parse
+    assert _lib.MIRRORED
+    for name in ("ESMI_TRAIN_LOSS_SCRATCH_FLOATS", "ESMI_TRAIN_ADAMW_HYPER_FLOATS", "ESMI_TRAIN_SCALER_FLOATS", "ESMI_REDUCE_QUEUE_ITEMS"):
+        assert name in _lib.MIRRORED, name
+    for name, value in _lib.MIRRORED.items():
+        assert name in header, f"{name} is not an integer #define of include/esmi.h"
+        assert value == header[name], (name, value, header[name])
+    for name in header:                                      # ... and the header adds no slot or error code that Python does not know
+        if name.startswith(("ESMI_HYPER_", "ESMI_SCALER_", "ESMI_ERR_")):
+            assert name in _lib.MIRRORED, name
+    assert len(_lib.ReduceQueue().items) == header["ESMI_REDUCE_QUEUE_ITEMS"]      # (the struct takes its length from the mirror)
+
+
 def exported_esmi_symbols(path):
     """Dynamic symbols of the shared library that start with esmi_ (nm -D --defined-only)."""
     import subprocess

@@ -268,6 +268,79 @@ def test_gpu_captured_step_equals_eager_step():
     assert torch.allclose(eager.flat.data, cap.flat.data, rtol=1e-4, atol=1e-6)
 
 
+@pytest.mark.gpu
+def test_gpu_step_count_set_on_a_captured_step_reaches_the_optimizer():
+    """`step.t = k` sets the ONE counter the optimizer reads, captured or not: from t = 7 a captured step gives the eager step's
+    parameters (with zero moments the bias corrections of step 1 and step 8 differ by about half a learning rate per element)."""
+    train, g, net, x, y = _setup("cuda")
+    a = train.TrainStep(net, lr=1e-3)
+    a.t = 7
+    a.step(x, y)
+    t2, g2, net2, x2, y2 = _setup("cuda")
+    b = t2.TrainStep(net2, lr=1e-3, graph=True)
+    b.t = 7
+    b.step(x2, y2)
+    assert a.t == b.t == 8
+    assert torch.allclose(a.flat.data, b.flat.data, rtol=1e-4, atol=1e-6)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("precision", [32, 16])
+def test_gpu_checkpoint_resumes_into_a_captured_step(precision):
+    """check_checkpoint_resume's first paragraph with graph=True on both sides: 2 steps, save, a 3rd; a fresh captured step resumed
+    from the checkpoint takes one step to the same losses and parameters, and counts 3.  Precision 16 starts at a scale the fixture
+    batch does not overflow at (check_precision16_step's) and grows it after 3 clean steps, so that the 3rd step's growth happens in
+    the resumed step only if the scaler's interval and its count of clean steps came back with the checkpoint."""
+    kw = dict(lr=1e-3, graph=True, precision=precision)
+    train, g, net, x, y = _setup("cuda")
+    a = train.TrainStep(net, init_scale=2048.0, growth_interval=3, **kw)
+    for _ in range(2):
+        a.step(x, y)
+    ckpt = a.state_dict()
+    assert ckpt["global_step"] == 2
+    last_a = a.step(x, y)
+    t2, g2, net2, x2, y2 = _setup("cuda")
+    b = t2.TrainStep(net2, **kw)
+    b.load_state_dict(ckpt)
+    last_b = b.step(x2, y2)
+    assert a.t == 3 and b.t == 3
+    assert torch.allclose(last_a, last_b, rtol=1e-4, atol=1e-6), (last_a, last_b)
+    assert torch.allclose(a.flat.data, b.flat.data, rtol=1e-4, atol=1e-6)
+    assert a.skipped == b.skipped == 0 and a.scale == b.scale == (4096.0 if precision == 16 else 1.0)
+
+
+def test_simulated_optimizer_state_counts_once_on_the_device_and_on_the_host():
+    """The CPU twin of the two tests above (capture itself cannot run on the simulator): `AdamWState` with its scalars in device
+    memory, as a captured precision-32 step has them, and with them on the host takes the same AdamW step from t = 7 to t = 8."""
+    import types
+    from efficientspeech_amd import train
+    from tests.simlib import launched_kernels
+    n, lr = 1003, 1e-3                                       # four blocks of 256, the last one partial
+    gen = torch.Generator().manual_seed(7)
+    p0, g0 = torch.randn(n, generator=gen), 1e-2 * torch.randn(n, generator=gen)
+    got = {}
+    with use_sim():
+        for graph in (True, False):
+            flat = types.SimpleNamespace(data=p0.clone(), grad=g0.clone(), m=torch.zeros(n), v=torch.zeros(n))
+            opt = train.AdamWState("cpu", precision=32, graph=graph, lr=lr)
+            assert opt.on_device == graph and (opt.hyper is not None) == graph and opt.scaler is None and opt.absmax is None
+            opt.t = 7
+            opt.set_lr(lr)
+            with launched_kernels() as names:
+                opt.launch(flat, lr, (0.9, 0.999), 1e-8, 1e-6)
+            assert names == (["train_bump_step_kernel", "train_adamw_dev_kernel"] if graph else ["train_adamw_kernel"])
+            assert opt.t == 8
+            got[graph] = flat
+    for k in ("data", "m", "v"):
+        assert torch.allclose(getattr(got[True], k), getattr(got[False], k), rtol=1e-4, atol=1e-6), k
+    # ... and it is step 8's update: from zero moments m = 0.1 g and v = 0.001 g^2, so every element moves by
+    # lr (0.1 / bc1) sqrt(bc2 / 0.001) = 0.4958 lr with bc1 = 1 - 0.9^8, bc2 = 1 - 0.999^8 (step 1 would move it by lr); eps = 1e-8
+    # against |g| ~ 1e-2 and the decay lr wd |p| ~ 1e-9 are below the 1 % allowed here
+    for flat in got.values():
+        moved = (flat.data - p0).abs()
+        assert 0.99 * 0.4958 * lr < float(moved.median()) < 1.01 * 0.4958 * lr, float(moved.median())
+
+
 def test_lr_schedule_matches_reference_lambda():
     """model.py:77-101: linear warm-up (50 epochs) then cosine decay, evaluated per epoch."""
     import math

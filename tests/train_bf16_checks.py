@@ -12,6 +12,7 @@ import ctypes as C
 import os
 
 import numpy as np
+import pytest
 import torch
 import torch.nn.functional as F
 
@@ -302,7 +303,11 @@ def check_mechanics(dev):
     from tests.test_train_step import _setup
     tr, g, net, x, y = _setup(dev, GOLD_BF16)
     step = tr.TrainStep(net, lr=1e-3, weight_decay=1e-6, precision="bf16-mixed")
-    assert step.precision == "bf16" and not hasattr(step, "_scaler")
+    assert step.precision == "bf16"
+    opt = step._opt                                   # no scaler block, no absmax slot, and (eager) nothing else in device memory either
+    assert isinstance(opt, tr.AdamWState) and opt.scaler is None and opt.absmax is None and not opt.on_device and opt.hyper is None
+    with pytest.raises(AttributeError, match="no loss scaler"):
+        step.growth_interval
     before = {k: p.detach().clone() for k, p in net.named_parameters()}
     first = step.step(x, y).clone()
     assert step.scale == 1.0 and step.skipped == 0 and step.t == 1 and "scaler" not in step.state_dict()
