@@ -28,14 +28,15 @@ FUSE_MERGE_QKV, FUSE_ATTN_FFN, FUSE_VARIANCE, FUSE_SPLIT2, FUSE_BLOCK, FUSE_CHAI
 REDUCE_QUEUE_ITEMS = 48
 TRAIN_LOSS_SCRATCH_FLOATS = 1536
 TRAIN_ADAMW_HYPER_FLOATS, TRAIN_SCALER_FLOATS = 8, 8
+TRAIN_GRAD_NORM_PARTIALS = 1024     # doubles that esmi_train_grad_sumsq_f32 writes and esmi_train_adamw_clip_f32 adds up
 # ... and the slots of those two blocks (esmi_train_adamw_graph_f32's hyper_dev and scaler_state)
-HYPER_LR, HYPER_DECAY, HYPER_STEP_SIZE, HYPER_BC2_SQRT, HYPER_SKIP, HYPER_GRAD_SCALE = range(6)
+HYPER_LR, HYPER_DECAY, HYPER_STEP_SIZE, HYPER_BC2_SQRT, HYPER_SKIP, HYPER_GRAD_SCALE, HYPER_GRAD_NORM, HYPER_CLIP_COEF = range(8)
 SCALER_SCALE, SCALER_GROWTH_FACTOR, SCALER_BACKOFF_FACTOR, SCALER_GROWTH_INTERVAL, SCALER_CLEAN_STEPS, SCALER_SKIPPED = range(6)
 
 _NAMES = ("MAX_DEPTH MAX_DEC_LAYERS HIFIGAN_MAX_UP HIFIGAN_MAX_KERNELS HIFIGAN_MAX_RBCONV PRECISION_BF16 ERR_ARG ERR_UNSUPPORTED "
           "ERR_WORKSPACE ERR_RANGE FUSE_MERGE_QKV FUSE_ATTN_FFN FUSE_VARIANCE FUSE_SPLIT2 FUSE_BLOCK FUSE_CHAIN16 FUSE_ALL "
-          "REDUCE_QUEUE_ITEMS TRAIN_LOSS_SCRATCH_FLOATS TRAIN_ADAMW_HYPER_FLOATS TRAIN_SCALER_FLOATS HYPER_LR HYPER_DECAY HYPER_STEP_SIZE "
-          "HYPER_BC2_SQRT HYPER_SKIP HYPER_GRAD_SCALE SCALER_SCALE SCALER_GROWTH_FACTOR SCALER_BACKOFF_FACTOR SCALER_GROWTH_INTERVAL "
+          "REDUCE_QUEUE_ITEMS TRAIN_LOSS_SCRATCH_FLOATS TRAIN_ADAMW_HYPER_FLOATS TRAIN_SCALER_FLOATS TRAIN_GRAD_NORM_PARTIALS HYPER_LR HYPER_DECAY "
+          "HYPER_STEP_SIZE HYPER_BC2_SQRT HYPER_SKIP HYPER_GRAD_SCALE HYPER_GRAD_NORM HYPER_CLIP_COEF SCALER_SCALE SCALER_GROWTH_FACTOR SCALER_BACKOFF_FACTOR SCALER_GROWTH_INTERVAL "
           "SCALER_CLEAN_STEPS SCALER_SKIPPED")
 MIRRORED = {"ESMI_OK": ESMI_OK, **{"ESMI_" + n: globals()[n] for n in _NAMES.split()}}      # header name -> the value held here
 
@@ -206,6 +207,7 @@ EXPORTS = (
     "esmi_train_add_f32", "esmi_train_copy_cols_f32", "esmi_train_repeat_fwd_f32", "esmi_train_repeat_bwd_f32",
     "esmi_train_loss_f32", "esmi_train_adamw_f32", "esmi_train_adamw_graph_f32", "esmi_train_conv_bwd_workspace_bytes",
     "esmi_train_conv_bwd_f32", "esmi_train_reduce_flush_f32", "esmi_train_pack_weights_f32", "esmi_train_cat_f32",
+    "esmi_train_grad_sumsq_f32", "esmi_train_adamw_clip_f32",
 )
 
 
@@ -309,6 +311,8 @@ def bind(lib):
     lib.esmi_train_loss_f32.argtypes = [P(TrainLossArgs), fp]
     lib.esmi_train_adamw_f32.argtypes = [fp, fp, fp, fp, i64, dbl, dbl, dbl, dbl, dbl, i, dbl, fp]
     lib.esmi_train_adamw_graph_f32.argtypes = [fp, fp, fp, fp, i64, fp, dbl, dbl, dbl, dbl, fp, fp, fp, fp]
+    lib.esmi_train_grad_sumsq_f32.argtypes = [fp, i64, fp, fp]
+    lib.esmi_train_adamw_clip_f32.argtypes = [fp, fp, fp, fp, i64, fp, dbl, dbl, dbl, dbl, fp, fp, fp, fp, dbl, fp]
     lib.esmi_pack_resblock_bytes.argtypes = [i, i]
     lib.esmi_pack_resblock_bytes.restype = sz
     lib.esmi_pack_resblock_f16.argtypes = [fp, fp, i, i, fp]

@@ -553,4 +553,27 @@ int esmi_train_adamw_graph_f32(float* p, const float* g, float* m, float* v, int
     return launch_status();
 }
 
+int esmi_train_grad_sumsq_f32(const float* g, int64_t n, double* partials, esmi_stream_t stream) {
+    if (!g || !partials || n <= 0 || (reinterpret_cast<uintptr_t>(partials) & 7) != 0) return ESMI_ERR_ARG;
+    const long n4 = (reinterpret_cast<uintptr_t>(g) & 15) == 0 ? (long)(n >> 2) : 0;   // whole 16-byte loads; the rest is the scalar tail
+    const long work = n4 > 0 ? n4 : (long)n, blocks = (work + 255) / 256;
+    ESMI_LAUNCH(train_grad_sumsq_kernel, dim3((unsigned)(blocks > ESMI_TRAIN_GRAD_NORM_PARTIALS ? ESMI_TRAIN_GRAD_NORM_PARTIALS : blocks)),
+                dim3(256), 256 * sizeof(double), S(stream), g, n4, (long)n, partials);
+    return launch_status();
+}
+
+int esmi_train_adamw_clip_f32(float* p, const float* g, float* m, float* v, int64_t n, float* hyper_dev, double beta1, double beta2,
+                              double eps, double weight_decay, int32_t* step_dev, const float* grad_absmax, float* scaler_state,
+                              const double* sumsq_partials, double max_norm, esmi_stream_t stream) {
+    if (!p || !g || !m || !v || !hyper_dev || !step_dev || n <= 0 || ((scaler_state != nullptr) != (grad_absmax != nullptr)) ||
+        !sumsq_partials || (reinterpret_cast<uintptr_t>(sumsq_partials) & 7) != 0 || !(max_norm > 0.0))
+        return ESMI_ERR_ARG;
+    ESMI_LAUNCH(train_bump_clip_kernel, dim3(1), dim3(256), 256 * sizeof(double), S(stream), step_dev, hyper_dev, beta1, beta2, weight_decay,
+                grad_absmax, scaler_state, sumsq_partials, max_norm);
+    if (int rc = launch_status()) return rc;
+    AdamWScalars h = {(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, 0.0f, 0.0f, 0.0f, 1.0f};
+    ESMI_LAUNCH(train_adamw_dev_kernel, grid1d(n), dim3(256), 0, S(stream), p, g, m, v, (long)n, h, (const float*)hyper_dev);
+    return launch_status();
+}
+
 }  // extern "C"

@@ -641,23 +641,38 @@ _SCALER_KEYS = (("scale", _lib.SCALER_SCALE), ("growth_factor", _lib.SCALER_GROW
 class AdamWState:
     """What AdamW and the loss scaler keep besides the moments (`FlatParams.m`, `.v`), and the optimizer launch that reads it.
 
-    Where the scalars live is decided here, once: `on_device` (graph replay, precision 16) keeps the step counter as one int32 and
+    Where the scalars live is decided here, once: `on_device` (graph replay, precision 16, gradient clipping) keeps the step counter as one int32 and
     the hyper block (`_lib.HYPER_*`: the caller's slot is the learning rate, the rest is the launch's own) in device memory, so that
     the step never waits for the host; otherwise the counter is a Python int and the scalars travel as arguments.  Either way there
     is ONE counter, and `t` reads and writes it: on the device a read is one device -> host copy and a write one `fill_`.
 
     Precision 16 adds torch.amp.GradScaler on the device: the scaler block (`_lib.SCALER_*`) and the slot that max|g| is reduced
-    into.  Without them (`scaler is None`) the backward is seeded with the constant 1 and no step is skipped."""
+    into.  Without them (`scaler is None`) the backward is seeded with the constant 1 and no step is skipped.
+
+    `gradient_clip_val` (Lightning's Trainer knob, algorithm "norm") = torch.nn.utils.clip_grad_norm_(params, value, norm_type=2)
+    between the scaler's unscale and the update, on the device: one more launch reduces the sum of squares of the flat gradient buffer
+    and the optimizer launch's bookkeeping kernel turns it into the coefficient every gradient is multiplied by.  None or 0: off (not
+    one launch, buffer or attribute differs from a state built without the keyword); inf: the norm is measured, nothing is clipped.
+    `grad_norm` / `clip_coef` read the last launch's norm of the unscaled gradients and its coefficient.  At precision 16 an overflow
+    still skips the step (the norm recorded is then not finite); at precision 32 / bf16 a non-finite norm makes the coefficient nan and
+    poisons the update exactly as torch's clip + step would: no skip is invented there."""
 
     def __init__(self, dev, precision=32, graph=False, lr=1e-3, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5,
-                 growth_interval=2000):
-        self.on_device = bool(graph) or precision == 16
+                 growth_interval=2000, gradient_clip_val=None):
+        clip = float(gradient_clip_val or 0.0)
+        if not clip >= 0.0:
+            raise ValueError(f"gradient_clip_val must be None or >= 0, not {gradient_clip_val!r}")
+        self.on_device = bool(graph) or precision == 16 or clip > 0.0
         self.scaler = self.absmax = self.hyper = None
         self._count = 0                             # the step counter: this int, or (on_device) one int32 in device memory
         if self.on_device:
             self._count = torch.zeros(1, dtype=torch.int32, device=dev)
             self.hyper = torch.full((_lib.TRAIN_ADAMW_HYPER_FLOATS,), lr, dtype=torch.float32, device=dev)
             self._lr = self.hyper[_lib.HYPER_LR:_lib.HYPER_LR + 1]
+        self.max_norm = clip if clip > 0.0 else None      # None: no clipping -- no reduction launch, no partial sums, the plain optimizer launch
+        if self.max_norm is not None:
+            self._sumsq = torch.zeros(_lib.TRAIN_GRAD_NORM_PARTIALS, dtype=torch.float64, device=dev)
+            self.hyper[_lib.HYPER_GRAD_NORM], self.hyper[_lib.HYPER_CLIP_COEF] = 0.0, 1.0     # what a read-out before the first step gives
         if precision == 16:
             block = [0.0] * _lib.TRAIN_SCALER_FLOATS              # (clean steps in a row and skipped steps start at 0)
             block[_lib.SCALER_SCALE], block[_lib.SCALER_GROWTH_FACTOR] = init_scale, growth_factor
@@ -701,6 +716,22 @@ class AdamWState:
     def growth_interval(self, n):
         self._need_scaler("growth_interval")[_lib.SCALER_GROWTH_INTERVAL] = float(n)
 
+    # read-outs of the last clipped launch (one small device -> host copy each, like `scale`)
+    def _need_clip(self, what):
+        if self.max_norm is None:
+            raise AttributeError(f"no {what}: this step does not clip (gradient_clip_val is None or 0)")
+        return self.hyper
+
+    @property
+    def grad_norm(self):
+        """The 2-norm of the last launch's unscaled gradients, before clipping."""
+        return float(self._need_clip("grad_norm")[_lib.HYPER_GRAD_NORM].item())
+
+    @property
+    def clip_coef(self):
+        """min(1, gradient_clip_val / (grad_norm + 1e-6)) of the last launch: what its gradients were multiplied by."""
+        return float(self._need_clip("clip_coef")[_lib.HYPER_CLIP_COEF].item())
+
     def scaler_state_dict(self):
         """torch.amp.GradScaler.state_dict() of the scaler block; None without one."""
         if self.scaler is None:
@@ -730,10 +761,18 @@ class AdamWState:
             # nan above every finite magnitude -- decides inside the optimizer launch whether the update runs (on g / scale) or is
             # skipped with the scale backed off; nothing is read back.
             lib.esmi_absmax_f32(_ptr(f.grad), f.grad.numel(), _ptr(self.absmax), st)
+        if self.max_norm is not None:
+            # clip_grad_norm_ on the device: the buffer's sum of squares as per-workgroup partial sums; the optimizer launch adds them up,
+            # divides the norm by the loss scale and folds the coefficient into the scale that every gradient is multiplied by
+            lib.esmi_train_grad_sumsq_f32(_ptr(f.grad), f.grad.numel(), _ptr(self._sumsq), st)
         if self.on_device:                          # (the launch counts: a skipped step does not advance the counter)
             absmax, scaler = (None, None) if self.scaler is None else (_ptr(self.absmax), _ptr(self.scaler))
-            lib.esmi_train_adamw_graph_f32(_ptr(f.data), _ptr(f.grad), _ptr(f.m), _ptr(f.v), f.data.numel(), _ptr(self.hyper),
-                                           betas[0], betas[1], eps, weight_decay, _ptr(self._count), absmax, scaler, st)
+            args = (_ptr(f.data), _ptr(f.grad), _ptr(f.m), _ptr(f.v), f.data.numel(), _ptr(self.hyper), betas[0], betas[1], eps,
+                    weight_decay, _ptr(self._count), absmax, scaler)
+            if self.max_norm is not None:
+                lib.esmi_train_adamw_clip_f32(*args, _ptr(self._sumsq), self.max_norm, st)
+            else:
+                lib.esmi_train_adamw_graph_f32(*args, st)
         else:
             self._count += 1
             lib.esmi_train_adamw_f32(_ptr(f.data), _ptr(f.grad), _ptr(f.m), _ptr(f.v), f.data.numel(), lr, betas[0], betas[1], eps,
@@ -750,10 +789,13 @@ class TrainStep:
     that shape (inputs are copied into the graph's static buffers; step count, learning rate and the loss scaler live in device
     memory): the whole step on one GPU, everything up to the gradient all-reduce when data-parallel (the collective and the
     optimizer launch then follow eagerly).  The eager step is bound by the host's dispatch of its ~180-220 launches (pinned row by row in
-    tests/test_train_dispatch.py); the replay runs at the kernels' own pace (both are `bench.py`'s `train_step` leg)."""
+    tests/test_train_dispatch.py); the replay runs at the kernels' own pace (both are `bench.py`'s `train_step` leg).
+
+    gradient_clip_val=c (Lightning's Trainer knob; None / 0: off) clips the gradients' 2-norm to c before the update, on the device and
+    inside a captured graph; `grad_norm` and `clip_coef` read the last step's norm and coefficient (inf: measure only)."""
 
     def __init__(self, net, lr=1e-3, weight_decay=1e-6, betas=(0.9, 0.999), eps=1e-8, group=None, world_size=1, graph=False,
-                 precision=32, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+                 precision=32, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, gradient_clip_val=None):
         self.net, self.flat = net, FlatParams(net)
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         self.group, self.world = group, world_size
@@ -767,7 +809,10 @@ class TrainStep:
         precision = normalize_precision(precision)
         self.precision = precision
         self.graph = bool(graph)
-        self._opt = AdamWState(self.flat.data.device, precision, self.graph, lr, init_scale, growth_factor, backoff_factor, growth_interval)
+        # gradient_clip_val = Lightning's Trainer knob (algorithm "norm"): clip_grad_norm_ over the flat gradient buffer -- after the
+        # all-reduce and the division by the world size, so every rank clips by the same coefficient -- on the device (`AdamWState`)
+        self._opt = AdamWState(self.flat.data.device, precision, self.graph, lr, init_scale, growth_factor, backoff_factor, growth_interval,
+                               gradient_clip_val)
         self._graphs = {}
         self._build_pack_list()
         self._packed = networks.PackedCopies(net)   # what the inference path keeps of the weights this step's optimizer overwrites
@@ -778,6 +823,8 @@ class TrainStep:
     scale = property(lambda self: self._opt.scale)
     skipped = property(lambda self: self._opt.skipped)
     growth_interval = property(lambda self: self._opt.growth_interval, lambda self, n: setattr(self._opt, "growth_interval", n))
+    grad_norm = property(lambda self: self._opt.grad_norm)      # (both: AttributeError unless gradient_clip_val is set)
+    clip_coef = property(lambda self: self._opt.clip_coef)
 
     # ---- checkpoint / resume (what Lightning's ModelCheckpoint keeps: weights, hyper-parameters, the optimizer's state_dict)
     def hyper_parameters(self):
@@ -906,7 +953,7 @@ class TrainStep:
 
     def _optimize(self, lr):
         """The exchange (one all-reduce of the flat gradient buffer when data-parallel) and the optimizer launch, which reads step
-        count / learning rate (/ the loss scaler's state) from device memory under graph replay and precision 16."""
+        count / learning rate (/ the loss scaler's state) from device memory under graph replay, precision 16 and gradient clipping."""
         f = self.flat
         if self.world > 1:
             import torch.distributed as dist

@@ -837,7 +837,9 @@ int esmi_train_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n
 #define ESMI_HYPER_STEP_SIZE 2  /* lr / (1 - beta1^step) */
 #define ESMI_HYPER_BC2_SQRT 3   /* sqrt(1 - beta2^step) */
 #define ESMI_HYPER_SKIP 4       /* != 0: the gradients overflowed, this update does not run */
-#define ESMI_HYPER_GRAD_SCALE 5 /* 1 / loss scale (1 without a scaler) */
+#define ESMI_HYPER_GRAD_SCALE 5 /* 1 / loss scale (1 without a scaler); esmi_train_adamw_clip_f32: clip coefficient / loss scale */
+#define ESMI_HYPER_GRAD_NORM 6  /* esmi_train_adamw_clip_f32 only: the 2-norm of the unscaled gradients of its last call */
+#define ESMI_HYPER_CLIP_COEF 7  /* esmi_train_adamw_clip_f32 only: min(1, max_norm / (norm + 1e-6)) of its last call */
 /* ... and of scaler_state */
 #define ESMI_SCALER_SCALE 0
 #define ESMI_SCALER_GROWTH_FACTOR 1
@@ -848,6 +850,22 @@ int esmi_train_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n
 int esmi_train_adamw_graph_f32(float* p, const float* g, float* m, float* v, int64_t n, float* hyper_dev, double beta1, double beta2,
                                double eps, double weight_decay, int32_t* step_dev, const float* grad_absmax /* or NULL */,
                                float* scaler_state /* or NULL */, esmi_stream_t stream);
+/* Gradient-norm clipping on the device, torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) (Lightning's `gradient_clip_val`),
+ * in two calls and with nothing read back.
+ * esmi_train_grad_sumsq_f32: sum of g[i]^2 over a flat fp32 buffer (any n > 0; 16-byte loads where g is 16-byte aligned, a scalar
+ * tail), as ESMI_TRAIN_GRAD_NORM_PARTIALS doubles -- one per workgroup of a fixed grid, the unused ones zeroed: their sum, in any fixed
+ * order, is the result.  Squares and sums are formed in double and there are no atomics: the same buffer gives the same bits.
+ * esmi_train_adamw_clip_f32: esmi_train_adamw_graph_f32 with the clipping between the unscale and the update.  sumsq_partials = what
+ * esmi_train_grad_sumsq_f32 left of the SAME (exchanged, still scaled) gradient buffer; max_norm > 0 (inf: measure only).  The norm is
+ * sqrt(sum) / loss scale, the coefficient min(1, max_norm / (norm + 1e-6)) in fp32 as torch forms it, and the update runs on
+ * g * coefficient / scale; both are left in hyper_dev[ESMI_HYPER_GRAD_NORM] / [ESMI_HYPER_CLIP_COEF].  With a scaler the skip rule is that
+ * of esmi_train_adamw_graph_f32 (the recorded norm of a skipped step is whatever non-finite value came out); without one a non-finite norm
+ * makes the coefficient nan and poisons the update, as in torch: no step is skipped. */
+#define ESMI_TRAIN_GRAD_NORM_PARTIALS 1024
+int esmi_train_grad_sumsq_f32(const float* g, int64_t n, double* partials /* ESMI_TRAIN_GRAD_NORM_PARTIALS doubles */, esmi_stream_t stream);
+int esmi_train_adamw_clip_f32(float* p, const float* g, float* m, float* v, int64_t n, float* hyper_dev, double beta1, double beta2,
+                              double eps, double weight_decay, int32_t* step_dev, const float* grad_absmax /* or NULL */,
+                              float* scaler_state /* or NULL */, const double* sumsq_partials, double max_norm, esmi_stream_t stream);
 
 #ifdef __cplusplus
 }

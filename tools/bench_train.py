@@ -12,7 +12,7 @@ from efficientspeech_amd.synth import synth_state_dict
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="tiny"); ap.add_argument("--batch", type=int, default=32)
-    ap.add_argument("--phonemes", type=int, default=128); ap.add_argument("--dur", type=int, default=6); ap.add_argument("--iters", type=int, default=5); ap.add_argument("--graph", action="store_true"); ap.add_argument("--precision", default="32", choices=["32", "16", "bf16"]); ap.add_argument("--torch-mirror", action="store_true", help="time plain PyTorch-ROCm ops (tests/torch_mirror.py + torch.optim.AdamW) on the same batch instead")
+    ap.add_argument("--phonemes", type=int, default=128); ap.add_argument("--dur", type=int, default=6); ap.add_argument("--iters", type=int, default=5); ap.add_argument("--graph", action="store_true"); ap.add_argument("--precision", default="32", choices=["32", "16", "bf16"]); ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="V", help="TrainStep(gradient_clip_val=V): clip the gradients' 2-norm to V on the device (inf: measure only)"); ap.add_argument("--torch-mirror", action="store_true", help="time plain PyTorch-ROCm ops (tests/torch_mirror.py + torch.optim.AdamW) on the same batch instead")
     a = ap.parse_args()
     cfg = CONFIGS[a.config]
     net = build_phoneme2mel(cfg)
@@ -34,7 +34,7 @@ if __name__ == "__main__":
                 return torch.stack([*[p.detach() for p in parts], total.detach()])
         step = _S()
     else:
-        step = train.TrainStep(net, graph=a.graph, precision=a.precision, init_scale=2048.0)
+        step = train.TrainStep(net, graph=a.graph, precision=a.precision, init_scale=2048.0, gradient_clip_val=a.clip_grad_norm)
     for _ in range(3):
         l0 = step.step(x, y)
     torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -44,4 +44,5 @@ if __name__ == "__main__":
     frames = a.batch * a.phonemes * a.dur
     mode = " (plain PyTorch-ROCm ops)" if a.torch_mirror else (" (hipGraph)" if a.graph else "")
     print(f"train step{mode} {a.config}: B={a.batch} T={a.phonemes} L={a.phonemes * a.dur}: {dt * 1e3:.1f} ms/step  {frames / dt:.3e} mel-frames/s  "
-          f"loss {float(l0[4]):.3f} -> {float(l1[4]):.3f}")
+          f"loss {float(l0[4]):.3f} -> {float(l1[4]):.3f}"
+          + (f"  grad norm {step.grad_norm:.4g} clip coef {step.clip_coef:.4g}" if a.clip_grad_norm and not a.torch_mirror else ""))
