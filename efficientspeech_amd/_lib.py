@@ -39,6 +39,10 @@ _NAMES = ("MAX_DEPTH MAX_DEC_LAYERS HIFIGAN_MAX_UP HIFIGAN_MAX_KERNELS HIFIGAN_M
           "HYPER_STEP_SIZE HYPER_BC2_SQRT HYPER_SKIP HYPER_GRAD_SCALE HYPER_GRAD_NORM HYPER_CLIP_COEF SCALER_SCALE SCALER_GROWTH_FACTOR SCALER_BACKOFF_FACTOR SCALER_GROWTH_INTERVAL "
           "SCALER_CLEAN_STEPS SCALER_SKIPPED")
 MIRRORED = {"ESMI_OK": ESMI_OK, **{"ESMI_" + n: globals()[n] for n in _NAMES.split()}}      # header name -> the value held here
+# csrc/wavesim_shim.h's kReduceGroups, the waves of a deterministic-reduction workgroup, by `esmi_backend()`: no entry point reports it,
+# and a caller that builds an `esmi_reduce_queue` by hand needs it to place chunk counts on the reduction loop's edges (tests only;
+# tests/test_abi_exports.py compares it with the header)
+REDUCE_GROUPS = {"wavesim": 4, "hip:gfx950": 16}
 
 _ERRS = {ERR_ARG: "ESMI_ERR_ARG (null pointer / bad size / misaligned)",
          ERR_UNSUPPORTED: "ESMI_ERR_UNSUPPORTED (shape outside what the kernels are built for)",

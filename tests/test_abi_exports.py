@@ -53,6 +53,17 @@ def test_python_mirrors_the_headers_constants():
     assert len(_lib.ReduceQueue().items) == header["ESMI_REDUCE_QUEUE_ITEMS"]      # (the struct takes its length from the mirror)
 
 
+def test_python_mirrors_the_reduction_workgroups_waves():
+    """`_lib.REDUCE_GROUPS` repeats csrc/wavesim_shim.h's kReduceGroups per backend name: the simulator branch's pair first, the
+    product build's behind its #else."""
+    from efficientspeech_amd import _lib
+    src = open(os.path.join(ROOT, "efficientspeech_amd", "csrc", "wavesim_shim.h")).read()
+    names = re.findall(r'constexpr const char\* kBackendName = "([^"]+)";', src)
+    groups = [int(v) for v in re.findall(r"constexpr int kReduceGroups = (\d+);", src)]
+    assert len(names) == len(groups) == 2                            # (findall keeps the file's order: each name with its own constant)
+    assert dict(zip(names, groups)) == _lib.REDUCE_GROUPS
+
+
 def exported_esmi_symbols(path):
     """Dynamic symbols of the shared library that start with esmi_ (nm -D --defined-only)."""
     import subprocess

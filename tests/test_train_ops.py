@@ -4,7 +4,9 @@ tiles that are not multiples of 32, strided / transposed / depthwise convolution
 here, as the numerics-test rule asks; the step-level parity is pinned to the reference fixture in test_train_step.py.)
 The largest convolution here has 3,500 rows, all at precision 32: on the device that reaches `convgemm_kernel` and, for the one k = 1
 shape above 2,048 rows, `convgemm_dma_kernel<4, 1>` -- not the kernels of a benchmark-size step (`pwgemm_kernel` from 32,768 rows,
-`convgemm_dma_kernel<4, 2>`) and no `precision = 16` instantiation; those are test_train_gemm_at_size.py's."""
+`convgemm_dma_kernel<4, 2>`) and no `precision = 16` instantiation; those are test_train_gemm_at_size.py's.  Nor do these shapes leave the
+common branch of the host code's choices between kernels (global-memory attention, misaligned or odd-width LayerNorm, the one-channel Linear's
+and the depthwise convolutions' variants): every such branch is a row of test_train_variants.py, against float64."""
 import numpy as np
 import pytest
 import torch
