@@ -1,4 +1,4 @@
-// esmi C-ABI, translation unit "tu_train.hip": the training step's operators (train_ops.h)
+// esmi C-ABI, translation unit "tu_train.hip": the training step's operators (train_ops.h and the train_*.h family headers it includes)
 // One of several translation units of libesmi.so (compiled in parallel by __graft_entry__.build(); the simulator build
 // tools/wavesim/build.sh compiles the same files with the host compiler).  Internal launchers are declared in launch.h.
 #include "launch.h"
@@ -7,9 +7,15 @@
 using namespace esmi;
 ESMI_TU_RANGE_SETTER(train)
 
+namespace {
+// every pointer 16-byte aligned (a null pointer counts as aligned: an absent optional tensor does not decide)
+template <class... P>
+inline bool aligned16(const P*... p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & 15u) == 0; }
+}  // namespace
+
 extern "C" {
 
-// ------------------------------------------------------------------ training step (csrc/train_ops.h)
+// ------------------------------------------------------------------ training step (csrc/train_ops.h: one header per operator family)
 namespace {
 int conv_desc_ok(const esmi_conv_desc* d, ConvDesc* o) {
     PrecisionMode mode;
@@ -58,7 +64,7 @@ int reduce_or_defer(esmi_reduce_queue* q, const float* part, long n, long stride
 // the workspace, reduce_or_defer sums them.  WgradPlan is the one description of that layout.
 inline bool wgrad_depthwise(const ConvDesc& c) { return !c.transposed && c.groups == c.c_in && c.c_in == c.c_out && c.k <= 8; }
 inline bool wgrad_on_mfma(const ConvDesc& c) {
-    // (train_ops.h train_conv_wgrad_mfma_kernel: 32-bit byte offsets into both tensors, one utterance boundary per 16-row trip at most)
+    // (train_wgrad.h train_conv_wgrad_mfma_kernel: 32-bit byte offsets into both tensors, one utterance boundary per 16-row trip at most)
     const long xb = (long)c.B * c.n_in * c.c_in * 4, yb = (long)c.B * c.n_out * c.c_out * 4;
     return c.groups == 1 && c.c_in >= 8 && c.c_out >= 8 && (c.c_out & 3) == 0 && c.n_out >= 16 && c.n_out < (1 << 23) && xb < 0x7FFFFFFFL && yb < 0x7FFFFFFFL;
 }
@@ -122,7 +128,7 @@ int conv_wgrad(const ConvDesc& c, const WgradPlan& p, const float* x, const floa
 // (convgemm.h) when there is room for the tap-major copy of the weight: the forward as it is, the data gradient as
 // the transposed problem -- d(Conv1d) is a ConvTranspose1d of dy with the same (Cout, Cin, k) tensor read as (Cin', Cout', k),
 // d(ConvTranspose1d) is a Conv1d of dy with (Cin, Cout, k) read as (Cout', Cin', k).  Everything else (depthwise, channel
-// counts the GEMM does not take, no room) runs the one-thread-per-element kernels of train_ops.h.
+// counts the GEMM does not take, no room) runs the one-thread-per-element kernels of train_conv.h.
 // how the GEMM of one direction reads the weight tensor: (supported, needs a copy, read as ConvTranspose1d, taps flipped)
 struct GemmWeight { bool ok, copy; int as_convT; bool flipped; int cin, cout; };
 GemmWeight gemm_weight(const ConvDesc& c, bool grad) {
@@ -332,10 +338,10 @@ int esmi_train_conv_bwd_f32(const esmi_conv_desc* d, const float* x, const float
         return launch_conv_gemm(c, g, true, dy, wc.wt, nullptr, dx, amp, amax, 0, nullptr, S(stream));
     }
     if (c.c_out == 1 && c.k == 1 && c.stride == 1 && c.pad == 0 && c.groups == 1 && !c.transposed && c.n_in == c.n_out && p.chunk <= 64) {
-        // a Linear down to one channel: the three gradients in one launch (train_ops.h train_lin1_bwd_kernel); its partial rows are
+        // a Linear down to one channel: the three gradients in one launch (train_wgrad.h train_lin1_bwd_kernel); its partial rows are
         // [weight partials (c_in) | bias partial]
         const long ps = c.c_in + 1;
-        const bool al16 = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(w)) & 15) == 0;
+        const bool al16 = aligned16(x, dx, w);
         float* pbias = dbias ? part + c.c_in : nullptr;
 #define ESMI_LIN1(LPR) ESMI_LAUNCH(train_lin1_bwd4_kernel<LPR>, dim3((unsigned)p.chunks), dim3(64), 0, S(stream), x, dy, w, p.rows, dx, part, pbias, ps)
         if (al16 && p.chunk == 32 && c.c_in == 16) ESMI_LIN1(4);
@@ -356,9 +362,7 @@ int esmi_train_conv_bwd_f32(const esmi_conv_desc* d, const float* x, const float
 int esmi_train_layernorm_fwd_f32(const float* x, const float* g, const float* b, int64_t rows, int C, float* y, float* mean,
                                  float* rstd, const float* res, float* xsum, const uint8_t* rowmask, int relu_out, esmi_stream_t stream) {
     if (!x || !g || !b || !y || !mean || !rstd || rows <= 0 || C <= 0 || (res && !xsum)) return ESMI_ERR_ARG;
-    uintptr_t al = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(b);
-    if (res) al |= reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(xsum);
-    if ((al & 15) == 0 && (C == 32 || C == 64 || C == 128 || C == 256)) {   // rows in registers, 16-byte accesses
+    if (aligned16(x, y, g, b) && (!res || aligned16(res, xsum)) && (C == 32 || C == 64 || C == 128 || C == 256)) {   // rows in registers, 16-byte accesses
 #define ESMI_LN4(LPR) ESMI_LAUNCH(train_ln_fwd4_kernel<LPR>, grid1d(rows, 4 * (64 / LPR)), dim3(256), 0, S(stream), x, g, b, (long)rows, 1e-5f, y, mean, rstd, res, xsum, rowmask, relu_out ? 1 : 0)
         if (C == 32) ESMI_LN4(8); else if (C == 64) ESMI_LN4(16); else if (C == 128) ESMI_LN4(32); else ESMI_LN4(64);
 #undef ESMI_LN4
@@ -381,9 +385,7 @@ int esmi_train_layernorm_bwd_f32(const float* x, const float* g, const float* me
     long chunks;
     if (C <= 256) {   // dx and the parameter partials in one pass
         chunks = train_chunks(rows, kLnRows);
-        uintptr_t al = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(g);
-        if (y_relu) al |= reinterpret_cast<uintptr_t>(y_relu);
-        if ((al & 15) == 0 && (C == 32 || C == 64 || C == 128)) {   // rows in registers, 16-byte accesses, all rows of a wave loaded up front
+        if (aligned16(x, dy, dx, g, y_relu) && (C == 32 || C == 64 || C == 128)) {   // rows in registers, 16-byte accesses, all rows of a wave loaded up front
 #define ESMI_LNB4(LPR) ESMI_LAUNCH(train_ln_bwd4_kernel<LPR>, dim3((unsigned)chunks), dim3(256), 4 * 2 * 256 * sizeof(float), S(stream), x, g, mean, rstd, dy, (long)rows, dx, part, rowmask, in_act, y_relu)
             if (C == 32) ESMI_LNB4(8); else if (C == 64) ESMI_LNB4(16); else ESMI_LNB4(32);
 #undef ESMI_LNB4
@@ -424,11 +426,8 @@ int esmi_train_attention_fwd_f32(const float* qkv, int B, int N, int C, int h, f
     if (!qkv || !P || !ctx || B <= 0 || N <= 0 || C <= 0 || h <= 0 || C % h) return ESMI_ERR_ARG;
     const size_t lds = train_attn_lds_bytes(N, C);
     if (lds <= 150 * 1024) {   // K and V of a head staged in LDS
-        static AttrOnce once;
-        if (lds > 48 * 1024)
-            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(train_attn_fwd_lds_kernel), once)) return rc;
-        ESMI_LAUNCH(train_attn_fwd_lds_kernel, dim3((unsigned)(B * h), attn_row_segments(B * h, N)), dim3(256), lds, S(stream), qkv, B, N, C, h,
-                    1.0f / sqrtf((float)(C / h)), P, ctx);
+        ESMI_LAUNCH_LDS(train_attn_fwd_lds_kernel, dim3((unsigned)(B * h), attn_row_segments(B * h, N)), dim3(256), lds, S(stream), qkv, B, N, C, h,
+                        1.0f / sqrtf((float)(C / h)), P, ctx);
         return launch_status();
     }
     ESMI_LAUNCH(train_attn_fwd_kernel, dim3((unsigned)((long)B * h * N)), dim3(64), 0, S(stream), qkv, B, N, C, h, 1.0f / sqrtf((float)(C / h)), P, ctx);
@@ -440,11 +439,8 @@ int esmi_train_attention_bwd_f32(const float* qkv, const float* P, const float* 
     const float scale = 1.0f / sqrtf((float)(C / h));
     const size_t lds = train_attn_lds_bytes(N, C);
     if (lds <= 150 * 1024) {
-        static AttrOnce once;
-        if (lds > 48 * 1024)
-            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(train_attn_bwd_rows_lds_kernel), once)) return rc;
-        ESMI_LAUNCH(train_attn_bwd_rows_lds_kernel, dim3((unsigned)(B * h), attn_row_segments(B * h, N)), dim3(256), lds, S(stream), qkv, P, dctx,
-                    B, N, C, h, scale, dS, dqkv);
+        ESMI_LAUNCH_LDS(train_attn_bwd_rows_lds_kernel, dim3((unsigned)(B * h), attn_row_segments(B * h, N)), dim3(256), lds, S(stream), qkv, P, dctx,
+                        B, N, C, h, scale, dS, dqkv);
     } else {
         ESMI_LAUNCH(train_attn_bwd_rows_kernel, dim3((unsigned)((long)B * h * N)), dim3(64), 0, S(stream), qkv, P, dctx, B, N, C, h, scale, dS, dqkv);
     }
@@ -503,7 +499,7 @@ int esmi_train_cat_f32(float* const* parts, const int* widths, int n, int64_t ro
 }
 int esmi_train_repeat_fwd_f32(const float* feat, const int32_t* cum, int B, int T, int C, int L, float* out, esmi_stream_t stream) {
     if (!feat || !cum || !out || B <= 0 || T <= 0 || C <= 0 || L <= 0) return ESMI_ERR_ARG;
-    if ((C & 3) == 0 && (long)B * L * (C / 4) < 0x7FFFFFFFL && ((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(out)) & 15) == 0) {
+    if ((C & 3) == 0 && (long)B * L * (C / 4) < 0x7FFFFFFFL && aligned16(feat, out)) {
         ESMI_LAUNCH(train_repeat_fwd4_kernel, grid1d((long)B * L * (C / 4)), dim3(256), 0, S(stream), feat, cum, B, T, C / 4, L, out);
         return launch_status();
     }
@@ -530,13 +526,27 @@ int esmi_train_loss_f32(const esmi_train_loss_args* a, esmi_stream_t stream) {
     ESMI_LAUNCH(train_loss_grad_kernel, grid1d(nm > np_ ? nm : np_), dim3(256), 0, S(stream), p);
     return launch_status();
 }
+namespace {
+// the scalars that do not depend on the step; decay, step size and bias correction come from the host (esmi_train_adamw_f32) or from
+// `hyper` on the device (train_adamw_dev_kernel)
+inline AdamWScalars adamw_scalars(double beta1, double beta2, double eps) {
+    return {(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, 0.0f, 0.0f, 0.0f, 1.0f};
+}
+// the update behind either bookkeeping launch (train_bump_step_kernel / train_bump_clip_kernel): everything step-dependent read from `hyper`
+int adamw_dev_update(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper_dev, double beta1, double beta2, double eps,
+                     hipStream_t st) {
+    if (int rc = launch_status()) return rc;
+    ESMI_LAUNCH(train_adamw_dev_kernel, grid1d(n), dim3(256), 0, st, p, g, m, v, (long)n, adamw_scalars(beta1, beta2, eps), hyper_dev);
+    return launch_status();
+}
+}  // namespace
 int esmi_train_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
                          double weight_decay, int step, double grad_scale, esmi_stream_t stream) {
     if (!p || !g || !m || !v || n <= 0 || step < 1 || !(grad_scale > 0.0)) return ESMI_ERR_ARG;
     // 1 - beta^step in double (-expm1(step * log beta)): in fp32, 1 - 0.999f^t carries ~6e-5 relative error at small t
     const double bc1 = -expm1((double)step * log(beta1)), bc2 = -expm1((double)step * log(beta2));
-    AdamWScalars h = {(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)(1.0 - lr * weight_decay),
-                      (float)(lr / bc1), (float)sqrt(bc2), (float)grad_scale};
+    AdamWScalars h = adamw_scalars(beta1, beta2, eps);
+    h.decay = (float)(1.0 - lr * weight_decay); h.step_size = (float)(lr / bc1); h.bc2_sqrt = (float)sqrt(bc2); h.gscale = (float)grad_scale;
     ESMI_LAUNCH(train_adamw_kernel, grid1d(n), dim3(256), 0, S(stream), p, g, m, v, (long)n, h);
     return launch_status();
 }
@@ -547,15 +557,12 @@ int esmi_train_adamw_graph_f32(float* p, const float* g, float* m, float* v, int
     if (!p || !g || !m || !v || !hyper_dev || !step_dev || n <= 0 || ((scaler_state != nullptr) != (grad_absmax != nullptr))) return ESMI_ERR_ARG;
     ESMI_LAUNCH(train_bump_step_kernel, dim3(1), dim3(64), 0, S(stream), step_dev, hyper_dev, beta1, beta2, weight_decay, grad_absmax,
                 scaler_state);
-    if (int rc = launch_status()) return rc;
-    AdamWScalars h = {(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, 0.0f, 0.0f, 0.0f, 1.0f};
-    ESMI_LAUNCH(train_adamw_dev_kernel, grid1d(n), dim3(256), 0, S(stream), p, g, m, v, (long)n, h, (const float*)hyper_dev);
-    return launch_status();
+    return adamw_dev_update(p, g, m, v, n, hyper_dev, beta1, beta2, eps, S(stream));
 }
 
 int esmi_train_grad_sumsq_f32(const float* g, int64_t n, double* partials, esmi_stream_t stream) {
     if (!g || !partials || n <= 0 || (reinterpret_cast<uintptr_t>(partials) & 7) != 0) return ESMI_ERR_ARG;
-    const long n4 = (reinterpret_cast<uintptr_t>(g) & 15) == 0 ? (long)(n >> 2) : 0;   // whole 16-byte loads; the rest is the scalar tail
+    const long n4 = aligned16(g) ? (long)(n >> 2) : 0;   // whole 16-byte loads; the rest is the scalar tail
     const long work = n4 > 0 ? n4 : (long)n, blocks = (work + 255) / 256;
     ESMI_LAUNCH(train_grad_sumsq_kernel, dim3((unsigned)(blocks > ESMI_TRAIN_GRAD_NORM_PARTIALS ? ESMI_TRAIN_GRAD_NORM_PARTIALS : blocks)),
                 dim3(256), 256 * sizeof(double), S(stream), g, n4, (long)n, partials);
@@ -570,10 +577,7 @@ int esmi_train_adamw_clip_f32(float* p, const float* g, float* m, float* v, int6
         return ESMI_ERR_ARG;
     ESMI_LAUNCH(train_bump_clip_kernel, dim3(1), dim3(256), 256 * sizeof(double), S(stream), step_dev, hyper_dev, beta1, beta2, weight_decay,
                 grad_absmax, scaler_state, sumsq_partials, max_norm);
-    if (int rc = launch_status()) return rc;
-    AdamWScalars h = {(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, 0.0f, 0.0f, 0.0f, 1.0f};
-    ESMI_LAUNCH(train_adamw_dev_kernel, grid1d(n), dim3(256), 0, S(stream), p, g, m, v, (long)n, h, (const float*)hyper_dev);
-    return launch_status();
+    return adamw_dev_update(p, g, m, v, n, hyper_dev, beta1, beta2, eps, S(stream));
 }
 
 }  // extern "C"

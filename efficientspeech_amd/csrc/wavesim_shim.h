@@ -28,8 +28,8 @@ namespace esmi {
 // LDS-staged kernels at every size so that the tests reach them)
 #ifdef ESMI_WAVESIM
 constexpr const char* kBackendName = "wavesim";
-constexpr int kReduceGroups = 4;            // train_ops.h: waves per deterministic-reduction workgroup
-constexpr int kLossBlocks = 8;              // train_ops.h: workgroups of the loss kernel
+constexpr int kReduceGroups = 4;            // train_reduce.h: waves per deterministic-reduction workgroup
+constexpr int kLossBlocks = 8;              // train_loss.h: workgroups of the loss kernel
 constexpr int kAttnLdsMinHeadsDefault = 1;  // tu_attention.hip: (utterance, head) pairs from which attention is LDS-staged
 constexpr int kGemmLdsMinRowsDefault = 1;   // tu_convgemm.hip: rows from which a GEMM is LDS-staged
 constexpr int kPwGemmMinRows = 1;           // tu_convgemm.hip: rows from which a k = 1 GEMM keeps its whole weight in LDS (pwgemm.h)

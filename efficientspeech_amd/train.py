@@ -1,7 +1,7 @@
 """Training step of the acoustic model on MI355X (reference: model.py:167-226 loss + training_step,
 :279-283 AdamW, train.py:66-76; the train=True data flow of layers/networks.py:336-434).
 
-Every arithmetic operation of the step is a HIP kernel behind the C-ABI (`esmi_train_*`, csrc/train_ops.h): forward operators
+Every arithmetic operation of the step is a HIP kernel behind the C-ABI (`esmi_train_*`, csrc/train_ops.h and the train_*.h it includes): forward operators
 that keep what their backward reads, data- and weight-gradient kernels, the fused masked loss, AdamW.  torch.autograd is used
 as the TAPE only (which operator's backward runs when, and the accumulation of gradients that fan in); torch.distributed
 (RCCL) carries the one gradient all-reduce.  Parameters and gradients of the model live in ONE flat fp32 buffer each

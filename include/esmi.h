@@ -687,8 +687,9 @@ int esmi_mask_rows_f32(float* x, const uint8_t* mask, int64_t rows, int C, esmi_
  * model.py:167-226 (loss, training_step), :279-283 (AdamW); the train=True data flow of layers/networks.py:336-434.
  * Operator-level entry points: each forward keeps what its backward reads; activations are channels-last (B, n, C) fp32,
  * weights and their gradients are in CHECKPOINT layout (what the optimizer updates): Conv1d (Cout, Cin/groups, k),
- * ConvTranspose1d (Cin, Cout, k), Linear (Cout, Cin) = a conv with k = 1.  First correct version: one thread per output
- * element, fp32 FMA loops, no atomics (a step is bitwise reproducible); see csrc/train_ops.h.  The Python side
+ * ConvTranspose1d (Cin, Cout, k), Linear (Cout, Cin) = a conv with k = 1.  Every sum runs in a fixed order (two-stage
+ * reductions over the rows; the one atomic is an order-independent integer max), so a step is bitwise reproducible: the
+ * contract and what it covers are stated in csrc/train_ops.h, the kernels live in the csrc/train_*.h it includes.  The Python side
  * (efficientspeech_amd/train.py) composes them with torch.autograd as the tape. */
 #define ESMI_PRECISION_BF16 0xB16 /* esmi_conv_desc.precision: bf16-mixed (below); the inference entry points' `precision`: bf16 (above) */
 typedef struct esmi_conv_desc {

@@ -55,8 +55,11 @@ def test_variant_check_catches_a_perturbed_gradient(row_id, what, message):
 
 # ---------------------------------------------------------------------------------------------------------------- completeness
 def kernels_of_train_ops():
-    """The `__global__` kernels of csrc/train_ops.h, templates as the instantiations tu_train.hip launches."""
-    src = open(os.path.join(ROOT, "efficientspeech_amd", "csrc", "train_ops.h")).read()
+    """The `__global__` kernels of the family headers csrc/train_ops.h includes (its `#include "train_*.h"` lines are the list), templates
+    as the instantiations tu_train.hip launches."""
+    csrc = os.path.join(ROOT, "efficientspeech_amd", "csrc")
+    headers = re.findall(r'^#include "(train_\w+\.h)"', open(os.path.join(csrc, "train_ops.h")).read(), re.M)
+    src = "".join(open(os.path.join(csrc, h)).read() for h in headers)
     found = re.findall(r"__global__\s+(?:__launch_bounds__\([^)]*\)\s+)?void\s+(\w+)\s*\(", src)
     assert len(found) == len(set(found)) >= 40 and set(K.INSTANTIATIONS) <= set(found)
     out = []

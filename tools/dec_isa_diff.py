@@ -6,6 +6,9 @@
 Compiles the five decoder translation units (or those named by --units, e.g. profiles/va_decide_refactor.md) for each library of __graft_entry__.VARIANTS to device assembly
 (FLAGS + the variant's defines + --cuda-device-only -S), replaces __hip_cuid_<hash> (derived from the output path) and reports per unit:
 "identical", or the second form: the kernels' resource metadata and the histogram of every mnemonic that is not scalar ALU / move.
+A unit that differs also lists which function symbols' text differs, with their code sizes; in a unit of many kernels (tu_train: 71
+symbols) the second form is judged per kernel: equal metadata, and equal counts of memory, MFMA and barrier instructions in every kernel
+whose text differs (profiles/r21_train_ops_split.md).
 Exit status 0 when every unit is identical or passes the second form.
 """
 import collections
@@ -50,6 +53,22 @@ def facts(text):
     return meta, hist
 
 
+TRAFFIC = re.compile(r"^(buffer_|global_|flat_|scratch_|ds_|v_mfma_|s_barrier)")
+
+
+def symbols(text):
+    """per function symbol (the listing split at its `_Z...:` labels): the body's text, its code size, its memory / matrix / barrier mnemonics"""
+    out = {}
+    for part in re.split(r"^(?=_Z\w+:)", text, flags=re.M)[1:]:
+        if ".Lfunc_end" not in part:
+            continue
+        body = re.sub(r"BB\d+_", "BB_", part.split(".Lfunc_end")[0])   # (block labels carry the function's ordinal in the unit)
+        ops = collections.Counter(s.split()[0] for s in (ln.strip() for ln in body.splitlines()[1:]) if s and s[0] not in ".;" and not s.endswith(":"))
+        size = re.search(r"codeLenInByte = (\d+)", part)
+        out[part[:part.index(":")]] = (body, int(size.group(1)) if size else -1, {m: n for m, n in ops.items() if TRAFFIC.match(m)})
+    return out
+
+
 def main():
     args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] not in ("--out", "--units")]
     parent, branch = os.path.abspath(args[0]), os.path.abspath(args[1])
@@ -70,10 +89,16 @@ def main():
         dm = [(k, f, ma[k].get(f), mb.get(k, {}).get(f)) for k in ma for f in ma[k] if ma[k].get(f) != mb.get(k, {}).get(f)]
         dh = [(m, ha[m], hb[m]) for m in sorted(set(ha) | set(hb)) if ha[m] != hb[m]]
         gated = [d for d in dh if GATED.match(d[0])]
-        ok = not dm and not gated and set(ma) == set(mb)
+        sa, sb = symbols(a), symbols(b)
+        moved = [k for k in sa if k in sb and sa[k][0] != sb[k][0]]
+        traffic = [k for k in moved if sa[k][2] != sb[k][2]]
+        ok = not dm and not (gated if len(sa) < 2 else traffic) and set(ma) <= set(mb) and set(sa) <= set(sb)
         bad += not ok
         print(f"{lib:22s} {unit:14s} {'second form' if ok else 'DIFFERS'}: metadata {dm or 'equal'}; gated mnemonics {gated or 'equal'}; "
               f"scalar ALU / move {[d for d in dh if not GATED.match(d[0])] or 'equal'}")
+        print(f"    {len(sa) - len(moved)} of {len(sa)} symbols identical; missing in the branch: {sorted(set(sa) - set(sb)) or 'none'}")
+        for k in moved:   # which kernels' text differs, their code sizes, and whether they issue the same memory / matrix / barrier operations
+            print(f"    differs: {k}  {sa[k][1]} -> {sb[k][1]} bytes; memory / mfma / barrier counts {'equal' if k not in traffic else (sa[k][2], sb[k][2])}")
     return 1 if bad else 0
 
 
