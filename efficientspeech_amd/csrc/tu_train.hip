@@ -1,8 +1,10 @@
 // esmi C-ABI, translation unit "tu_train.hip": the training step's operators (train_ops.h and the train_*.h family headers it includes)
+// and the gradient accumulator (train_accum.h)
 // One of several translation units of libesmi.so (compiled in parallel by __graft_entry__.build(); the simulator build
 // tools/wavesim/build.sh compiles the same files with the host compiler).  Internal launchers are declared in launch.h.
 #include "launch.h"
 #include "train_ops.h"
+#include "train_accum.h"
 
 using namespace esmi;
 ESMI_TU_RANGE_SETTER(train)
@@ -578,6 +580,18 @@ int esmi_train_adamw_clip_f32(float* p, const float* g, float* m, float* v, int6
     ESMI_LAUNCH(train_bump_clip_kernel, dim3(1), dim3(256), 256 * sizeof(double), S(stream), step_dev, hyper_dev, beta1, beta2, weight_decay,
                 grad_absmax, scaler_state, sumsq_partials, max_norm);
     return adamw_dev_update(p, g, m, v, n, hyper_dev, beta1, beta2, eps, S(stream));
+}
+
+int esmi_train_grad_accumulate_f32(float* acc, const float* g, int64_t n, float weight, esmi_stream_t stream) {
+    if (!acc || !g || n < 0) return ESMI_ERR_ARG;
+    if (n == 0) return ESMI_OK;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(acc), g0 = reinterpret_cast<uintptr_t>(g), bytes = (uintptr_t)n * sizeof(float);
+    if (a0 < g0 + bytes && g0 < a0 + bytes) return ESMI_ERR_ARG;   // the two ranges overlap
+    const long n4 = aligned16(acc, g) ? (long)(n >> 2) : 0;        // whole 16-byte loads and stores; the rest is the scalar tail
+    const long work = n4 > 0 ? n4 : (long)n, blocks = (work + 255) / 256;
+    ESMI_LAUNCH(train_grad_accumulate_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, S(stream), acc, g, n4, (long)n,
+                weight);
+    return launch_status();
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@ reference-compatible checkpoint and the inference path (`networks.py`) picks the
 import contextlib
 import ctypes as C
 import dataclasses
+import numbers
 
 import torch
 
@@ -609,9 +610,11 @@ _UNREACHED = ("encoder.pitch_decoder.norm2.", "encoder.energy_decoder.norm2.")
 
 
 class FlatParams:
-    """All trainable parameters of a module as views into one flat fp32 buffer, their gradients into another."""
+    """All trainable parameters of a module as views into one flat fp32 buffer, their gradients into another.  accumulate=True adds
+    `acc`, the running sum of a window of micro-batch gradients (`TrainStep(accumulate_grad_batches=N)`); without it there is no such
+    attribute."""
 
-    def __init__(self, net):
+    def __init__(self, net, accumulate=False):
         named = [(k, p) for k, p in net.named_parameters() if p.requires_grad and not k.startswith(_UNREACHED)]
         self.names = [k for k, _ in named]
         self.params = [p for _, p in named]
@@ -623,6 +626,8 @@ class FlatParams:
         self.data = torch.zeros(n, dtype=torch.float32, device=dev)          # (pad elements stay 0 under AdamW: g = 0, p = 0)
         self.grad = torch.zeros(n, dtype=torch.float32, device=dev)
         self.m, self.v = torch.zeros_like(self.data), torch.zeros_like(self.data)
+        if accumulate:
+            self.acc = torch.zeros_like(self.grad)  # (pad elements stay 0 here too: the accumulate launch adds weight * 0)
         for p, sl in zip(self.params, self.slices):
             self.data[sl].copy_(p.detach().reshape(-1))
             p.data = self.data[sl].view(p.shape)
@@ -752,22 +757,24 @@ class AdamWState:
         if self.on_device:
             self._lr.fill_(lr)
 
-    def launch(self, flat, lr, betas, eps, weight_decay):
-        """One AdamW update of `flat` by its (already exchanged) gradients."""
+    def launch(self, flat, lr, betas, eps, weight_decay, grad=None):
+        """One AdamW update of `flat` by its (already exchanged) gradients: `grad`, the buffer all three launches read -- None: `flat.grad`;
+        a `TrainStep` that accumulates passes `flat.acc` on a window's boundary.  Which buffer is the only thing it selects."""
         f = flat
+        g = f.grad if grad is None else grad
         lib, st = _rt(f.data)
         if self.scaler is not None:
             # GradScaler.step + .update on the device: max|g| of the (still scaled) gradients -- absmax's integer max orders inf and
             # nan above every finite magnitude -- decides inside the optimizer launch whether the update runs (on g / scale) or is
             # skipped with the scale backed off; nothing is read back.
-            lib.esmi_absmax_f32(_ptr(f.grad), f.grad.numel(), _ptr(self.absmax), st)
+            lib.esmi_absmax_f32(_ptr(g), g.numel(), _ptr(self.absmax), st)
         if self.max_norm is not None:
             # clip_grad_norm_ on the device: the buffer's sum of squares as per-workgroup partial sums; the optimizer launch adds them up,
             # divides the norm by the loss scale and folds the coefficient into the scale that every gradient is multiplied by
-            lib.esmi_train_grad_sumsq_f32(_ptr(f.grad), f.grad.numel(), _ptr(self._sumsq), st)
+            lib.esmi_train_grad_sumsq_f32(_ptr(g), g.numel(), _ptr(self._sumsq), st)
         if self.on_device:                          # (the launch counts: a skipped step does not advance the counter)
             absmax, scaler = (None, None) if self.scaler is None else (_ptr(self.absmax), _ptr(self.scaler))
-            args = (_ptr(f.data), _ptr(f.grad), _ptr(f.m), _ptr(f.v), f.data.numel(), _ptr(self.hyper), betas[0], betas[1], eps,
+            args = (_ptr(f.data), _ptr(g), _ptr(f.m), _ptr(f.v), f.data.numel(), _ptr(self.hyper), betas[0], betas[1], eps,
                     weight_decay, _ptr(self._count), absmax, scaler)
             if self.max_norm is not None:
                 lib.esmi_train_adamw_clip_f32(*args, _ptr(self._sumsq), self.max_norm, st)
@@ -775,7 +782,7 @@ class AdamWState:
                 lib.esmi_train_adamw_graph_f32(*args, st)
         else:
             self._count += 1
-            lib.esmi_train_adamw_f32(_ptr(f.data), _ptr(f.grad), _ptr(f.m), _ptr(f.v), f.data.numel(), lr, betas[0], betas[1], eps,
+            lib.esmi_train_adamw_f32(_ptr(f.data), _ptr(g), _ptr(f.m), _ptr(f.v), f.data.numel(), lr, betas[0], betas[1], eps,
                                      weight_decay, self._count, 1.0, st)
 
 
@@ -792,11 +799,27 @@ class TrainStep:
     tests/test_train_dispatch.py); the replay runs at the kernels' own pace (both are `bench.py`'s `train_step` leg).
 
     gradient_clip_val=c (Lightning's Trainer knob; None / 0: off) clips the gradients' 2-norm to c before the update, on the device and
-    inside a captured graph; `grad_norm` and `clip_coef` read the last step's norm and coefficient (inf: measure only)."""
+    inside a captured graph; `grad_norm` and `clip_coef` read the last step's norm and coefficient (inf: measure only).
+
+    accumulate_grad_batches=N (Lightning's Trainer knob; None / 1: off -- not one launch, buffer or attribute differs) makes `step` one
+    MICRO-batch: forward, loss and backward as ever, then one launch adds its gradients / N to `flat.acc`.  Every N-th call is the
+    window's boundary: the all-reduce (data-parallel: only there, Lightning's `no_sync` in between), the unscale, the clipping and the
+    AdamW launch run once on the sum, which is then zeroed.  At precision 16 the loss scale holds for the whole window and an inf / nan
+    of any micro-batch skips all of it.  `micro` counts the open window's micro-batches, `flush()` closes a short one (the last batches
+    of an epoch; not renormalised), `t` counts optimizer steps.  graph=True: the per-shape graph ends with the accumulate launch, and one
+    more graph, shared by all shapes, replays the boundary (one GPU; data-parallel it stays eager, as the optimizer launch does)."""
+
+    _accum_n, _micro, _boundary_graph = 1, 0, None      # class-level: an instance that does not accumulate has no attribute of its own
 
     def __init__(self, net, lr=1e-3, weight_decay=1e-6, betas=(0.9, 0.999), eps=1e-8, group=None, world_size=1, graph=False,
-                 precision=32, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, gradient_clip_val=None):
-        self.net, self.flat = net, FlatParams(net)
+                 precision=32, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, gradient_clip_val=None,
+                 accumulate_grad_batches=None):
+        n_acc = 1 if accumulate_grad_batches is None else accumulate_grad_batches
+        if isinstance(n_acc, bool) or not isinstance(n_acc, numbers.Integral) or n_acc < 1:
+            raise ValueError(f"accumulate_grad_batches must be None or an int >= 1, not {accumulate_grad_batches!r}")
+        if n_acc > 1:
+            self._accum_n, self._micro = int(n_acc), 0
+        self.net, self.flat = net, FlatParams(net, accumulate=n_acc > 1)
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         self.group, self.world = group, world_size
         self.epoch = 0                              # what `state_dict()` records; `fit` and `load_state_dict` set it
@@ -825,6 +848,7 @@ class TrainStep:
     growth_interval = property(lambda self: self._opt.growth_interval, lambda self, n: setattr(self._opt, "growth_interval", n))
     grad_norm = property(lambda self: self._opt.grad_norm)      # (both: AttributeError unless gradient_clip_val is set)
     clip_coef = property(lambda self: self._opt.clip_coef)
+    micro = property(lambda self: self._micro)     # micro-batches in the open accumulation window: a Python int, no device read (0 when off)
 
     # ---- checkpoint / resume (what Lightning's ModelCheckpoint keeps: weights, hyper-parameters, the optimizer's state_dict)
     def hyper_parameters(self):
@@ -860,7 +884,9 @@ class TrainStep:
         state_dict] (loads into `torch.optim.AdamW(net.parameters())`), `global_step`.  The reference's own
         `load_from_checkpoint` additionally expects `hifigan.*` weights (its module owns the vocoder, model.py:148) and a
         `preprocess_config` argument: pass `strict=False, preprocess_config=...` there, or attach the vocoder's weights under
-        `hifigan.` before saving."""
+        `hifigan.` before saving.  Inside an accumulation window (`micro != 0`) there is no consistent state to write: RuntimeError."""
+        if self._micro:
+            raise RuntimeError(f"{self._micro} micro-batch(es) of an accumulation window are pending: call flush() before state_dict()")
         ck = {"state_dict": {"phoneme2mel." + k: v.detach().clone() for k, v in self.net.state_dict().items()},
               "hyper_parameters": self.hyper_parameters(), "optimizer_states": [self.optimizer_state_dict()],
               "global_step": self.t, "epoch": int(self.epoch)}
@@ -874,7 +900,8 @@ class TrainStep:
         (torch's AdamW state_dict layout, as `state_dict()` writes it).  Only optimizer states written by `TrainStep.state_dict()` --
         i.e. over `net.parameters()` of the acoustic model alone -- load: the reference's own optimizer also owns the vocoder's
         parameters (model.py:148, 279-283), so its state has a different parameter list and is refused below.  `ckpt['epoch']`
-        (when present) is returned so that the caller can pass it to `fit(first_epoch=...)`."""
+        (when present) is returned so that the caller can pass it to `fit(first_epoch=...)`.  An open accumulation window is dropped
+        (the accumulator zeroed, `micro` = 0): a checkpoint is never taken inside one, and `accumulate_grad_batches` is not part of it."""
         sd = {k[len("phoneme2mel."):]: v for k, v in ckpt["state_dict"].items() if k.startswith("phoneme2mel.")}
         own = dict(self.net.state_dict())
         missing = [k for k in own if k not in sd]
@@ -906,6 +933,9 @@ class TrainStep:
         self.lr, self.wd, self.betas, self.eps = g.get("initial_lr", g["lr"]), g["weight_decay"], tuple(g["betas"]), g["eps"]
         self._opt.load_scaler_state_dict(ckpt.get("scaler"))
         self._packed.invalidate()
+        if self._accum_n > 1:
+            f.acc.zero_()
+            self._micro = 0
         self.epoch = int(ckpt.get("epoch", 0))
         return self.epoch
 
@@ -966,33 +996,27 @@ class TrainStep:
         self._optimize(lr)
         return losses
 
-    def step(self, x, y, lr=None):
-        """One training step.  graph=True: a hipGraph per batch SHAPE replays the step (inputs are copied into its static buffers) --
-        the whole step on one GPU; data-parallel, everything up to the gradient all-reduce (the collective and the optimizer launch
-        follow eagerly)."""
-        lr = self.lr if lr is None else lr
-        self._opt.set_lr(lr)
-        if not self.graph:
-            out = self._body(x, y, lr)
-            self._packed.invalidate()
-            return out
-        whole = self.world == 1                    # the collective stays outside a graph
+    def _replayed(self, x, y, head, tail=None):
+        """graph=True: `head(x, y)` -> losses through the hipGraph of this batch SHAPE (inputs are copied into its static buffers), then
+        `tail()` eagerly (what cannot be captured: a collective and what follows it).  The first batch of a shape runs both eagerly
+        on a side stream, which warms the allocator, and then captures `head`: the capture itself does not execute."""
         key = tuple((k, tuple(v.shape)) for k, v in sorted({**x, **{"y." + k: v for k, v in y.items()}}.items()) if torch.is_tensor(v))
         ent = self._graphs.get(key)
         if ent is None:
             sx = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in x.items()}
             sy = {k: v.clone() for k, v in y.items()}
-            side = torch.cuda.Stream(device=self.flat.data.device)          # one eager step on a side stream warms the allocator
+            side = torch.cuda.Stream(device=self.flat.data.device)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                out = self._body(sx, sy, lr)
+                out = head(sx, sy)
+                if tail is not None:
+                    tail()
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                static_out = self._body(sx, sy, lr) if whole else self._fwd_bwd(sx, sy)
+                static_out = head(sx, sy)
             self._graphs[key] = (g, sx, sy, static_out)
-            self._packed.invalidate()
-            return out.clone()                     # (the capture itself does not execute: this batch's step ran eagerly above)
+            return out.clone()
         g, sx, sy, static_out = ent
         for k, v in x.items():
             if torch.is_tensor(v):
@@ -1000,10 +1024,76 @@ class TrainStep:
         for k, v in y.items():
             sy[k].copy_(v)
         g.replay()
-        if not whole:
-            self._optimize(lr)
-        self._packed.invalidate()
+        if tail is not None:
+            tail()
         return static_out.clone()
+
+    def step(self, x, y, lr=None):
+        """One training step.  graph=True: a hipGraph per batch SHAPE replays the step (inputs are copied into its static buffers) --
+        the whole step on one GPU; data-parallel, everything up to the gradient all-reduce (the collective and the optimizer launch
+        follow eagerly).  With accumulate_grad_batches=N this is one micro-batch, and every N-th call ends with the window's boundary;
+        the losses returned are this micro-batch's own, undivided."""
+        lr = self.lr if lr is None else lr
+        self._opt.set_lr(lr)
+        if self._accum_n > 1:
+            out = self._micro_body(x, y) if not self.graph else self._replayed(x, y, self._micro_body)
+            self._micro += 1
+            if self._micro == self._accum_n:
+                self._boundary(lr)
+            return out
+        if not self.graph:
+            out = self._body(x, y, lr)
+        elif self.world == 1:
+            out = self._replayed(x, y, lambda sx, sy: self._body(sx, sy, lr))
+        else:                                      # the collective stays outside a graph
+            out = self._replayed(x, y, self._fwd_bwd, lambda: self._optimize(lr))
+        self._packed.invalidate()
+        return out
+
+    # ---- gradient accumulation (accumulate_grad_batches=N > 1)
+    def _micro_body(self, x, y):
+        """One micro-batch: everything up to the exchange, then the one launch that adds its gradients / N to the accumulator (the
+        backward overwrites `flat.grad`, so the sum cannot live there).  Capturable."""
+        losses = self._fwd_bwd(x, y)
+        f = self.flat
+        lib, st = _rt(f.data)
+        lib.esmi_train_grad_accumulate_f32(_ptr(f.acc), _ptr(f.grad), f.grad.numel(), 1.0 / self._accum_n, st)   # (1 / N rounds to fp32 once)
+        return losses
+
+    def _boundary_body(self, lr):
+        """The exchange of the accumulator (data-parallel), the optimizer launch on it, and its zeroing for the next window."""
+        f = self.flat
+        if self.world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(f.acc, op=dist.ReduceOp.SUM, group=self.group)
+            f.acc.div_(self.world)
+        self._opt.launch(f, lr, self.betas, self.eps, self.wd, grad=f.acc)
+        f.acc.zero_()                              # (also after a skipped window: its inf / nan must not reach the next one)
+
+    def _boundary(self, lr):
+        if self.graph and self.world == 1:         # one graph for every window, whatever shapes its micro-batches had
+            if self._boundary_graph is None:
+                self._boundary_body(lr)            # (this window's boundary runs eagerly: the capture itself does not execute)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    self._boundary_body(lr)
+                self._boundary_graph = g
+            else:
+                self._boundary_graph.replay()
+        else:
+            self._boundary_body(lr)
+        self._micro = 0
+        self._packed.invalidate()
+
+    def flush(self, lr=None):
+        """Close the open accumulation window now (Lightning's last-batch-of-the-epoch rule): the boundary on whatever has
+        accumulated, the 1 / N weights kept (a short window is not renormalised).  -> False, and nothing runs, when `micro == 0`."""
+        if not self._micro:
+            return False
+        lr = self.lr if lr is None else lr
+        self._opt.set_lr(lr)
+        self._boundary(lr)
+        return True
 
 
 def lr_at_epoch(epoch, base_lr=1e-3, warmup=50, total=5000, min_lr=0.0):
@@ -1026,7 +1116,9 @@ def fit(step, loader, epochs, device, base_lr=None, warmup=50, total=5000, first
     """The reference's training loop (train.py:66-76 -> Lightning `trainer.fit`) reduced to what it computes: for every epoch,
     the scheduled learning rate; for every batch of the datamodule, one `TrainStep.step`; at the end of the epoch the means of the
     five losses over the epoch's steps, averaged over the data-parallel ranks (model.py:227-242: `on_train_epoch_end` logs them
-    with `sync_dist=True`) -- one 5-float all-reduce per epoch on `step.group`.  Returns the per-epoch records."""
+    with `sync_dist=True`) -- one 5-float all-reduce per epoch on `step.group`.  Returns the per-epoch records.  A step that
+    accumulates (`accumulate_grad_batches=N`) is flushed after the last batch of every epoch, so no window stays open, and the means
+    are over its micro-batches: the reference logs per `training_step`."""
     base_lr = step.lr if base_lr is None else base_lr
     history = []
     for epoch in range(first_epoch, first_epoch + epochs):
@@ -1036,6 +1128,8 @@ def fit(step, loader, epochs, device, base_lr=None, warmup=50, total=5000, first
             losses = step.step(to_device(x, device), to_device(y, device), lr=lr)
             acc = losses.clone() if acc is None else acc + losses        # five scalars per step: bookkeeping, like self.log()
             n += 1
+        if step.micro:                  # an epoch never leaves an accumulation window open
+            step.flush(lr)
         mean = acc / max(n, 1) if acc is not None else None
         if mean is not None and step.world > 1:
             import torch.distributed as dist

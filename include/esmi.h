@@ -867,6 +867,13 @@ int esmi_train_grad_sumsq_f32(const float* g, int64_t n, double* partials /* ESM
 int esmi_train_adamw_clip_f32(float* p, const float* g, float* m, float* v, int64_t n, float* hyper_dev, double beta1, double beta2,
                               double eps, double weight_decay, int32_t* step_dev, const float* grad_absmax /* or NULL */,
                               float* scaler_state /* or NULL */, const double* sumsq_partials, double max_norm, esmi_stream_t stream);
+/* Gradient accumulation over micro-batches (Lightning's `accumulate_grad_batches`).  The operators' backward overwrites the flat gradient
+ * buffer, so the running sum lives in a buffer of its own and this call adds one micro-batch's gradients to it:
+ * acc[q] = fmaf(g[q], weight, acc[q]) for q < n, one rounding per element.  16 bytes per lane where BOTH pointers are 16-byte aligned,
+ * with a scalar tail; otherwise scalar throughout.  Nothing at or beyond index n is read or written; acc and g must not overlap
+ * (ESMI_ERR_ARG); n == 0 succeeds without a launch.  inf and nan in g arrive in acc: the optimizer calls above then see them in the
+ * accumulator as they would in a single gradient buffer (the precision-16 skip rule).  No atomics: the same inputs give the same bits. */
+int esmi_train_grad_accumulate_f32(float* acc, const float* g, int64_t n, float weight, esmi_stream_t stream);
 
 #ifdef __cplusplus
 }
