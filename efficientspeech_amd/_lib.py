@@ -212,6 +212,7 @@ EXPORTS = (
     "esmi_train_loss_f32", "esmi_train_adamw_f32", "esmi_train_adamw_graph_f32", "esmi_train_conv_bwd_workspace_bytes",
     "esmi_train_conv_bwd_f32", "esmi_train_reduce_flush_f32", "esmi_train_pack_weights_f32", "esmi_train_cat_f32",
     "esmi_train_grad_sumsq_f32", "esmi_train_adamw_clip_f32", "esmi_train_grad_accumulate_f32",
+    "esmi_train_ema_update_f32", "esmi_train_swap_f32",
 )
 
 
@@ -318,6 +319,8 @@ def bind(lib):
     lib.esmi_train_grad_sumsq_f32.argtypes = [fp, i64, fp, fp]
     lib.esmi_train_adamw_clip_f32.argtypes = [fp, fp, fp, fp, i64, fp, dbl, dbl, dbl, dbl, fp, fp, fp, fp, dbl, fp]
     lib.esmi_train_grad_accumulate_f32.argtypes = [fp, fp, i64, f, fp]
+    lib.esmi_train_ema_update_f32.argtypes = [fp, fp, i64, f, fp, fp]
+    lib.esmi_train_swap_f32.argtypes = [fp, fp, i64, fp]
     lib.esmi_pack_resblock_bytes.argtypes = [i, i]
     lib.esmi_pack_resblock_bytes.restype = sz
     lib.esmi_pack_resblock_f16.argtypes = [fp, fp, i, i, fp]

@@ -1,10 +1,11 @@
 // esmi C-ABI, translation unit "tu_train.hip": the training step's operators (train_ops.h and the train_*.h family headers it includes)
-// and the gradient accumulator (train_accum.h)
+// and the gradient accumulator (train_accum.h), the weight average and the buffer exchange (train_ema.h)
 // One of several translation units of libesmi.so (compiled in parallel by __graft_entry__.build(); the simulator build
 // tools/wavesim/build.sh compiles the same files with the host compiler).  Internal launchers are declared in launch.h.
 #include "launch.h"
 #include "train_ops.h"
 #include "train_accum.h"
+#include "train_ema.h"
 
 using namespace esmi;
 ESMI_TU_RANGE_SETTER(train)
@@ -582,15 +583,45 @@ int esmi_train_adamw_clip_f32(float* p, const float* g, float* m, float* v, int6
     return adamw_dev_update(p, g, m, v, n, hyper_dev, beta1, beta2, eps, S(stream));
 }
 
+// The flat-buffer pair launches (train_accum.h, train_ema.h) share one geometry: -> false when the ranges [a, a + n) and [b, b + n) overlap,
+// else n4 (whole 16-byte loads and stores: 0 unless BOTH pointers are 16-byte aligned; the rest is the scalar tail) and the grid (one
+// workgroup of 256 per 256 float4s, or per 256 scalars when n4 == 0, at most 1024).
+static bool flat_pair_geometry(const float* a, const float* b, int64_t n, long* n4, unsigned* grid) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b), bytes = (uintptr_t)n * sizeof(float);
+    if (a0 < b0 + bytes && b0 < a0 + bytes) return false;
+    *n4 = aligned16(a, b) ? (long)(n >> 2) : 0;
+    const long work = *n4 > 0 ? *n4 : (long)n, blocks = (work + 255) / 256;
+    *grid = (unsigned)(blocks > 1024 ? 1024 : blocks);
+    return true;
+}
+
 int esmi_train_grad_accumulate_f32(float* acc, const float* g, int64_t n, float weight, esmi_stream_t stream) {
     if (!acc || !g || n < 0) return ESMI_ERR_ARG;
     if (n == 0) return ESMI_OK;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(acc), g0 = reinterpret_cast<uintptr_t>(g), bytes = (uintptr_t)n * sizeof(float);
-    if (a0 < g0 + bytes && g0 < a0 + bytes) return ESMI_ERR_ARG;   // the two ranges overlap
-    const long n4 = aligned16(acc, g) ? (long)(n >> 2) : 0;        // whole 16-byte loads and stores; the rest is the scalar tail
-    const long work = n4 > 0 ? n4 : (long)n, blocks = (work + 255) / 256;
-    ESMI_LAUNCH(train_grad_accumulate_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, S(stream), acc, g, n4, (long)n,
-                weight);
+    long n4;
+    unsigned grid;
+    if (!flat_pair_geometry(acc, g, n, &n4, &grid)) return ESMI_ERR_ARG;
+    ESMI_LAUNCH(train_grad_accumulate_kernel, dim3(grid), dim3(256), 0, S(stream), acc, g, n4, (long)n, weight);
+    return launch_status();
+}
+
+int esmi_train_ema_update_f32(float* ema, const float* p, int64_t n, float weight, const float* hyper_dev, esmi_stream_t stream) {
+    if (!ema || !p || n < 0) return ESMI_ERR_ARG;
+    if (n == 0) return ESMI_OK;
+    long n4;
+    unsigned grid;
+    if (!flat_pair_geometry(ema, p, n, &n4, &grid)) return ESMI_ERR_ARG;
+    ESMI_LAUNCH(train_ema_update_kernel, dim3(grid), dim3(256), 0, S(stream), ema, p, n4, (long)n, weight, hyper_dev);
+    return launch_status();
+}
+
+int esmi_train_swap_f32(float* a, float* b, int64_t n, esmi_stream_t stream) {
+    if (!a || !b || n < 0) return ESMI_ERR_ARG;
+    if (n == 0) return ESMI_OK;
+    long n4;
+    unsigned grid;
+    if (!flat_pair_geometry(a, b, n, &n4, &grid)) return ESMI_ERR_ARG;
+    ESMI_LAUNCH(train_swap_kernel, dim3(grid), dim3(256), 0, S(stream), a, b, n4, (long)n);
     return launch_status();
 }
 

@@ -137,7 +137,8 @@ class EfficientSpeech(nn.Module):
         `precision=16` is the reference's `--precision 16` (binary16 GEMM operands, device-side loss scaler), `precision="bf16"` (or
         Lightning's "bf16-mixed") its bfloat16 twin, which needs no scaler and skips no step; `graph=True` captures either;
         `gradient_clip_val=c` is the Trainer's knob of that name (clip_grad_norm_ before the update, on the device), and so is
-        `accumulate_grad_batches=N` (`step` is then one micro-batch; every N-th call, or `flush()`, updates)."""
+        `accumulate_grad_batches=N` (`step` is then one micro-batch; every N-th call, or `flush()`, updates); `ema_decay=d` keeps an
+        exponential moving average of the weights on the device (`step.ema_weights()`, `step.ema_state_dict()`, `step.evaluate`)."""
         from . import train
         kw.setdefault("lr", self.hparams.get("lr", 1e-3))
         kw.setdefault("weight_decay", self.hparams.get("weight_decay", 1e-6))

@@ -612,9 +612,10 @@ _UNREACHED = ("encoder.pitch_decoder.norm2.", "encoder.energy_decoder.norm2.")
 class FlatParams:
     """All trainable parameters of a module as views into one flat fp32 buffer, their gradients into another.  accumulate=True adds
     `acc`, the running sum of a window of micro-batch gradients (`TrainStep(accumulate_grad_batches=N)`); without it there is no such
-    attribute."""
+    attribute.  ema=True adds `ema`, the exponential moving average of the weights (`TrainStep(ema_decay=d)`): a copy of `data` at
+    construction, pad elements 0 like `data`'s (the update launch averages 0 with 0); without it there is no such attribute either."""
 
-    def __init__(self, net, accumulate=False):
+    def __init__(self, net, accumulate=False, ema=False):
         named = [(k, p) for k, p in net.named_parameters() if p.requires_grad and not k.startswith(_UNREACHED)]
         self.names = [k for k, _ in named]
         self.params = [p for _, p in named]
@@ -633,6 +634,8 @@ class FlatParams:
             p.data = self.data[sl].view(p.shape)
             p.grad = self.grad[sl].view(p.shape)
             p._esmi_grad_view = p.grad              # operators' backward passes write here directly (see _grad_buffer)
+        if ema:
+            self.ema = self.data.clone()            # ema_0: the weights at construction
 
     def zero_grad(self):
         self.grad.zero_()
@@ -807,19 +810,39 @@ class TrainStep:
     AdamW launch run once on the sum, which is then zeroed.  At precision 16 the loss scale holds for the whole window and an inf / nan
     of any micro-batch skips all of it.  `micro` counts the open window's micro-batches, `flush()` closes a short one (the last batches
     of an epoch; not renormalised), `t` counts optimizer steps.  graph=True: the per-shape graph ends with the accumulate launch, and one
-    more graph, shared by all shapes, replays the boundary (one GPU; data-parallel it stays eager, as the optimizer launch does)."""
+    more graph, shared by all shapes, replays the boundary (one GPU; data-parallel it stays eager, as the optimizer launch does).
+
+    ema_decay=d (a float, 0 < d < 1; None: off -- not one launch, buffer or attribute differs) keeps an exponential moving average of the
+    weights in `flat.ema`: ema_0 is the weights at construction and one launch directly after every optimizer launch makes
+    ema_k = lerp(ema_{k-1}, p_k, 1 - d) -- torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn(d) whose first update_parameters
+    saw the initial weights, so there is no update counter, and there is NO decay warm-up.  The launch lies inside whatever is captured,
+    runs only on a window's boundary (and `flush()`) when accumulating, does not run for a skipped precision-16 step (it reads the
+    optimizer's skip flag on the device) and adds no collective: replicas hold identical weights, hence identical averages.
+    `ema_weights()` is a context manager inside which `net` holds the averaged weights (one in-place exchange of the two buffers each
+    way: parameters, packed copies and captured graphs keep their addresses); while it is open `step`, `flush`, `state_dict`,
+    `load_state_dict` and a nested `ema_weights()` raise RuntimeError.  `ema_state_dict()` exports the average as 'phoneme2mel.<key>'
+    weights; `state_dict()` stores it under "ema" and `load_state_dict` restores it (a checkpoint without one restarts the average from
+    the loaded weights).
+
+    evaluate(x, y, ema=None) is the teacher-forced forward and the loss under no_grad, eagerly: a validation loss that touches neither
+    the optimizer nor any buffer of the step (ema=None: on the averaged weights where the step has them)."""
 
     _accum_n, _micro, _boundary_graph = 1, 0, None      # class-level: an instance that does not accumulate has no attribute of its own
+    _ema_decay, _ema_weight, _ema_open = None, None, False      # ... and one that does not average has none of these
 
     def __init__(self, net, lr=1e-3, weight_decay=1e-6, betas=(0.9, 0.999), eps=1e-8, group=None, world_size=1, graph=False,
                  precision=32, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, gradient_clip_val=None,
-                 accumulate_grad_batches=None):
+                 accumulate_grad_batches=None, ema_decay=None):
+        if ema_decay is not None and (isinstance(ema_decay, bool) or not isinstance(ema_decay, float) or not 0.0 < ema_decay < 1.0):
+            raise ValueError(f"ema_decay must be None or a float with 0 < ema_decay < 1, not {ema_decay!r}")
         n_acc = 1 if accumulate_grad_batches is None else accumulate_grad_batches
         if isinstance(n_acc, bool) or not isinstance(n_acc, numbers.Integral) or n_acc < 1:
             raise ValueError(f"accumulate_grad_batches must be None or an int >= 1, not {accumulate_grad_batches!r}")
         if n_acc > 1:
             self._accum_n, self._micro = int(n_acc), 0
-        self.net, self.flat = net, FlatParams(net, accumulate=n_acc > 1)
+        if ema_decay is not None:                   # 1 - d in double, rounded to fp32 once by the call
+            self._ema_decay, self._ema_weight, self._ema_open = float(ema_decay), 1.0 - float(ema_decay), False
+        self.net, self.flat = net, FlatParams(net, accumulate=n_acc > 1, ema=ema_decay is not None)
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         self.group, self.world = group, world_size
         self.epoch = 0                              # what `state_dict()` records; `fit` and `load_state_dict` set it
@@ -885,6 +908,7 @@ class TrainStep:
         `load_from_checkpoint` additionally expects `hifigan.*` weights (its module owns the vocoder, model.py:148) and a
         `preprocess_config` argument: pass `strict=False, preprocess_config=...` there, or attach the vocoder's weights under
         `hifigan.` before saving.  Inside an accumulation window (`micro != 0`) there is no consistent state to write: RuntimeError."""
+        self._refuse_inside_ema_weights("state_dict()")
         if self._micro:
             raise RuntimeError(f"{self._micro} micro-batch(es) of an accumulation window are pending: call flush() before state_dict()")
         ck = {"state_dict": {"phoneme2mel." + k: v.detach().clone() for k, v in self.net.state_dict().items()},
@@ -893,6 +917,8 @@ class TrainStep:
         scaler = self._opt.scaler_state_dict()
         if scaler is not None:
             ck["scaler"] = scaler
+        if self._ema_decay is not None:
+            ck["ema"] = {"decay": self._ema_decay, "state_dict": self.ema_state_dict()}
         return ck
 
     def load_state_dict(self, ckpt):
@@ -901,7 +927,13 @@ class TrainStep:
         i.e. over `net.parameters()` of the acoustic model alone -- load: the reference's own optimizer also owns the vocoder's
         parameters (model.py:148, 279-283), so its state has a different parameter list and is refused below.  `ckpt['epoch']`
         (when present) is returned so that the caller can pass it to `fit(first_epoch=...)`.  An open accumulation window is dropped
-        (the accumulator zeroed, `micro` = 0): a checkpoint is never taken inside one, and `accumulate_grad_batches` is not part of it."""
+        (the accumulator zeroed, `micro` = 0): a checkpoint is never taken inside one, and `accumulate_grad_batches` is not part of it.
+        With `ema_decay`: the checkpoint's "ema" entry restores the average (a stored decay other than this step's: RuntimeError); without
+        an entry the average starts again from the loaded weights.  A step without `ema_decay` ignores the entry."""
+        self._refuse_inside_ema_weights("load_state_dict()")
+        ema = ckpt.get("ema") if self._ema_decay is not None else None
+        if ema is not None and float(ema["decay"]) != self._ema_decay:
+            raise RuntimeError(f"the checkpoint's average was kept with ema_decay {ema['decay']!r}, this step's is {self._ema_decay!r}")
         sd = {k[len("phoneme2mel."):]: v for k, v in ckpt["state_dict"].items() if k.startswith("phoneme2mel.")}
         own = dict(self.net.state_dict())
         missing = [k for k in own if k not in sd]
@@ -936,6 +968,11 @@ class TrainStep:
         if self._accum_n > 1:
             f.acc.zero_()
             self._micro = 0
+        if self._ema_decay is not None:
+            f.ema.copy_(f.data)
+            if ema is not None:
+                for k, sl in zip(f.names, f.slices):
+                    f.ema[sl].copy_(ema["state_dict"]["phoneme2mel." + k].reshape(-1))
         self.epoch = int(ckpt.get("epoch", 0))
         return self.epoch
 
@@ -990,6 +1027,8 @@ class TrainStep:
             dist.all_reduce(f.grad, op=dist.ReduceOp.SUM, group=self.group)
             f.grad.div_(self.world)                # DDP averages (train.py:66-70 runs Lightning's default DDP strategy)
         self._opt.launch(f, lr, self.betas, self.eps, self.wd)
+        if self._ema_decay is not None:
+            self._ema_update()
 
     def _body(self, x, y, lr):
         losses = self._fwd_bwd(x, y)
@@ -1033,6 +1072,7 @@ class TrainStep:
         the whole step on one GPU; data-parallel, everything up to the gradient all-reduce (the collective and the optimizer launch
         follow eagerly).  With accumulate_grad_batches=N this is one micro-batch, and every N-th call ends with the window's boundary;
         the losses returned are this micro-batch's own, undivided."""
+        self._refuse_inside_ema_weights("step()")
         lr = self.lr if lr is None else lr
         self._opt.set_lr(lr)
         if self._accum_n > 1:
@@ -1068,6 +1108,8 @@ class TrainStep:
             dist.all_reduce(f.acc, op=dist.ReduceOp.SUM, group=self.group)
             f.acc.div_(self.world)
         self._opt.launch(f, lr, self.betas, self.eps, self.wd, grad=f.acc)
+        if self._ema_decay is not None:
+            self._ema_update()
         f.acc.zero_()                              # (also after a skipped window: its inf / nan must not reach the next one)
 
     def _boundary(self, lr):
@@ -1088,12 +1130,86 @@ class TrainStep:
     def flush(self, lr=None):
         """Close the open accumulation window now (Lightning's last-batch-of-the-epoch rule): the boundary on whatever has
         accumulated, the 1 / N weights kept (a short window is not renormalised).  -> False, and nothing runs, when `micro == 0`."""
+        self._refuse_inside_ema_weights("flush()")
         if not self._micro:
             return False
         lr = self.lr if lr is None else lr
         self._opt.set_lr(lr)
         self._boundary(lr)
         return True
+
+    # ---- the weights' exponential moving average (ema_decay=d) and the validation loss
+    def _ema_update(self):
+        """ema = lerp(ema, p, 1 - d), one launch directly behind the optimizer's (capturable).  Where the optimizer keeps its scalars on
+        the device the launch reads the skip flag there: a skipped precision-16 step does not advance the average."""
+        f = self.flat
+        lib, st = _rt(f.data)
+        lib.esmi_train_ema_update_f32(_ptr(f.ema), _ptr(f.data), f.data.numel(), self._ema_weight,
+                                      _ptr(self._opt.hyper) if self._opt.on_device else None, st)
+
+    def _need_ema(self, what):
+        if self._ema_decay is None:
+            raise AttributeError(f"no {what}: this step keeps no average of the weights (ema_decay is None)")
+        return self.flat.ema
+
+    def _refuse_inside_ema_weights(self, what):
+        if self._ema_open:
+            raise RuntimeError(f"{what} inside ema_weights(): the weights and their average are exchanged; leave the context first")
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context `net` (its inference path, `evaluate`) runs on the averaged weights: one launch exchanges the contents of
+        `flat.data` and `flat.ema` on entry and one exchanges them back on exit, after which both are bitwise what they were."""
+        self._need_ema("ema_weights()")
+        self._refuse_inside_ema_weights("ema_weights()")
+        self._ema_exchange()
+        self._ema_open = True
+        try:
+            yield self
+        finally:
+            self._ema_open = False
+            self._ema_exchange()
+
+    def _ema_exchange(self):
+        f = self.flat
+        lib, st = _rt(f.data)
+        lib.esmi_train_swap_f32(_ptr(f.data), _ptr(f.ema), f.data.numel(), st)
+        self._packed.invalidate()
+
+    def ema_state_dict(self):
+        """The averaged weights as {'phoneme2mel.<key>': tensor}, cloned: with `hyper_parameters()` what `EfficientSpeech.load_from_checkpoint`
+        needs to synthesize from the average.  Parameters outside the flat buffer (the bins, the two unreached LayerNorms) and buffers
+        are `net`'s own."""
+        f = self.flat
+        avg = f.data if self._ema_open else self._need_ema("ema_state_dict()")     # (inside ema_weights() the two are exchanged)
+        sd = {"phoneme2mel." + k: v.detach().clone() for k, v in self.net.state_dict().items()}
+        for k, p, sl in zip(f.names, f.params, f.slices):
+            sd["phoneme2mel." + k] = avg[sl].view(p.shape).clone()
+        return sd
+
+    def evaluate(self, x, y, ema=None):
+        """The loss 5-vector (`step`'s layout) of the teacher-forced forward under no_grad: a validation loss.  ema=None: on the averaged
+        weights if this step keeps them; True: on them (AttributeError without `ema_decay`); False: on the weights as they are.  Runs
+        eagerly (also when graph=True), in a step context of its own -- the step's precision, no loss seed, the pack launch first, so it
+        reads the weights as they are now -- and changes nothing: weights, average, gradients, moments, accumulator, counters, scaler
+        and hyper block stay bitwise what they were, also inside an open accumulation window."""
+        if ema is None:
+            ema = self._ema_decay is not None
+        if ema:
+            self._need_ema("evaluate(ema=True)")
+        if ema and not self._ema_open:              # (inside ema_weights() the weights already are the average)
+            with self.ema_weights():
+                return self._forward_loss(x, y)
+        return self._forward_loss(x, y)
+
+    def _forward_loss(self, x, y):
+        lib0, st0 = _rt(self.flat.data)
+        with torch.no_grad(), _step_context(self.precision, False) as now:
+            if USE_MATRIX_PIPE and self._pack_n:
+                lib0.esmi_train_pack_weights_f32(self._pack_descs, self._pack_w, self._pack_n, st0)
+                now.packed_valid = True
+            parts, total = training_loss(self.net, x, y)
+        return loss_vector(parts, total)
 
 
 def lr_at_epoch(epoch, base_lr=1e-3, warmup=50, total=5000, min_lr=0.0):
@@ -1112,13 +1228,30 @@ def to_device(batch, device):
     return {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
 
 
-def fit(step, loader, epochs, device, base_lr=None, warmup=50, total=5000, first_epoch=0, log=None):
+def _epoch_mean(step, acc, n):
+    """The mean of `n` summed loss vectors, averaged over the data-parallel ranks (one 5-float all-reduce on `step.group`)."""
+    mean = acc / max(n, 1) if acc is not None else None
+    if mean is not None and step.world > 1:
+        import torch.distributed as dist
+        dist.all_reduce(mean, op=dist.ReduceOp.SUM, group=step.group)
+        mean = mean / step.world
+    return mean
+
+
+def fit(step, loader, epochs, device, base_lr=None, warmup=50, total=5000, first_epoch=0, log=None, val_loader=None,
+        check_val_every_n_epoch=10):
     """The reference's training loop (train.py:66-76 -> Lightning `trainer.fit`) reduced to what it computes: for every epoch,
     the scheduled learning rate; for every batch of the datamodule, one `TrainStep.step`; at the end of the epoch the means of the
     five losses over the epoch's steps, averaged over the data-parallel ranks (model.py:227-242: `on_train_epoch_end` logs them
     with `sync_dist=True`) -- one 5-float all-reduce per epoch on `step.group`.  Returns the per-epoch records.  A step that
     accumulates (`accumulate_grad_batches=N`) is flushed after the last batch of every epoch, so no window stays open, and the means
-    are over its micro-batches: the reference logs per `training_step`."""
+    are over its micro-batches: the reference logs per `training_step`.  With a `val_loader`, validation runs after every epoch e with
+    (e + 1) % check_val_every_n_epoch == 0 (Lightning's rule; the reference's Trainer sets 10, train.py:66-70), after the epoch's flush:
+    the mean of `step.evaluate` over its batches (on the averaged weights where the step keeps them), averaged over the ranks as the
+    training means are, is that epoch's record["val_losses"].  Every other record has no such key."""
+    if val_loader is not None and (isinstance(check_val_every_n_epoch, bool) or not isinstance(check_val_every_n_epoch, numbers.Integral)
+                                   or check_val_every_n_epoch < 1):
+        raise ValueError(f"check_val_every_n_epoch must be an int >= 1, not {check_val_every_n_epoch!r}")
     base_lr = step.lr if base_lr is None else base_lr
     history = []
     for epoch in range(first_epoch, first_epoch + epochs):
@@ -1130,12 +1263,16 @@ def fit(step, loader, epochs, device, base_lr=None, warmup=50, total=5000, first
             n += 1
         if step.micro:                  # an epoch never leaves an accumulation window open
             step.flush(lr)
-        mean = acc / max(n, 1) if acc is not None else None
-        if mean is not None and step.world > 1:
-            import torch.distributed as dist
-            dist.all_reduce(mean, op=dist.ReduceOp.SUM, group=step.group)
-            mean = mean / step.world
+        mean = _epoch_mean(step, acc, n)
         history.append({"epoch": epoch, "lr": lr, "losses": mean.cpu().tolist() if mean is not None else None})
+        if val_loader is not None and (epoch + 1) % check_val_every_n_epoch == 0:
+            acc, n = None, 0
+            for x, y in val_loader:
+                losses = step.evaluate(to_device(x, device), to_device(y, device))
+                acc = losses.clone() if acc is None else acc + losses
+                n += 1
+            mean = _epoch_mean(step, acc, n)
+            history[-1]["val_losses"] = mean.cpu().tolist() if mean is not None else None
         step.epoch = epoch + 1          # what `state_dict()` records: the epoch a resumed `fit(first_epoch=...)` starts with
         if log:
             log(history[-1])

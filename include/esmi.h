@@ -874,6 +874,19 @@ int esmi_train_adamw_clip_f32(float* p, const float* g, float* m, float* v, int6
  * (ESMI_ERR_ARG); n == 0 succeeds without a launch.  inf and nan in g arrive in acc: the optimizer calls above then see them in the
  * accumulator as they would in a single gradient buffer (the precision-16 skip rule).  No atomics: the same inputs give the same bits. */
 int esmi_train_grad_accumulate_f32(float* acc, const float* g, int64_t n, float weight, esmi_stream_t stream);
+/* Exponential moving average of the weights (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn(decay)), one launch over the flat
+ * parameter buffer directly after the optimizer's: ema[q] = fmaf(weight, p[q] - ema[q], ema[q]) for q < n with weight = 1 - decay (formed in
+ * double by the caller, rounded to fp32 once) -- torch.lerp(ema, p, weight)'s form for weight < 0.5.  Geometry, alignment rule, bounds
+ * and determinism as esmi_train_grad_accumulate_f32; ema and p must not overlap (ESMI_ERR_ARG); n == 0 succeeds without a launch.
+ * hyper_dev != NULL is the hyper block of the optimizer call above: where its [ESMI_HYPER_SKIP] slot is non-zero (a precision-16 step that
+ * overflowed) the kernel returns without touching ema -- a skipped step advances the average as little as the step count.  Weights travel as
+ * they are: an inf or nan in p arrives in ema. */
+int esmi_train_ema_update_f32(float* ema, const float* p, int64_t n, float weight, const float* hyper_dev /* or NULL */, esmi_stream_t stream);
+/* Exchange the contents of two buffers in one launch, without a temporary: a[q] <-> b[q] for q < n (how the model is run on the averaged
+ * weights: parameters, packed copies and captured graphs hold the flat buffer's address, so contents move and pointers stay).  Loads and
+ * stores only: every bit travels, two calls restore both buffers exactly.  Same geometry and alignment rule; a and b must not overlap
+ * (ESMI_ERR_ARG); n == 0 succeeds without a launch. */
+int esmi_train_swap_f32(float* a, float* b, int64_t n, esmi_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Development: time the training step (efficientspeech_amd.train.TrainStep) on a synthetic teacher-forced batch.
 python tools/bench_train.py [--config tiny] [--batch 32] [--phonemes 128] [--dur 6] [--iters 5] [--accumulate N]
---accumulate N times whole windows of N micro-batches (TrainStep(accumulate_grad_batches=N)) and prints ms per micro-batch and per window."""
+--accumulate N times whole windows of N micro-batches (TrainStep(accumulate_grad_batches=N)) and prints ms per micro-batch and per window.
+--ema-decay D compares the REPLAYED step (graph=True) without and with the weight average (TrainStep(ema_decay=D)) in alternating legs off / on /
+off, at the tool's default shape (32 x 128 phonemes) and at 128 x 100: per shape the legs' ms per step, the ratio on / mean(off) and the spread of
+the two off legs (what the ratio has to be read against).  --timeline DB adds the update launch's own duration from a rocprofv3 result database
+(rocprofv3 --kernel-trace -d DIR -o NAME -- python tools/bench_train.py --ema-decay D ...: DIR/NAME_results.db; tools/train_timeline.py lists
+the whole step from the same file); with --timeline alone nothing runs on the GPU."""
 import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -10,15 +15,65 @@ from efficientspeech_amd import CONFIGS, build_phoneme2mel, train
 from efficientspeech_amd.synth import synth_state_dict
 
 
+def _fresh_net(cfg):
+    net = build_phoneme2mel(cfg)
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in synth_state_dict(cfg, 1234).items()})
+    return net.cuda().train()
+
+
+def _ms_per_step(step, x, y, iters):
+    for _ in range(3):                      # (the third call replays the graph)
+        step.step(x, y)
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    for _ in range(iters):
+        step.step(x, y)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters * 1e3
+
+
+def ema_legs(a):
+    """Alternating legs off / on / off of the replayed step: three steps on three fresh nets, each warmed up before any leg is timed, then
+    the three legs one after the other."""
+    cfg = CONFIGS[a.config]
+    for B, T in ((32, 128), (128, 100)):
+        x, y = train.synthetic_batch(B, T, a.dur, "cuda")
+        kw = dict(graph=True, precision=a.precision, init_scale=2048.0, gradient_clip_val=a.clip_grad_norm)
+        steps = [train.TrainStep(_fresh_net(cfg), **kw, ema_decay=d) for d in (None, a.ema_decay, None)]
+        for s in steps:
+            _ms_per_step(s, x, y, 3)
+        off1, on, off2 = (_ms_per_step(s, x, y, a.iters) for s in steps)
+        off = 0.5 * (off1 + off2)
+        print(f"replayed step {a.config} precision {a.precision} B={B} T={T}: off {off1:.4f} ms  on (ema_decay={a.ema_decay}) {on:.4f} ms  off {off2:.4f} ms  "
+              f"on / off {on / off:.4f}  spread of the off legs {abs(off1 - off2) / off:.4f}  ({a.iters} steps per leg, "
+              f"{steps[1].flat.data.numel()} floats in the flat buffer)")
+
+
+def ema_launch_from_timeline(path):
+    import sqlite3
+    db = sqlite3.connect(path)
+    cols = [r[1] for r in db.execute("pragma table_info(kernels)")]
+    rows = [dict(zip(cols, r)) for r in db.execute("select * from kernels order by start")]
+    us = sorted((r["end"] - r["start"]) / 1e3 for r in rows if "train_ema_update_kernel" in r["name"])
+    if not us:
+        raise SystemExit(f"{path}: no train_ema_update_kernel launch in the trace")
+    print(f"train_ema_update_kernel in {os.path.basename(path)}: {len(us)} launches, median {us[len(us) // 2]:.2f} us, min {us[0]:.2f} us, max {us[-1]:.2f} us")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="tiny"); ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--phonemes", type=int, default=128); ap.add_argument("--dur", type=int, default=6); ap.add_argument("--iters", type=int, default=5); ap.add_argument("--graph", action="store_true"); ap.add_argument("--precision", default="32", choices=["32", "16", "bf16"]); ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="V", help="TrainStep(gradient_clip_val=V): clip the gradients' 2-norm to V on the device (inf: measure only)"); ap.add_argument("--accumulate", type=int, default=None, metavar="N", help="TrainStep(accumulate_grad_batches=N): --iters counts windows of N micro-batches"); ap.add_argument("--torch-mirror", action="store_true", help="time plain PyTorch-ROCm ops (tests/torch_mirror.py + torch.optim.AdamW) on the same batch instead")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="D", help="TrainStep(ema_decay=D): legs off / on / off of the replayed step at 32 x 128 and 128 x 100 (--batch / --phonemes / --graph / --accumulate are not read)")
+    ap.add_argument("--timeline", default=None, metavar="DB", help="a rocprofv3 --kernel-trace result database: print train_ema_update_kernel's duration from it")
     a = ap.parse_args()
+    if a.timeline:
+        ema_launch_from_timeline(a.timeline)
+        sys.exit(0)
+    if a.ema_decay is not None:
+        ema_legs(a)
+        sys.exit(0)
     cfg = CONFIGS[a.config]
-    net = build_phoneme2mel(cfg)
-    net.load_state_dict({k: torch.from_numpy(v) for k, v in synth_state_dict(cfg, 1234).items()})
-    net = net.cuda().train()
+    net = _fresh_net(cfg)
     x, y = train.synthetic_batch(a.batch, a.phonemes, a.dur, "cuda")
     if a.torch_mirror:
         from tests import torch_mirror as M
