@@ -34,7 +34,7 @@ def _new(shape, like, dtype=torch.float32):
 
 @dataclasses.dataclass
 class _Step:
-    """What a running `TrainStep` tells the operators; `TrainStep._fwd_bwd` turns the last three on as the step gets there."""
+    """What a running `TrainStep` tells the operators; `TrainStep` turns the last three on as the step gets there (`_operators_in_step`, `_fwd_bwd`)."""
     precision: object               # 16: the reference's `--precision 16` -- the dense GEMMs (forward, data gradient) round their operands to
     #                                 binary16 (one MFMA product instead of three); "bf16": `--precision bf16-mixed`, the same in bfloat16
     loss_seed: object               # what the backward is seeded with: False = 1, else the device scalar (the loss scale) -- the loss kernel
@@ -672,6 +672,7 @@ class AdamWState:
             raise ValueError(f"gradient_clip_val must be None or >= 0, not {gradient_clip_val!r}")
         self.on_device = bool(graph) or precision == 16 or clip > 0.0
         self.scaler = self.absmax = self.hyper = None
+        self.lr = lr                                # what `set_lr` recorded last: the host-scalar launch's argument
         self._count = 0                             # the step counter: this int, or (on_device) one int32 in device memory
         if self.on_device:
             self._count = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -756,11 +757,13 @@ class AdamWState:
                 self.scaler[slot] = float(sd[key])
 
     def set_lr(self, lr):
-        """This step's learning rate, for the launch that reads it from device memory (outside a captured graph: before the replay)."""
+        """The learning rate of the launches that follow: kept here for the launch that takes it as an argument, and written to the hyper
+        block for the one that reads it from device memory (outside a captured graph: before the replay)."""
+        self.lr = lr
         if self.on_device:
             self._lr.fill_(lr)
 
-    def launch(self, flat, lr, betas, eps, weight_decay, grad=None):
+    def launch(self, flat, betas, eps, weight_decay, grad=None):
         """One AdamW update of `flat` by its (already exchanged) gradients: `grad`, the buffer all three launches read -- None: `flat.grad`;
         a `TrainStep` that accumulates passes `flat.acc` on a window's boundary.  Which buffer is the only thing it selects."""
         f = flat
@@ -785,8 +788,62 @@ class AdamWState:
                 lib.esmi_train_adamw_graph_f32(*args, st)
         else:
             self._count += 1
-            lib.esmi_train_adamw_f32(_ptr(f.data), _ptr(g), _ptr(f.m), _ptr(f.v), f.data.numel(), lr, betas[0], betas[1], eps,
+            lib.esmi_train_adamw_f32(_ptr(f.data), _ptr(g), _ptr(f.m), _ptr(f.v), f.data.numel(), self.lr, betas[0], betas[1], eps,
                                      weight_decay, self._count, 1.0, st)
+
+
+class WeightAverage:
+    """The exponential moving average of the weights that `TrainStep(ema_decay=d)` keeps in `FlatParams.ema`: its decay, its two launches
+    and its entry in a checkpoint.  `open` is set while `TrainStep.ema_weights()` has the weights and the average exchanged."""
+
+    def __init__(self, flat, decay):
+        self.flat, self.decay, self.open = flat, float(decay), False
+        self.weight = 1.0 - self.decay              # 1 - d in double, rounded to fp32 once by the call
+
+    def update(self, opt):
+        """ema = lerp(ema, p, 1 - d), one launch directly behind the optimizer's (capturable).  Where the optimizer keeps its scalars on
+        the device the launch reads the skip flag there: a skipped precision-16 step does not advance the average."""
+        f = self.flat
+        lib, st = _rt(f.data)
+        lib.esmi_train_ema_update_f32(_ptr(f.ema), _ptr(f.data), f.data.numel(), self.weight, _ptr(opt.hyper) if opt.on_device else None, st)
+
+    def exchange(self, packed):
+        """The contents of `flat.data` and `flat.ema` change places, in one launch and in place; `packed` (the inference path's copies of
+        the weights that just left) is invalidated."""
+        f = self.flat
+        lib, st = _rt(f.data)
+        lib.esmi_train_swap_f32(_ptr(f.data), _ptr(f.ema), f.data.numel(), st)
+        packed.invalidate()
+
+    def weights(self, net):
+        """The averaged weights as {'phoneme2mel.<key>': tensor}, cloned; what the flat buffer does not own is `net`'s."""
+        f = self.flat
+        avg = f.data if self.open else f.ema        # (inside ema_weights() the two are exchanged)
+        sd = {"phoneme2mel." + k: v.detach().clone() for k, v in net.state_dict().items()}
+        for k, p, sl in zip(f.names, f.params, f.slices):
+            sd["phoneme2mel." + k] = avg[sl].view(p.shape).clone()
+        return sd
+
+    def entry(self, net):
+        """The checkpoint's "ema" entry."""
+        return {"decay": self.decay, "state_dict": self.weights(net)}
+
+    def accept(self, entry):
+        """-> `entry` (a checkpoint's "ema" entry, or None) once it is known to load: one kept with another decay is refused."""
+        if entry is not None and float(entry["decay"]) != self.decay:
+            raise RuntimeError(f"the checkpoint's average was kept with ema_decay {entry['decay']!r}, this step's is {self.decay!r}")
+        return entry
+
+    def load(self, entry):
+        """Restart the average from the weights as they are, then take the entry's where there is one."""
+        f = self.flat
+        f.ema.copy_(f.data)
+        if entry is not None:
+            for k, sl in zip(f.names, f.slices):
+                f.ema[sl].copy_(entry["state_dict"]["phoneme2mel." + k].reshape(-1))
+
+
+_EAGER, _SHAPE_GRAPH, _SHARED_GRAPH = "eager", "in the per-shape graph", "in the shared boundary graph"     # `TrainStep._boundary_in`
 
 
 class TrainStep:
@@ -810,7 +867,8 @@ class TrainStep:
     AdamW launch run once on the sum, which is then zeroed.  At precision 16 the loss scale holds for the whole window and an inf / nan
     of any micro-batch skips all of it.  `micro` counts the open window's micro-batches, `flush()` closes a short one (the last batches
     of an epoch; not renormalised), `t` counts optimizer steps.  graph=True: the per-shape graph ends with the accumulate launch, and one
-    more graph, shared by all shapes, replays the boundary (one GPU; data-parallel it stays eager, as the optimizer launch does).
+    more graph, shared by all shapes, replays the boundary (one GPU; data-parallel it stays eager, as the optimizer launch does).  Without
+    the knob the schedule is the same with a window of one: the table in `__init__` says where the boundary runs in every case.
 
     ema_decay=d (a float, 0 < d < 1; None: off -- not one launch, buffer or attribute differs) keeps an exponential moving average of the
     weights in `flat.ema`: ema_0 is the weights at construction and one launch directly after every optimizer launch makes
@@ -827,9 +885,6 @@ class TrainStep:
     evaluate(x, y, ema=None) is the teacher-forced forward and the loss under no_grad, eagerly: a validation loss that touches neither
     the optimizer nor any buffer of the step (ema=None: on the averaged weights where the step has them)."""
 
-    _accum_n, _micro, _boundary_graph = 1, 0, None      # class-level: an instance that does not accumulate has no attribute of its own
-    _ema_decay, _ema_weight, _ema_open = None, None, False      # ... and one that does not average has none of these
-
     def __init__(self, net, lr=1e-3, weight_decay=1e-6, betas=(0.9, 0.999), eps=1e-8, group=None, world_size=1, graph=False,
                  precision=32, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, gradient_clip_val=None,
                  accumulate_grad_batches=None, ema_decay=None):
@@ -838,13 +893,22 @@ class TrainStep:
         n_acc = 1 if accumulate_grad_batches is None else accumulate_grad_batches
         if isinstance(n_acc, bool) or not isinstance(n_acc, numbers.Integral) or n_acc < 1:
             raise ValueError(f"accumulate_grad_batches must be None or an int >= 1, not {accumulate_grad_batches!r}")
-        if n_acc > 1:
-            self._accum_n, self._micro = int(n_acc), 0
-        if ema_decay is not None:                   # 1 - d in double, rounded to fp32 once by the call
-            self._ema_decay, self._ema_weight, self._ema_open = float(ema_decay), 1.0 - float(ema_decay), False
         self.net, self.flat = net, FlatParams(net, accumulate=n_acc > 1, ema=ema_decay is not None)
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         self.group, self.world = group, world_size
+        # The schedule: a call of `step` is one micro-batch, and a boundary when it fills the window of N (None / 1: a window of one).
+        self._window, self._micro = int(n_acc), 0   # N, and the micro-batches in the open window
+        self._avg = WeightAverage(self.flat, ema_decay) if ema_decay is not None else None
+        # Where the boundary runs:
+        #   graph   world   N     the per-shape graph holds        the boundary
+        #   off     any     any   --                               eager
+        #   on      1       1     micro-batch + boundary           inside that graph
+        #   on      1       > 1   micro-batch (accumulate last)    the one shared graph `_boundary_graph` (the first boundary runs eagerly,
+        #                                                          then is captured: a capture does not execute)
+        #   on      > 1     any   micro-batch                      eager, behind the all-reduce: a collective stays outside a graph
+        #                                                          (N = 1: as the tail of the shape's replay, see `_replayed`)
+        self._boundary_in = _EAGER if not graph or world_size > 1 else (_SHAPE_GRAPH if n_acc == 1 else _SHARED_GRAPH)
+        self._boundary_graph = None                 # (stays None unless the third row applies)
         self.epoch = 0                              # what `state_dict()` records; `fit` and `load_state_dict` set it
         # precision 16 = what Lightning's `precision=16` does around the reference's step (train.py:66-70): autocast-class GEMMs
         # (binary16 operands, fp32 accumulate, fp32 master weights) + torch.amp.GradScaler's dynamic loss scaling: the backward
@@ -917,8 +981,8 @@ class TrainStep:
         scaler = self._opt.scaler_state_dict()
         if scaler is not None:
             ck["scaler"] = scaler
-        if self._ema_decay is not None:
-            ck["ema"] = {"decay": self._ema_decay, "state_dict": self.ema_state_dict()}
+        if self._avg is not None:
+            ck["ema"] = self._avg.entry(self.net)
         return ck
 
     def load_state_dict(self, ckpt):
@@ -931,9 +995,7 @@ class TrainStep:
         With `ema_decay`: the checkpoint's "ema" entry restores the average (a stored decay other than this step's: RuntimeError); without
         an entry the average starts again from the loaded weights.  A step without `ema_decay` ignores the entry."""
         self._refuse_inside_ema_weights("load_state_dict()")
-        ema = ckpt.get("ema") if self._ema_decay is not None else None
-        if ema is not None and float(ema["decay"]) != self._ema_decay:
-            raise RuntimeError(f"the checkpoint's average was kept with ema_decay {ema['decay']!r}, this step's is {self._ema_decay!r}")
+        ema = self._avg.accept(ckpt.get("ema")) if self._avg is not None else None      # (refused before anything is overwritten)
         sd = {k[len("phoneme2mel."):]: v for k, v in ckpt["state_dict"].items() if k.startswith("phoneme2mel.")}
         own = dict(self.net.state_dict())
         missing = [k for k in own if k not in sd]
@@ -965,14 +1027,11 @@ class TrainStep:
         self.lr, self.wd, self.betas, self.eps = g.get("initial_lr", g["lr"]), g["weight_decay"], tuple(g["betas"]), g["eps"]
         self._opt.load_scaler_state_dict(ckpt.get("scaler"))
         self._packed.invalidate()
-        if self._accum_n > 1:
+        if self._window > 1:
             f.acc.zero_()
             self._micro = 0
-        if self._ema_decay is not None:
-            f.ema.copy_(f.data)
-            if ema is not None:
-                for k, sl in zip(f.names, f.slices):
-                    f.ema[sl].copy_(ema["state_dict"]["phoneme2mel." + k].reshape(-1))
+        if self._avg is not None:
+            self._avg.load(ema)
         self.epoch = int(ckpt.get("epoch", 0))
         return self.epoch
 
@@ -998,6 +1057,17 @@ class TrainStep:
             self._pack_descs[j] = d
             self._pack_w[j] = w.data_ptr()
 
+    @contextlib.contextmanager
+    def _operators_in_step(self, loss_seed):
+        """The operators run inside a step: its context (precision, what the backward is seeded with) and, first of all, the ONE pack
+        launch whose copies of the current weights every dense operator then reads."""
+        with _step_context(self.precision, loss_seed) as now:
+            if USE_MATRIX_PIPE and self._pack_n:
+                lib, st = _rt(self.flat.data)
+                lib.esmi_train_pack_weights_f32(self._pack_descs, self._pack_w, self._pack_n, st)
+                now.packed_valid = True
+            yield now
+
     def _fwd_bwd(self, x, y):
         """Forward, loss, backward, and the one launch that finishes every parameter gradient: everything up to the exchange.
         Capturable as a hipGraph (no host reads, no collectives)."""
@@ -1006,10 +1076,7 @@ class TrainStep:
         rq = (_lib.ReduceQueue(), [])
         lib0, st0 = _rt(f.data)
         seed = self._opt.loss_seed                 # one device float: the loss scale, or the constant 1 where there is no scaler
-        with _step_context(self.precision, seed if self._opt.scaler is not None else False) as now:
-            if USE_MATRIX_PIPE and self._pack_n:   # every operator of this step reads these copies of the current weights
-                lib0.esmi_train_pack_weights_f32(self._pack_descs, self._pack_w, self._pack_n, st0)
-                now.packed_valid = True
+        with self._operators_in_step(seed if self._opt.scaler is not None else False) as now:
             parts, total = training_loss(self.net, x, y)
             # one backward on a zeroed buffer: operators write parameter gradients in place and queue their reductions' second stages
             now.direct_grads, now.reduce_queue = True, rq
@@ -1018,27 +1085,44 @@ class TrainStep:
         rq[1].clear()
         return loss_vector(parts, total)
 
-    def _optimize(self, lr):
-        """The exchange (one all-reduce of the flat gradient buffer when data-parallel) and the optimizer launch, which reads step
-        count / learning rate (/ the loss scaler's state) from device memory under graph replay, precision 16 and gradient clipping."""
-        f = self.flat
-        if self.world > 1:
-            import torch.distributed as dist
-            dist.all_reduce(f.grad, op=dist.ReduceOp.SUM, group=self.group)
-            f.grad.div_(self.world)                # DDP averages (train.py:66-70 runs Lightning's default DDP strategy)
-        self._opt.launch(f, lr, self.betas, self.eps, self.wd)
-        if self._ema_decay is not None:
-            self._ema_update()
-
-    def _body(self, x, y, lr):
+    # ---- the schedule: micro-batch, boundary, and where each runs (the table in __init__)
+    def _micro_batch(self, x, y):
+        """One micro-batch: everything up to the exchange and, in a window of N > 1, the one launch that adds its gradients / N to the
+        accumulator (the backward overwrites `flat.grad`, so the sum cannot live there).  Capturable."""
         losses = self._fwd_bwd(x, y)
-        self._optimize(lr)
+        if self._window > 1:
+            f = self.flat
+            lib, st = _rt(f.data)
+            lib.esmi_train_grad_accumulate_f32(_ptr(f.acc), _ptr(f.grad), f.grad.numel(), 1.0 / self._window, st)   # (1 / N rounds to fp32 once)
         return losses
 
-    def _replayed(self, x, y, head, tail=None):
-        """graph=True: `head(x, y)` -> losses through the hipGraph of this batch SHAPE (inputs are copied into its static buffers), then
-        `tail()` eagerly (what cannot be captured: a collective and what follows it).  The first batch of a shape runs both eagerly
-        on a side stream, which warms the allocator, and then captures `head`: the capture itself does not execute."""
+    def _boundary(self):
+        """A window's boundary on its gradients -- `flat.acc` where the step accumulates, else `flat.grad`: the exchange (one all-reduce of
+        that buffer when data-parallel), the optimizer launch (step count, learning rate and the loss scaler's state are `AdamWState`'s),
+        the average's update.  Capturable on one GPU."""
+        f = self.flat
+        g = f.acc if self._window > 1 else f.grad
+        if self.world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(g, op=dist.ReduceOp.SUM, group=self.group)
+            g.div_(self.world)                     # DDP averages (train.py:66-70 runs Lightning's default DDP strategy)
+        self._opt.launch(f, self.betas, self.eps, self.wd, grad=g)
+        if self._avg is not None:
+            self._avg.update(self._opt)
+        if g is not f.grad:
+            g.zero_()                              # (also after a skipped window: its inf / nan must not reach the next one)
+
+    def _captured(self, x, y):
+        """What the hipGraph of a batch shape holds."""
+        losses = self._micro_batch(x, y)
+        if self._boundary_in == _SHAPE_GRAPH:
+            self._boundary()
+        return losses
+
+    def _replayed(self, x, y, tail):
+        """graph=True: `_captured(x, y)` -> losses through the hipGraph of this batch SHAPE (inputs are copied into its static buffers), then
+        `tail()` eagerly where there is one (what cannot be captured: a collective and what follows it).  The first batch of a shape runs
+        both eagerly on a side stream, which warms the allocator, and then captures `_captured`: the capture itself does not execute."""
         key = tuple((k, tuple(v.shape)) for k, v in sorted({**x, **{"y." + k: v for k, v in y.items()}}.items()) if torch.is_tensor(v))
         ent = self._graphs.get(key)
         if ent is None:
@@ -1047,13 +1131,13 @@ class TrainStep:
             side = torch.cuda.Stream(device=self.flat.data.device)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                out = head(sx, sy)
+                out = self._captured(sx, sy)
                 if tail is not None:
                     tail()
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                static_out = head(sx, sy)
+                static_out = self._captured(sx, sy)
             self._graphs[key] = (g, sx, sy, static_out)
             return out.clone()
         g, sx, sy, static_out = ent
@@ -1067,65 +1151,38 @@ class TrainStep:
             tail()
         return static_out.clone()
 
+    def _close_window(self, boundary_ran=False):
+        """The boundary, unless the call's graph or its tail has run it, and the one place where a window ends."""
+        if not boundary_ran:
+            if self._boundary_in != _SHARED_GRAPH:
+                self._boundary()
+            elif self._boundary_graph is not None:
+                self._boundary_graph.replay()
+            else:                                  # one graph for every window, whatever shapes its micro-batches had
+                self._boundary()                   # (this window's boundary runs eagerly: the capture itself does not execute)
+                self._boundary_graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self._boundary_graph):
+                    self._boundary()
+        self._micro = 0
+        self._packed.invalidate()
+
     def step(self, x, y, lr=None):
         """One training step.  graph=True: a hipGraph per batch SHAPE replays the step (inputs are copied into its static buffers) --
         the whole step on one GPU; data-parallel, everything up to the gradient all-reduce (the collective and the optimizer launch
         follow eagerly).  With accumulate_grad_batches=N this is one micro-batch, and every N-th call ends with the window's boundary;
         the losses returned are this micro-batch's own, undivided."""
         self._refuse_inside_ema_weights("step()")
-        lr = self.lr if lr is None else lr
-        self._opt.set_lr(lr)
-        if self._accum_n > 1:
-            out = self._micro_body(x, y) if not self.graph else self._replayed(x, y, self._micro_body)
-            self._micro += 1
-            if self._micro == self._accum_n:
-                self._boundary(lr)
-            return out
+        self._opt.set_lr(self.lr if lr is None else lr)
+        # a captured window of one runs its boundary within this call's replay: inside the shape's graph, or eagerly as its tail
+        within = self.graph and self._window == 1
         if not self.graph:
-            out = self._body(x, y, lr)
-        elif self.world == 1:
-            out = self._replayed(x, y, lambda sx, sy: self._body(sx, sy, lr))
-        else:                                      # the collective stays outside a graph
-            out = self._replayed(x, y, self._fwd_bwd, lambda: self._optimize(lr))
-        self._packed.invalidate()
-        return out
-
-    # ---- gradient accumulation (accumulate_grad_batches=N > 1)
-    def _micro_body(self, x, y):
-        """One micro-batch: everything up to the exchange, then the one launch that adds its gradients / N to the accumulator (the
-        backward overwrites `flat.grad`, so the sum cannot live there).  Capturable."""
-        losses = self._fwd_bwd(x, y)
-        f = self.flat
-        lib, st = _rt(f.data)
-        lib.esmi_train_grad_accumulate_f32(_ptr(f.acc), _ptr(f.grad), f.grad.numel(), 1.0 / self._accum_n, st)   # (1 / N rounds to fp32 once)
-        return losses
-
-    def _boundary_body(self, lr):
-        """The exchange of the accumulator (data-parallel), the optimizer launch on it, and its zeroing for the next window."""
-        f = self.flat
-        if self.world > 1:
-            import torch.distributed as dist
-            dist.all_reduce(f.acc, op=dist.ReduceOp.SUM, group=self.group)
-            f.acc.div_(self.world)
-        self._opt.launch(f, lr, self.betas, self.eps, self.wd, grad=f.acc)
-        if self._ema_decay is not None:
-            self._ema_update()
-        f.acc.zero_()                              # (also after a skipped window: its inf / nan must not reach the next one)
-
-    def _boundary(self, lr):
-        if self.graph and self.world == 1:         # one graph for every window, whatever shapes its micro-batches had
-            if self._boundary_graph is None:
-                self._boundary_body(lr)            # (this window's boundary runs eagerly: the capture itself does not execute)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._boundary_body(lr)
-                self._boundary_graph = g
-            else:
-                self._boundary_graph.replay()
+            out = self._micro_batch(x, y)
         else:
-            self._boundary_body(lr)
-        self._micro = 0
-        self._packed.invalidate()
+            out = self._replayed(x, y, self._boundary if within and self._boundary_in == _EAGER else None)
+        self._micro += 1                           # (only now: a forward that raised has left the window as it was)
+        if self._micro == self._window:
+            self._close_window(boundary_ran=within)
+        return out
 
     def flush(self, lr=None):
         """Close the open accumulation window now (Lightning's last-batch-of-the-epoch rule): the boundary on whatever has
@@ -1133,24 +1190,17 @@ class TrainStep:
         self._refuse_inside_ema_weights("flush()")
         if not self._micro:
             return False
-        lr = self.lr if lr is None else lr
-        self._opt.set_lr(lr)
-        self._boundary(lr)
+        self._opt.set_lr(self.lr if lr is None else lr)
+        self._close_window()
         return True
 
-    # ---- the weights' exponential moving average (ema_decay=d) and the validation loss
-    def _ema_update(self):
-        """ema = lerp(ema, p, 1 - d), one launch directly behind the optimizer's (capturable).  Where the optimizer keeps its scalars on
-        the device the launch reads the skip flag there: a skipped precision-16 step does not advance the average."""
-        f = self.flat
-        lib, st = _rt(f.data)
-        lib.esmi_train_ema_update_f32(_ptr(f.ema), _ptr(f.data), f.data.numel(), self._ema_weight,
-                                      _ptr(self._opt.hyper) if self._opt.on_device else None, st)
+    # ---- the weights' exponential moving average (ema_decay=d: `WeightAverage`) and the validation loss
+    _ema_open = property(lambda self: self._avg is not None and self._avg.open)
 
     def _need_ema(self, what):
-        if self._ema_decay is None:
+        if self._avg is None:
             raise AttributeError(f"no {what}: this step keeps no average of the weights (ema_decay is None)")
-        return self.flat.ema
+        return self._avg
 
     def _refuse_inside_ema_weights(self, what):
         if self._ema_open:
@@ -1160,32 +1210,21 @@ class TrainStep:
     def ema_weights(self):
         """Inside the context `net` (its inference path, `evaluate`) runs on the averaged weights: one launch exchanges the contents of
         `flat.data` and `flat.ema` on entry and one exchanges them back on exit, after which both are bitwise what they were."""
-        self._need_ema("ema_weights()")
+        avg = self._need_ema("ema_weights()")
         self._refuse_inside_ema_weights("ema_weights()")
-        self._ema_exchange()
-        self._ema_open = True
+        avg.exchange(self._packed)
+        avg.open = True
         try:
             yield self
         finally:
-            self._ema_open = False
-            self._ema_exchange()
-
-    def _ema_exchange(self):
-        f = self.flat
-        lib, st = _rt(f.data)
-        lib.esmi_train_swap_f32(_ptr(f.data), _ptr(f.ema), f.data.numel(), st)
-        self._packed.invalidate()
+            avg.open = False
+            avg.exchange(self._packed)
 
     def ema_state_dict(self):
         """The averaged weights as {'phoneme2mel.<key>': tensor}, cloned: with `hyper_parameters()` what `EfficientSpeech.load_from_checkpoint`
         needs to synthesize from the average.  Parameters outside the flat buffer (the bins, the two unreached LayerNorms) and buffers
         are `net`'s own."""
-        f = self.flat
-        avg = f.data if self._ema_open else self._need_ema("ema_state_dict()")     # (inside ema_weights() the two are exchanged)
-        sd = {"phoneme2mel." + k: v.detach().clone() for k, v in self.net.state_dict().items()}
-        for k, p, sl in zip(f.names, f.params, f.slices):
-            sd["phoneme2mel." + k] = avg[sl].view(p.shape).clone()
-        return sd
+        return self._need_ema("ema_state_dict()").weights(self.net)
 
     def evaluate(self, x, y, ema=None):
         """The loss 5-vector (`step`'s layout) of the teacher-forced forward under no_grad: a validation loss.  ema=None: on the averaged
@@ -1194,20 +1233,11 @@ class TrainStep:
         reads the weights as they are now -- and changes nothing: weights, average, gradients, moments, accumulator, counters, scaler
         and hyper block stay bitwise what they were, also inside an open accumulation window."""
         if ema is None:
-            ema = self._ema_decay is not None
+            ema = self._avg is not None
         if ema:
             self._need_ema("evaluate(ema=True)")
-        if ema and not self._ema_open:              # (inside ema_weights() the weights already are the average)
-            with self.ema_weights():
-                return self._forward_loss(x, y)
-        return self._forward_loss(x, y)
-
-    def _forward_loss(self, x, y):
-        lib0, st0 = _rt(self.flat.data)
-        with torch.no_grad(), _step_context(self.precision, False) as now:
-            if USE_MATRIX_PIPE and self._pack_n:
-                lib0.esmi_train_pack_weights_f32(self._pack_descs, self._pack_w, self._pack_n, st0)
-                now.packed_valid = True
+        on_average = self.ema_weights() if ema and not self._ema_open else contextlib.nullcontext()     # (inside ema_weights() they already are)
+        with on_average, torch.no_grad(), self._operators_in_step(False):
             parts, total = training_loss(self.net, x, y)
         return loss_vector(parts, total)
 

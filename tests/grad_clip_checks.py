@@ -112,10 +112,10 @@ def check_optimizer_launch(dev, launches=None):
         flat.grad.copy_(g)
         if launches is not None and j == 0:
             with launches() as names:
-                opt.launch(flat, LR, BETAS, EPS, WD)
+                opt.launch(flat, BETAS, EPS, WD)
             assert names == ["train_grad_sumsq_kernel", "train_bump_clip_kernel", "train_adamw_dev_kernel"]
         else:
-            opt.launch(flat, LR, BETAS, EPS, WD)
+            opt.launch(flat, BETAS, EPS, WD)
         ref = torch_clip_adamw(*ref[:3], j, g, c)
         print(f"launch {j + 1}: grad_norm {opt.grad_norm!r} (torch {ref[3]!r}), clip_coef {opt.clip_coef!r} (torch {ref[4]!r})")
         assert opt.t == j + 1 and opt.clip_coef < 1.0
@@ -140,7 +140,7 @@ def check_inactive_clip_is_bitwise_the_unclipped_launch(dev):
         opt.set_lr(LR)
         for g in grads:
             flat.grad.copy_(g)
-            opt.launch(flat, LR, BETAS, EPS, WD)
+            opt.launch(flat, BETAS, EPS, WD)
             if c is not None:
                 assert opt.clip_coef == 1.0
                 assert abs(opt.grad_norm - float(g.double().norm())) <= NORM_RTOL * float(g.double().norm())

@@ -143,14 +143,15 @@ def test_two_rank_clipped_step_clips_every_replica_by_the_same_coefficient(tmp_p
 @pytest.mark.parametrize("precision", [32, "bf16"])
 def test_clipped_step_adds_exactly_the_reduction_launch(precision):
     """Beside tests/test_train_dispatch.py's rows: the clipped step's launches are those of the unclipped step with its optimizer's
-    scalars on the device (what a captured step runs; its body is run eagerly here, capture cannot run on the simulator) plus exactly
+    scalars on the device (what a captured step runs; its micro-batch and boundary are run eagerly here, capture cannot run on the simulator) plus exactly
     one launch, the reduction, directly in front of the bookkeeping kernel -- every other record (name, grid, block, LDS) unchanged."""
     with use_sim():
         train, _, net, x, y = _setup("cpu")
         plain = train.TrainStep(net, precision=precision, graph=True)
         plain._opt.set_lr(plain.lr)
         with launch_records() as base:
-            plain._body(x, y, plain.lr)
+            plain._micro_batch(x, y)
+            plain._boundary()
         train, _, net, x, y = _setup("cpu")
         clipped = train.TrainStep(net, precision=precision, gradient_clip_val=1.0)
         n = clipped.flat.grad.numel()

@@ -5,15 +5,20 @@ The parity tests of the training step pass whichever kernels a shape lands on, s
 and pins (a) the kernels in launch order, written run-length (`6x name`), and (b) a digest of the complete launch records -- name,
 grid, block, LDS bytes -- so that a change of chunking or of a workspace layout is caught as well as a change of kernel.
 
+Below the rows, `test_schedule_across_the_option_matrix` pins what follows the micro-batch -- the accumulate launch and the window's
+boundary -- for every combination of precision, clipping, accumulation and the weight average, by rule, with nothing recorded.
+
 To re-record after an intended change of the launches: `python -m tests.test_train_dispatch` prints the table.
 """
+import functools
 import hashlib
+import itertools
 import os
 import textwrap
 
 import pytest
 
-from tests.simlib import sim_lib, use_sim
+from tests.simlib import launch_records, sim_lib, use_sim
 from tests.test_train_step import GOLD_SMALL, _setup, fused_conv_ln
 
 
@@ -474,6 +479,63 @@ def test_train_step_launches(row):
     got_count, got_digest, got = summarize(launch_log(setup))
     assert got.split() == expected.split()                 # which kernels, in which order
     assert (got_count, got_digest) == (count, digest)      # ... and every grid, block and LDS size
+
+
+# ---------------------------------------------------------------------------------------------- the schedule across the option matrix
+MATRIX = list(itertools.product((32, 16, "bf16"), (None, 1.0), (1, 2), (None, 0.9)))     # precision, clip, N, decay: the first of a precision is its base
+LAST_OF_THE_MICRO_BATCH = "train_reduce_batch_kernel"
+
+
+def _matrix_calls(precision, clip, n, decay):
+    """-> the launch records of each of the N calls of `step` that fill one window; asserts the counters after every call."""
+    train, _, net, x, y = _setup("cpu")
+    kw = {"init_scale": 1024.0} if precision == 16 else {}
+    step = train.TrainStep(net, precision=precision, gradient_clip_val=clip, accumulate_grad_batches=n, ema_decay=decay, **kw)
+    calls = []
+    for k in range(1, n + 1):
+        with launch_records() as got:
+            step.step(x, y)
+        assert step.micro == k % n and step.t == (1 if k == n else 0), (k, step.micro, step.t)
+        calls.append(got)
+    return calls
+
+
+def _split(records):
+    names = [name for name, _ in records]
+    at = len(names) - 1 - names[::-1].index(LAST_OF_THE_MICRO_BATCH)
+    return records[:at], names[at:]
+
+
+@functools.lru_cache(maxsize=None)
+def _matrix_head(precision):
+    """the records of a precision's first case (no clipping, N = 1, no average) in front of its last train_reduce_batch_kernel"""
+    (records,) = _matrix_calls(precision, None, 1, None)
+    return _split(records)[0]
+
+
+def _boundary_names(precision, clip, decay):
+    names = ["absmax_kernel"] if precision == 16 else []
+    names += ["train_grad_sumsq_kernel"] if clip else []
+    if precision == 16 or clip:                            # the optimizer's scalars on the device
+        names += ["train_bump_clip_kernel" if clip else "train_bump_step_kernel", "train_adamw_dev_kernel"]
+    else:
+        names += ["train_adamw_kernel"]
+    return names + (["train_ema_update_kernel"] if decay else [])
+
+
+@pytest.mark.parametrize("precision,clip,n,decay", MATRIX, ids=lambda v: str(v))
+def test_schedule_across_the_option_matrix(precision, clip, n, decay):
+    """Every combination of precision, clipping, accumulation and the average: each of a window's N calls launches the base case's
+    micro-batch record for record, then the accumulate launch when N > 1, and the N-th alone the boundary -- the scaler's reduction,
+    the clipping's, the optimizer in its mode, the average's update, in this order and nothing else."""
+    with use_sim():
+        head = _matrix_head(precision)
+        calls = _matrix_calls(precision, clip, n, decay)
+    for k, records in enumerate(calls, 1):
+        got_head, got_tail = _split(records)
+        assert got_head == head, (k, len(got_head), len(head))
+        want = [LAST_OF_THE_MICRO_BATCH] + (["train_grad_accumulate_kernel"] if n > 1 else [])
+        assert got_tail == want + (_boundary_names(precision, clip, decay) if k == n else []), (k, got_tail)
 
 
 if __name__ == "__main__":

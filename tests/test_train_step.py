@@ -327,7 +327,7 @@ def test_simulated_optimizer_state_counts_once_on_the_device_and_on_the_host():
             opt.t = 7
             opt.set_lr(lr)
             with launched_kernels() as names:
-                opt.launch(flat, lr, (0.9, 0.999), 1e-8, 1e-6)
+                opt.launch(flat, (0.9, 0.999), 1e-8, 1e-6)
             assert names == (["train_bump_step_kernel", "train_adamw_dev_kernel"] if graph else ["train_adamw_kernel"])
             assert opt.t == 8
             got[graph] = flat

@@ -6,7 +6,9 @@ with `cmp` (profiles/r21_train_ops_split.md: a refactor that reorders no sum mus
 
  (a) every tensor every row of tests/train_variant_checks.ROWS hands to its judge;
  (b) the losses and the flat parameter buffer after 3 steps of train.TrainStep on train.synthetic_batch, tiny at B = 2, T = 17:
-     precision 32, 16, bf16, precision 32 with gradient_clip_val, precision 32 as a captured graph (device only);
+     precision 32, 16, bf16, precision 32 with gradient_clip_val, with accumulate_grad_batches=2 (one boundary crossed, one window left open;
+     `flat.acc` too), with ema_decay (`flat.ema` too), all of these together at precision 16; precision 32, the accumulating and the combined
+     run as captured graphs (device only);
  (c) --at-size: (b)'s precision-32 runs at B = 128, T = 100, the size tools/bench_train.py is timed at (device only).
 --sim runs on the CPU wave simulator (tests/simlib.py); otherwise on cuda:0 through libesmi.so, or the library ESMI_LIB names."""
 import hashlib
@@ -49,6 +51,9 @@ def steps(dev, out, tag, B, T, **kw):
     if dev != "cpu":
         torch.cuda.synchronize()
     out.append(f"step/{tag}/params {digest(ts.flat.data)}")
+    for name in ("acc", "ema"):
+        if hasattr(ts.flat, name):
+            out.append(f"step/{tag}/{name} {digest(getattr(ts.flat, name))}")
 
 
 def main():
@@ -56,8 +61,10 @@ def main():
     path = [a for a in sys.argv[1:] if not a.startswith("--")][0]
     dev, out = ("cpu" if sim else "cuda"), []
     runs = [("p32", {}), ("p16", dict(precision="16")), ("bf16", dict(precision="bf16")), ("p32_clip", dict(gradient_clip_val=1.0))]
+    accum, every = dict(accumulate_grad_batches=2), dict(precision=16, init_scale=2048.0, gradient_clip_val=1.0, accumulate_grad_batches=2, ema_decay=0.9)
+    runs += [("p32_accum2", accum), ("p32_ema", dict(ema_decay=0.9)), ("p16_clip_accum2_ema", every)]
     if not sim:
-        runs.append(("p32_graph", dict(graph=True)))
+        runs += [("p32_graph", dict(graph=True)), ("p32_accum2_graph", dict(accum, graph=True)), ("p16_clip_accum2_ema_graph", dict(every, graph=True))]
     rows(dev, out)
     for tag, kw in runs:
         steps(dev, out, f"B2_T17/{tag}", 2, 17, **kw)
