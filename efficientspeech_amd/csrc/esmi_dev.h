@@ -75,6 +75,13 @@ __device__ __forceinline__ f32x16 mfma32_split2_wx(const u32x4& b1, const u32x4&
     c = mfma32_f16(b1, a.h1, c);
     return c;
 }
+// the same three products in the same order on a 16 x 16 tile over 32 channels (v_mfma_f32_16x16x32_f16)
+__device__ __forceinline__ f32x4 mfma16_split2_wx(const u32x4& b1, const u32x4& b2, const f16x2p& a, f32x4 c) {   // D^T
+    c = mfma16_f16(b1, a.h2, c);
+    c = mfma16_f16(b2, a.h1, c);
+    c = mfma16_f16(b1, a.h1, c);
+    return c;
+}
 
 // row of accumulator register r inside a 32-row MFMA tile
 // sum over the 32 lanes that hold one tile row (lanes sharing lane>>5); every lane ends with the same bits

@@ -60,6 +60,16 @@
 //    is searched in global memory;
 //  * dx2 = 256: LayerNorm on the K loop's accumulators -- per-(row, column slice) sums through a 1 KB-per-32-rows LDS exchange, normalised
 //    in registers, stored once (dx2 = 128: tanh rows -> tile -> barrier -> row owners read, normalise, write back).
+//  * dx2 = 128, split build: the K loops of the default (three-product) mode run on v_mfma_f32_16x16x32 tiles (4 row tiles x 2 column
+//    tiles per wave) instead of v_mfma_f32_32x32x16 (2 x 1): the same wave tile, blob, LDS bytes, weight bytes and matrix-pipe cycles,
+//    3 % MORE shader cycles, but on random activations the chip holds a 6 % higher clock under it: tiny decoder 173.1 -> 166.7 us
+//    (profiles/r25_decoder_mfma16.md; on zero activations it is 3 % slower).  The one-product modes gain nothing from it (precision 16:
+//    118.7 vs 119.0 us; bf16: 144.1 vs 146.4) and keep the 32-row form.  ESMI_DEC_MFMA16 is a mask of the modes that take the 16-row
+//    form -- 1 the default mode, 2 precision 16, 4 bf16 -- so every combination builds from this tree (-DESMI_DEC_MFMA16=0 .. 7).
+#ifndef ESMI_DEC_MFMA16
+#define ESMI_DEC_MFMA16 1
+#endif
+
 namespace esmi {
 
 constexpr int kDecWps128 = 4, kDecWeightRing256 = 2;
@@ -156,6 +166,14 @@ __device__ __forceinline__ void dec_zero_acc(f32x16 (&acc)[MT][NTW]) {
     for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
         for (int t = 0; t < NTW; ++t) acc[mt][t] = zero16();
+    }
+}
+template <int RT, int CT>
+__device__ __forceinline__ void dec_zero_acc(f32x4 (&acc)[RT][CT]) {   // (the 16-row tiles of ESMI_DEC_MFMA16)
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = zero4();
     }
 }
 

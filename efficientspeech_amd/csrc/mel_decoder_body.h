@@ -23,6 +23,9 @@
     constexpr int NV = DX2 / (4 * TPR);     // float4 per LayerNorm thread and row (channel groups c + 16k, c = lane % 16)
     constexpr bool STREAM = DX2 > 128;      // the chunk walk (see the chunk loop)
     constexpr bool LNA = DX2 > 128;         // LayerNorm on the accumulators (see ln_acc)
+    // K loops on 16x16x32 MFMA tiles (see `acc4`): ESMI_DEC_MFMA16 has one bit per precision mode -- 1 the default mode, 2 precision 16, 4 bf16
+    constexpr bool M16 = SPLIT && DX2 <= 128 && ((ESMI_DEC_MFMA16 >> (P16 ? 1 : BF ? 2 : 0)) & 1) != 0;
+    static_assert(!M16 || (MT == 2 && NTW == 1 && KCH == 1), "the 16-row form is written for the 64-frame x 32-channel wave tile");
     ESMI_DYN_LDS(lds);
     // per-layer small parameters in LDS: [taps KD*DX2 | dw_b] (group A: read by the depthwise phase) and
     // [pw_b | ln_g | ln_b | skip_g | skip_b] (group B: read by the tanh / LayerNorm phases).  Single buffer: layer l+1's
@@ -41,6 +44,7 @@
     int tid = (int)threadIdx.x, lane = lane_id();       // (re-derived per chunk below: see the chunk loop)
     const int w = uniform_i(wave_id());  // an SGPR: everything derived from the wave's place (mh, ns, weight-slice offsets) stays scalar
     int i = lane & 31, h = lane >> 5;
+    [[maybe_unused]] const int j16 = lane & 15, g16 = lane >> 4;   // M16: the lane's place in a 16x16x32 MFMA (frame j16, k group / channel quad g16)
     const int mh = w / NS, ns = w % NS;
     // XCD-aware workgroup -> (utterance, window) map: workgroup id % 8 is the XCD (round-robin dispatch), so the windows
     // of one utterance are given ids that agree mod 8 and its h0 / cum rows are fetched into ONE XCD's L2 instead of eight.
@@ -254,6 +258,12 @@
     auto row_inside = [&](int j) __attribute__((always_inline)) { return (unsigned)(fb_cur + ln_row0 + j) < (unsigned)L; };
     set_edge(f0);
     f32x16 acc[MT][NTW];
+    // M16: the same 32 registers as 4 row tiles x 2 column tiles of v_mfma_f32_16x16x32 results.  The products stay transposed (weights
+    // first), so register r of lane (j16, g16) in tile (rt, ct) is frame 16 rt + j16, channel 16 ct + 4 g16 + r of the wave's 64 x 32
+    // tile: still four consecutive channels per lane.  `acc_row` / `acc_col16` are that map; the epilogues' M16 forms go through them.
+    f32x4 acc4[M16 ? 2 * MT : 1][M16 ? 2 * NTW : 1];
+    [[maybe_unused]] auto acc_row = [&](int rt) __attribute__((always_inline)) { return 32 * MT * mh + 16 * rt + j16; };
+    [[maybe_unused]] auto acc_col16 = [&](int ct) __attribute__((always_inline)) { return ns * WCOLS + 16 * ct + 4 * g16; };
     f32x16 skipA[LNA ? MT : 1][LNA ? NTW : 1];   // LNA: the block's skip tensor in the accumulators' layout
     f32x4 skip[RPT][NV];
 #pragma unroll
@@ -269,8 +279,33 @@
     // the wave's B fragments of KSUB k-steps: the split form's two f16 planes per 16-channel step / the exact-fp32 form's float4 per k-step
     constexpr int KS16 = KSUB / 2;
     std::conditional_t<SPLIT, u32x4[NTW][KS16][NPL], f32x4[NTW][KSUB]> bf;
+    // M16: one 32-channel step of the wave's slice, column tiles [0, NCT), out of the SAME 32x32x16 packing (dec_layout.h: per 16-channel
+    // step and plane a 1 KiB slot, lane (i, h) = row i, channels 8 h .. + 7).  Operand lane (j16, g16) of column tile ct wants row
+    // 16 ct + j16, channels 8 g16 .. + 7 of the 32: lane 16 ct + j16 + 32 (g16 & 1) of the slot of step 2 S + (g16 >> 1).  The lane's byte
+    // offset `wl16` is formed once per K loop (`wlane16`; opaque: a register kept across the other phases is one the bf16 kernel spills); step,
+    // plane and column tile are SGPR / immediate offsets.  -> bf[0][ct][plane]
+    [[maybe_unused]] auto wlane16 = [&]() __attribute__((always_inline)) {
+        return (unsigned)opaque_i((j16 + 32 * (g16 & 1)) * 16 + (g16 >> 1) * (2 * 256 * 4));
+    };
+    [[maybe_unused]] auto load_b16 = [&](int wsl, int S, unsigned wl16, auto nctc) __attribute__((always_inline)) {
+        if constexpr (M16) {
+            constexpr int NCT = decltype(nctc)::value;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+                const int o = wsl + (2 * S * 2) * 256;
+                if constexpr (BF) {   // both planes -> one bfloat16 operand
+                    bf[0][ct][0] = bf16_of_f16_planes(__builtin_bit_cast(u32x4, blob_ld(o, wl16 + 256u * ct)), __builtin_bit_cast(u32x4, blob_ld(o + 256, wl16 + 256u * ct)));
+                } else {
+#pragma unroll
+                    for (int pl = 0; pl < NPL; ++pl) bf[0][ct][pl] = __builtin_bit_cast(u32x4, blob_ld(o + pl * 256, wl16 + 256u * ct));
+                }
+            }
+        }
+    };
     auto load_b = [&](int wsl, int k0) __attribute__((always_inline)) {   // wsl: float offset of the wave's weight slice in the blob
-        if constexpr (SPLIT) {
+        if constexpr (M16) {
+            load_b16(wsl, k0 >> 2, wlane16(), std::integral_constant<int, 2>{});
+        } else if constexpr (SPLIT) {
 #pragma unroll
             for (int t = 0; t < NTW; ++t) {
 #pragma unroll
@@ -295,7 +330,27 @@
     };
     // fp32 rows in the tile (the split form splits them on the fly, esmi_dev.h)
     auto mma_sub = [&](int a_col0, int k0) __attribute__((always_inline)) {
-        if constexpr (SPLIT) {
+        if constexpr (M16) {   // one 32-channel step (KSUB = 4): lane (j16, g16) splits channels 8 g16 .. + 7 of its row per row tile
+            static_assert(!M16 || (KSUB == 4 && KS16 == 2), "a weight sub-slice is one 32-channel step");
+            const float* a_base = xs + opaque_i((kDecPadRows + 32 * MT * mh + j16) * LDSROW + 8 * g16);
+#pragma unroll
+            for (int rt = 0; rt < 2 * MT; ++rt) {
+                const float* ap = a_base + 16 * rt * LDSROW + a_col0 + 8 * k0;
+                if constexpr (BF) {
+                    const u32x4 a1 = round_bf16x8(*reinterpret_cast<const f32x4*>(ap), *reinterpret_cast<const f32x4*>(ap + 4));
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) acc4[rt][ct] = mfma16_bf16(bf[0][ct][0], a1, acc4[rt][ct]);
+                } else if constexpr (P16) {
+                    const u32x4 a1 = round_f16x8(*reinterpret_cast<const f32x4*>(ap), *reinterpret_cast<const f32x4*>(ap + 4));
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) acc4[rt][ct] = mfma16_f16(bf[0][ct][0], a1, acc4[rt][ct]);
+                } else {
+                    const f16x2p a2 = split_f16x2(*reinterpret_cast<const f32x4*>(ap), *reinterpret_cast<const f32x4*>(ap + 4));
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) acc4[rt][ct] = mfma16_split2_wx(bf[0][ct][0], bf[0][ct][1], a2, acc4[rt][ct]);
+                }
+            }
+        } else if constexpr (SPLIT) {
             const float* a_base = xs + opaque_i((kDecPadRows + 32 * MT * mh + i) * LDSROW + 8 * h);
 #pragma unroll
             for (int st = 0; st < KS16; ++st) {
@@ -435,6 +490,43 @@
             }
         }
     };
+    // M16 form of the WD == 0 loop: a step is 32 channels -- its weights are loaded (as many registers as the KSUB = 4 sub-slice above),
+    // then per 16-row tile one ds_read_b128 per operand plane at k offset 8 g16 and 3 MFMAs per column tile.  Per wave and layer the
+    // same 32 KB of LDS reads, 16 KB of weights and matrix-pipe time as the 32-row form.  (The reads are NOT conflict-free: a ds_read_b128 lane
+    // group holds eight rows of k group g and the other eight of g + 1, and at a row stride of DX2 + 4 dwords one 16-byte slot of each
+    // group is hit twice: 4 extra LDS cycles per read, measured and weighed in profiles/r25_decoder_mfma16.md.)
+    // (`nctc`: 16-column tiles of THIS contraction -- 2; 1 where the mel Linear's second tile lies at or beyond n_mel)
+    [[maybe_unused]] auto gemm_planes16 = [&](int off, auto nctc) __attribute__((always_inline)) {
+        if constexpr (M16) {
+            constexpr int NCT = decltype(nctc)::value;
+            const unsigned* a_base = reinterpret_cast<const unsigned*>(xs) + opaque_i((kDecPadRows + 32 * MT * mh + j16) * LDSROW + 4 * g16);
+            const unsigned wl16 = wlane16();
+#pragma unroll
+            for (int S = 0; S < DX2 / 32; ++S) {
+                load_b16(wslice(off, 0), S, wl16, nctc);
+                if constexpr (BF) sched_fence();   // (the four row tiles' operands are not fetched across the planes' conversion: 2 spilled registers otherwise)
+#pragma unroll
+                for (int rt = 0; rt < 2 * MT; ++rt) {
+                    const unsigned* ap = a_base + 16 * rt * LDSROW + 16 * S;
+                    if constexpr (BF) {
+                        const u32x4 a1 = *reinterpret_cast<const u32x4*>(ap);
+#pragma unroll
+                        for (int ct = 0; ct < NCT; ++ct) acc4[rt][ct] = mfma16_bf16(bf[0][ct][0], a1, acc4[rt][ct]);
+                    } else if constexpr (P16) {
+                        const u32x4 a1 = *reinterpret_cast<const u32x4*>(ap);
+#pragma unroll
+                        for (int ct = 0; ct < NCT; ++ct) acc4[rt][ct] = mfma16_f16(bf[0][ct][0], a1, acc4[rt][ct]);
+                    } else {
+                        f16x2p a2;
+                        a2.h1 = *reinterpret_cast<const u32x4*>(ap);
+                        a2.h2 = *reinterpret_cast<const u32x4*>(ap + DX2 / 2);
+#pragma unroll
+                        for (int ct = 0; ct < NCT; ++ct) acc4[rt][ct] = mfma16_split2_wx(bf[0][ct][0], bf[0][ct][1], a2, acc4[rt][ct]);
+                    }
+                }
+            }
+        }
+    };
     // full dx2-wide contraction over fp32 rows of the tile, un-pipelined
     auto gemm_rows = [&](int off) __attribute__((always_inline)) {
 #pragma unroll
@@ -458,6 +550,18 @@
     // first channel of the lane's quad 0 in column tile t (quad g: + 8 g)
     auto acc_col = [&](int t) __attribute__((always_inline)) { return ns * WCOLS + 32 * t + 4 * h; };
     auto tanh_acc = [&](const float* bias) __attribute__((always_inline)) {
+        if constexpr (M16) {
+#pragma unroll
+            for (int ct = 0; ct < 2 * NTW; ++ct) {
+                const f32x4 bc = *reinterpret_cast<const f32x4*>(bias + opaque_i(acc_col16(ct))) * kTanhExpScale;
+#pragma unroll
+                for (int rt = 0; rt < 2 * MT; ++rt) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc4[rt][ct][e] = tanh_fast_fma_f32(acc4[rt][ct][e], WSI * kTanhExpScale, bc[e]);
+                }
+            }
+            return;
+        }
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
             const float* bp = bias + opaque_i(acc_col(t));
@@ -473,6 +577,15 @@
         }
     };
     auto store_acc = [&]() __attribute__((always_inline)) {
+        if constexpr (M16) {   // one ds_write_b128 per (row tile, column tile)
+            float* base = xs + opaque_i((kDecPadRows + acc_row(0)) * LDSROW + acc_col16(0));
+#pragma unroll
+            for (int ct = 0; ct < 2 * NTW; ++ct) {
+#pragma unroll
+                for (int rt = 0; rt < 2 * MT; ++rt) *reinterpret_cast<f32x4*>(base + 16 * rt * LDSROW + 16 * ct) = acc4[rt][ct];
+            }
+            return;
+        }
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
             float* base = xs + opaque_i((kDecPadRows + 32 * MT * mh + i) * LDSROW + ns * WCOLS + 32 * t + 4 * h);
@@ -663,6 +776,8 @@
     constexpr int NTM = (SPLIT && DX2 > 128) ? 1 : NTW;
     typedef std::integral_constant<int, NTW> NtwC;
     typedef std::integral_constant<int, NTM> NtmC;
+    typedef std::integral_constant<int, 1> OneC;   // (M16: 16-column tiles of a contraction)
+    typedef std::integral_constant<int, 2> TwoC;
 
     // ---- proj: Linear(d4, dx2) + Tanh + LN.  All three are row-wise, and a frame's input row is its phoneme's row: when
     // the caller supplies h0 = LN(tanh(proj(x))) at PHONEME rate (enc_fuse_va_kernel computes it while the features
@@ -718,7 +833,8 @@
         carry_put(0);
         __syncthreads();
     } else {
-        dec_zero_acc(acc);
+        if constexpr (M16) dec_zero_acc(acc4);
+        else dec_zero_acc(acc);
         const int nchunks = p.d4 / 128;
         for (int ch = 0; ch < nchunks; ++ch) {
             if (ch > 0) __syncthreads();  // previous chunk fully consumed
@@ -849,8 +965,10 @@
         __syncthreads();
         ESMI_STAMP();   // 4: barrier
         // 2. pointwise conv: K = dx2
-        dec_zero_acc(acc);
-        if constexpr (SPLIT) gemm_planes(lbase + lay.l_pw, NtwC{});
+        if constexpr (M16) dec_zero_acc(acc4);
+        else dec_zero_acc(acc);
+        if constexpr (M16) gemm_planes16(lbase + lay.l_pw, TwoC{});
+        else if constexpr (SPLIT) gemm_planes(lbase + lay.l_pw, NtwC{});
         else gemm_rows(lbase + lay.l_pw);
         ESMI_STAMP();   // 5: K loop issued
         // 3. bias + tanh on the accumulators (no tile access: ahead of the barrier), then -> tile
@@ -923,8 +1041,14 @@
     const float* mb = pbuf;                          // mel bias (zero padded to dx2)
     const bool vec_ok = (p.n_mel & 3) == 0;          // rows of 16-byte multiples: float4 stores
     if (mel_wave) {
-        dec_zero_acc(acc);
-        if constexpr (SPLIT) {
+        if constexpr (M16) dec_zero_acc(acc4);
+        else dec_zero_acc(acc);
+        if constexpr (M16) {
+            // a 16-column tile at or beyond n_mel is not computed (n_mel = 80: five tiles, the third slice's padding tile is skipped)
+            if (n_layers == 0) gemm_rows(lay.mel_w);
+            else if (ns * WCOLS + 16 < p.n_mel) gemm_planes16(lay.mel_w, TwoC{});   // (wave-uniform)
+            else gemm_planes16(lay.mel_w, OneC{});
+        } else if constexpr (SPLIT) {
             if (n_layers > 0) gemm_planes(lay.mel_w, NtmC{});
             else gemm_rows(lay.mel_w);
         } else {
@@ -974,6 +1098,32 @@
         } else {   // rows that are not 16-byte multiples: element by element
             const int n = (out_hi - f_lo) * p.n_mel;
             for (int e = tid; e < n; e += kDecThreads) dp[e] = sp[(e / p.n_mel) * mstride + e % p.n_mel];
+        }
+    } else if (M16 && mel_wave) {
+        if constexpr (M16) {
+#pragma unroll
+            for (int rt = 0; rt < 2 * MT; ++rt) {
+                const int f = g0 + acc_row(rt);
+                if (f < f_lo || f >= out_hi) continue;
+                float* orow = p.mel + ((long)b * p.L_out + f) * p.n_mel;
+                const bool live = f < valid_end;
+#pragma unroll
+                for (int ct = 0; ct < 2 * NTM; ++ct) {
+                    const int col = acc_col16(ct);
+                    if (col >= p.n_mel) continue;
+                    const f32x4 bc = *reinterpret_cast<const f32x4*>(mb + col);
+                    f32x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = live ? fmaf(acc4[rt][ct][e], WSI, bc[e]) : 0.0f;
+                    if (vec_ok) {
+                        *reinterpret_cast<f32x4*>(orow + col) = v;
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (col + e < p.n_mel) orow[col + e] = v[e];
+                    }
+                }
+            }
         }
     } else if (mel_wave) {
 #pragma unroll
